@@ -7,30 +7,37 @@ seeded synthetic weights / orbit poses (no dataset or checkpoint exists offline)
 full view through the product path (nm_render_rays: coarse intervals -> coarse MLP -> composite ->
 inverse-CDF resample -> fine MLP -> composite), ray directions already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Multi-GPU: one process per GPU.  `python bench.py --gpus N` with no launcher environment re-executes itself
+Multi-GPU: one process per GPU.  `python bench.py --gpus N` with no launcher environment runs itself again as a child
 under `torch.distributed.run --nproc-per-node N` (and exits non-zero if the node has fewer than N GPUs); under
 a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.  Default `--mode weak` (BASELINE config 3: the test set's views
 dealt to the ranks): rank r renders view (step * N + r), followed by the one real exchange step of the path, an RCCL
 all-gather of the rendered pixels (7.68 MB / rank / view).  `--mode strong`: every step is ONE view whose rays are
-split into contiguous ranges over the ranks (`dist.render_view_sharded`), total work fixed.  At N > 1 the line also
+split into contiguous ranges over the ranks (`dist.render_view_sharded`), total work fixed.  At N > 1 a `--full` line also
 carries the sharded `mesh` (config 4: axis-0 slabs of the density grid, all-gather, marching cubes; compute and
 all-gather times separately) and `buff` (config 5: ray-sharded) objects with per-rank roofline fractions.
 `--ranks-per-gpu k` (k > 1) is a FUNCTIONAL mode for boxes with fewer GPUs than ranks: k processes share each GPU over
 the gloo backend (RCCL refuses duplicate devices); the line then says `"ranks_per_gpu": k` and its rates are not scaling
 numbers.
 
-Prints ONE JSON line on rank 0 (see the task contract): metric/value, roofline of the dominant kernel
-(the fused MLP; fp32 MFMA peak 157.3 TFLOP/s), the CPU baseline (the oracle = torch-CPU port of the reference
-path, timed on this host's cores on a bounded ray sample), PSNR parity against it, and -- at N = 1 -- secondary
-objects for BASELINE configs 4 (`mesh`: 480^3 density grid + marching cubes) and 5 (`buff`: 504x378 rays x 192
-samples through the voxel-tree sampler) and one training iteration (`train`).
+Prints ONE JSON line on rank 0 (see the task contract): metric/value, ms_per_step and the roofline of the dominant
+kernel (the fused MLP; fp32 MFMA peak 157.3 TFLOP/s, from per-launch events inside the timed steps).  A plain run does
+only that.  `--full` adds everything else the benchmark measures: the CPU baseline (the oracle = torch-CPU port of the
+reference path, timed on this host's cores on a bounded ray sample), PSNR parity against it, and -- at N = 1 --
+secondary objects for BASELINE configs 4 (`mesh`: 480^3 density grid + marching cubes) and 5 (`buff`: 504x378 rays x
+192 samples through the voxel-tree sampler), one training iteration (`train`) and the others in benchlib/; at N > 1 the
+sharded `mesh` and `buff` objects.  The `--no-*` options drop single objects from a `--full` run.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its last step: DIR/rgb_map.npy
+(float32, [rays, 3]; at N > 1 the all-gathered pixels of every rank, in rank order; beyond 64 MB every k-th ray).
+Weights, poses and rays are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -70,8 +77,12 @@ def main():
     ap.add_argument("--no-eval-probe", action="store_true")
     ap.add_argument("--eval-views", type=int, default=20)
     ap.add_argument("--headline-only", action="store_true", help="skip every secondary object and the CPU legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, parity and every secondary object (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_train_probe = args.no_mesh_probe = args.no_buff_probe = args.no_b3_probe = True
         args.no_tiny_probe = args.no_eval_probe = True
 
@@ -89,7 +100,8 @@ def main():
         # no launcher: become one.  One process per rank, rendezvous on 127.0.0.1.
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        # a child process, not exec: this process has already opened the GPU (device_count above)
+        raise SystemExit(subprocess.run(cmd).returncode)
 
     # stdout carries the ONE JSON line and nothing else: whatever native libraries print there (RCCL's version banner
     # at communicator creation / teardown, which lands AFTER the line) is sent to stderr by pointing fd 1 at fd 2 and
@@ -178,6 +190,14 @@ def main():
                 "gathered_bytes_per_step": int(gathered.numel() * 4),
                 "slots_match_rank_checksums": bool(torch.allclose(slots, allv[:, 0], rtol=1e-9, atol=0)),   # fp64 sums, two reduction shapes
                 "roofline_frac_per_rank": [float(x) / FP32_MFMA_PEAK_TFLOPS for x in allv[:, 1]]}
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        rgb = gathered if use_dist else image          # the last timed step's pixels
+        rows = (64 << 20) // (rgb.shape[1] * 4)        # at most 64 MB: beyond that every k-th ray, the same ones in every run
+        if rgb.shape[0] > rows:
+            rgb = rgb[::-(-rgb.shape[0] // rows)]
+        np.save(os.path.join(args.dump_outputs, "rgb_map.npy"), rgb.float().cpu().numpy())
 
     rays_total = args.steps * H * W * views_per_step
     value = rays_total / elapsed

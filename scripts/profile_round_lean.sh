@@ -9,11 +9,14 @@
 set -u
 tag=${1:-r04}
 R=$GRAFT_REPO_ROOT
+# the bench runs below are --full runs (a plain bench.py run is the headline alone); their files go to $OUT
+OUT=${PROFILE_OUT:?set PROFILE_OUT to the folder that collects this run (the one scripts/summarize_profiles.py reads)}
+mkdir -p "$OUT"
 mkdir -p $R/gpurun_out/prof_$tag $R/gpurun_out/pmc_$tag
-cd $R && python bench.py > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err
-cp $R/bench_full.json $R/gpurun_out/bench_full_$tag.json 2>/dev/null      # every object as measured (the line is the compact form)
+cd $R && python bench.py --full > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
+cp $R/bench_full.json $OUT/bench_full_$tag.json 2>/dev/null      # every object as measured (the line is the compact form)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$tag -o bench --output-format csv -- python $R/bench.py --no-cpu-baseline > $R/gpurun_out/bench_${tag}_profiled.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_$tag -o bench --output-format csv -- python $R/bench.py --full --no-cpu-baseline > $OUT/bench_${tag}_profiled.log 2>&1
 for group in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   name=$(echo $group | cut -d' ' -f1)
   rocprofv3 --pmc $group --kernel-trace -d $R/gpurun_out/pmc_$tag/$name -o pmc --output-format csv -- python $R/bench.py --headline-only --steps 1 --warmup 0 > $R/gpurun_out/pmc_$tag/$name.log 2>&1

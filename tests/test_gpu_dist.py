@@ -78,6 +78,25 @@ def test_bench_refuses_more_gpus_than_visible():
     assert '"n_gpus"' not in r.stdout, "no bench line may be printed for a run that could not happen"
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` run measures the headline alone (everything else takes `--full`), `--steps` is the number of timed
+    steps, `ms_per_step` the time of one, and `--dump-outputs` writes the pixels the last timed step rendered."""
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(printed) == 1, printed
+    line = json.loads(printed[0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "rays/s" and line["dtype"] == "f32"
+    assert abs(line["value"] - 640000 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    for name in ("cpu_baseline", "parity", "mesh", "buff", "eval", "tiny", "train", "bf16x3"):
+        assert name not in line, name
+    import numpy as np
+    rgb = np.load(tmp_path / "rgb_map.npy")
+    assert rgb.shape == (640000, 3) and rgb.dtype == np.float32 and np.isfinite(rgb).all()
+    assert rgb.min() >= 0.0 and rgb.max() <= 1.0 + 1e-5 and rgb.std() > 0
+
+
 def test_bench_rccl_leg_on_one_rank():
     """bench.py under a launcher environment of ONE rank: RCCL is initialised, the pixels go through the all-gather,
     and the line says how many ranks the collective saw."""
@@ -93,12 +112,12 @@ def test_bench_rccl_leg_on_one_rank():
 
 @pytest.mark.parametrize("mode", ["weak", "strong"])
 def test_bench_two_ranks_on_one_gpu_carries_the_sharded_objects(mode):
-    """`python bench.py --gpus 1 --ranks-per-gpu 2` (self-launching, gloo): the N > 1 legs of BASELINE configs 3 / 4 / 5
+    """`python bench.py --gpus 1 --ranks-per-gpu 2 --full` (self-launching, gloo): the N > 1 legs of BASELINE configs 3 / 4 / 5
     -- views dealt to the ranks or one view's rays split over them, the slab-sharded density grid + all-gather +
     marching cubes (bitwise vs the C oracle in-run), the ray-sharded BuFF view -- all present on the line, with
     per-rank roofline fractions, and labelled as a functional (not a scaling) run."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--ranks-per-gpu", "2", "--steps", "1", "--warmup", "1",
-                        "--mode", mode, "--mesh-res", "120", "--no-cpu-baseline"],
+                        "--mode", mode, "--mesh-res", "120", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -139,7 +158,7 @@ def test_bench_line_survives_a_failing_secondary_object_at_two_ranks(inject, exp
     env = _env()
     env["NM_BENCH_INJECT_FAILURE"] = inject
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--ranks-per-gpu", "2", "--steps", "1", "--warmup", "1",
-                        "--mesh-res", "60", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--mesh-res", "60", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(printed) == 1, (printed, r.stderr[-3000:])
     line = json.loads(printed[0])
@@ -153,11 +172,11 @@ def test_bench_line_survives_a_failing_secondary_object_at_two_ranks(inject, exp
 
 
 def test_bench_eight_ranks_on_one_gpu():
-    """`python bench.py --gpus 1 --ranks-per-gpu 8 --mesh-res 120`: the exact launch shape of the driver's 8-GPU scaling run
+    """`python bench.py --gpus 1 --ranks-per-gpu 8 --mesh-res 120 --full`: the exact launch shape of the driver's 8-GPU scaling run
     (8 ranks, views dealt to the ranks, 8-way slab split of the mesh grid, ray-sharded BuFF view) rehearsed on one GPU over
     gloo -- a functional run: its rates say nothing about scaling, its objects must all be there and consistent."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--ranks-per-gpu", "8", "--steps", "1", "--warmup", "1",
-                        "--mesh-res", "120", "--no-cpu-baseline"],
+                        "--mesh-res", "120", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
