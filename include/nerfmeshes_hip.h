@@ -42,6 +42,8 @@ extern "C" {
 /* 6 (round 6): + nm_mlp_backward_fused (+ _supported, _workspace_bytes, nm_mlp_param_grads): the 64-wide networks' whole
  * backward in one kernel; nm_mlp_tape.v_stride (0 = contiguous rows of d_v, as before); nm_mlp_backward_ex (flags),
  * nm_mlp_export_xyz_weight.  No signature changed. */
+/* 6, later: + nm_mlp_sample_density, nm_mc_vertex_edges, nm_mc_edge_points, nm_mc_refine_vertices (mesh_nerf
+ * --super-sampling).  Additions only: no struct and no signature changed, so the version stays 6. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -137,6 +139,11 @@ int nm_mlp_eval_rays(nm_mlp* mlp, const float* d_origins, int origins_per_ray, c
 int nm_mlp_grid_query(nm_mlp* mlp, const float* d_ax0, const float* d_ax1, const float* d_ax2,
                       int32_t n0, int32_t n1, int32_t n2, int64_t first, int64_t count,
                       int32_t density_only, float* d_out, void* stream);
+
+/* Raw sigma of arbitrary points: d_points (n,3) -> d_sigma (n,), exactly what nm_mlp_grid_query(density_only = 1) writes
+ * for the same fp32 triple (the point is its own view direction, as in the grid mode; sigma does not depend on it).  Every
+ * fp32 kernel family; bf16x3 handles are rejected (geometry is fp32 by contract). */
+int nm_mlp_sample_density(nm_mlp* mlp, const float* d_points, int64_t n, float* d_sigma, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Ray-batch primitives
@@ -574,6 +581,36 @@ int nm_mc_emit_slab(const float* d_volume, int32_t n0, int32_t n1, int32_t n2, d
                     int32_t ghost_below, int32_t ghost_above, void* d_workspace, void* d_vertex_scratch, int64_t vertices,
                     int64_t faces, int64_t ghost_vertices, int64_t ghost_faces, int64_t index_base, float* d_verts,
                     int32_t* d_faces, float* d_normals, float* d_values, void* stream);
+
+/* Super-sampled marching cubes (mesh_nerf --super-sampling ss; the reference's src/mesh_nerf.py:95-128 is dead code, the
+ * semantics are DESIGN.md's): the plain mesh's topology, normals and values, with every EDGE vertex moved along its own
+ * edge to the first sign change among the ss interior samples of that edge.  Keys name a vertex's edge:
+ *   key = global linear index of the lower-corner voxel * 4 + axis, axis in ARRAY order (0 = axis 0, the slowest, and
+ *   the first vertex column); axis 3 = the centre vertex of an MC33 tiling (the key's voxel is then its cube's origin).
+ *
+ * nm_mc_vertex_edges: after nm_mc_emit / nm_mc_emit_slab, with the same dims, z_global and d_vertex_scratch, and the
+ *   `vertices` / `ghost_vertices` that call was given (0 for nm_mc_emit; they fix the scratch's layout), writes the key of
+ *   each of the call's own vertex rows: d_keys (vertices - ghost_vertices,), row r = the emit's row r.  The scratch keeps
+ *   these values until it is reused.
+ * nm_mc_edge_points: d_keys (V,) of a global (n0,n1,n2) grid -> d_points (V,ss,3): interior sample s = 1..ss of the edge of
+ *   the voxel (i0,i1,i2) along array axis a is the point whose coordinate a is fine_a[i_a*(ss+1) + s], the others base.
+ *   d_base_a has n_a entries, d_fine_a (n_a-1)*(ss+1)+1 (linspace(-limit, limit, .) in fp32).  Centre rows get an in-range
+ *   point, which refinement ignores.  ss = 0 writes nothing (d_points and the fine axes may then be NULL).
+ * nm_mc_refine_vertices: d_volume holds the global planes [z_global, z_global + n0) of the grid (a slab, or the whole grid
+ *   with z_global = 0); d_fine_sigma (V,ss) the densities of those points.  For each edge row: d_0 = v_lo - iso,
+ *   d_1..d_ss = fine - iso, d_ss+1 = v_hi - iso (fp64); m = the first index with (d_m > 0) != (d_m+1 > 0);
+ *   w1 = 1/(eps + |d_m|), w2 = 1/(eps + |d_m+1|) (eps = skimage's 2^-52); column a of d_verts (V,3) becomes
+ *   i_a + (m + w2/(w1+w2)) / (ss+1), rounded to fp32 once.  Centre rows are untouched.  With ss = 0 (d_fine_sigma = NULL)
+ *   this is nm_mc_emit's own interpolation, bit for bit.
+ * ss is in [0, 64]; every fine axis must fit int32.  One thread per vertex, no workspace, no host synchronisation. */
+int nm_mc_vertex_edges(const void* d_vertex_scratch, int64_t vertices, int64_t ghost_vertices, int32_t n0, int32_t n1,
+                       int32_t n2, int32_t z_global, int64_t* d_keys, void* stream);
+int nm_mc_edge_points(const int64_t* d_keys, int64_t V, int32_t n0, int32_t n1, int32_t n2, int32_t ss,
+                      const float* d_base0, const float* d_base1, const float* d_base2, const float* d_fine0,
+                      const float* d_fine1, const float* d_fine2, float* d_points, void* stream);
+int nm_mc_refine_vertices(const float* d_volume, int32_t n0, int32_t n1, int32_t n2, int32_t z_global, double iso,
+                          const int64_t* d_keys, int64_t V, int32_t ss, const float* d_fine_sigma, float* d_verts,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mesh export: export_obj (src/nerf/nerf_helpers.py:86-111), byte-identical text.  HOST arrays:

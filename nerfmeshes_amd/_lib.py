@@ -81,6 +81,7 @@ SIGNATURES = {
     "nm_mlp_profile_enable": (C.c_int, [C.c_int]),
     "nm_mlp_profile_read": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nm_mlp_sample_points": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]),
+    "nm_mlp_sample_density": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]),
     "nm_mlp_eval_rays": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, C.c_int64, C.c_int32, c_void_p,
                                    c_void_p]),
     "nm_mlp_grid_query": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -173,6 +174,12 @@ SIGNATURES = {
     "nm_mc_emit_slab": (C.c_int, [c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_void_p,
                                   c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "nm_mc_vertex_edges": (C.c_int, [c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_p,
+                                     c_void_p]),
+    "nm_mc_edge_points": (C.c_int, [c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mc_refine_vertices": (C.c_int, [c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, c_void_p,
+                                        C.c_int64, C.c_int32, c_void_p, c_void_p, c_void_p]),
     "nm_export_obj": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64,
                                 C.c_char_p]),
 }

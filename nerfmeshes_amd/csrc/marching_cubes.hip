@@ -1068,6 +1068,26 @@ __global__ __launch_bounds__(256) void mc_vertex_attributes(const float* __restr
     out.values[vid] = value;
 }
 
+// ---- edge keys of the emitted vertices (super-sampled meshing, mc_refine.hip) -----------------------------------------
+// key = global linear voxel of the edge's lower corner * 4 + axis in ARRAY order (edge_axis numbers x first, as skimage:
+// array axis = 2 - edge_axis); 3 = the centre vertex, keyed by its cube's origin voxel.
+__global__ __launch_bounds__(256) void mc_vertex_keys(McDims d, int zg0, const int64_t* __restrict__ vertex_cube,
+                                                      const int8_t* __restrict__ vertex_edge, int64_t nverts,
+                                                      int64_t* __restrict__ keys) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nverts) return;
+    const int e = vertex_edge[r];
+    int z, y, x;
+    cube_coords(d, vertex_cube[r] & MC_ID_MASK, z, y, x);    // ids decode with the cube extents of any layer count
+    int axis = 3;
+    if (e != 12) {
+        const int lo = edge_lo(e);
+        z += lo >> 2; y += (lo >> 1) & 1; x += lo & 1;
+        axis = 2 - edge_axis(e);
+    }
+    keys[r] = ((((int64_t)(z + zg0)) * d.n1 + y) * d.n2 + x) * 4 + axis;
+}
+
 static inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct McWorkspace {
@@ -1312,6 +1332,25 @@ int nm_mc_emit(const float* d_volume, int32_t n0, int32_t n1, int32_t n2, double
                float* d_normals, float* d_values, void* stream_) {
     return nm_mc_emit_slab(d_volume, n0, n1, n2, iso, 0, 0, 0, d_workspace, d_vertex_scratch, vertices, faces, 0, 0, 0, d_verts,
                            d_faces, d_normals, d_values, stream_);
+}
+
+int nm_mc_vertex_edges(const void* d_vertex_scratch, int64_t vertices, int64_t ghost_vertices, int32_t n0, int32_t n1,
+                       int32_t n2, int32_t z_global, int64_t* d_keys, void* stream_) {
+    NM_REQUIRE(n0 >= 2 && n1 >= 2 && n2 >= 2, "Input array must be at least 2x2x2.");
+    NM_REQUIRE(z_global >= 0 && (int64_t)z_global + n0 <= (int64_t(1) << 31), "mc keys: bad global plane index");
+    NM_REQUIRE(vertices >= 0 && ghost_vertices >= 0 && ghost_vertices <= vertices, "mc keys: bad vertex counts");
+    const int64_t own_v = vertices - ghost_vertices;
+    NM_REQUIRE(own_v == 0 || (d_vertex_scratch && d_keys), "bad argument");
+    if (own_v == 0) return 0;
+    const McDims d = make_dims(n0, n1, n2);
+    NM_REQUIRE(d.cubes < (int64_t(1) << 40), "volume too large");
+    // the layout nm_mc_emit_slab gave the scratch for `vertices` rows
+    const int64_t* vertex_cube = static_cast<const int64_t*>(d_vertex_scratch);
+    const int8_t* vertex_edge = reinterpret_cast<const int8_t*>(static_cast<const char*>(d_vertex_scratch) + al((size_t)vertices * 8));
+    hipLaunchKernelGGL(mc_vertex_keys, dim3((unsigned)((own_v + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream_), d,
+                       (int)z_global, vertex_cube, vertex_edge, own_v, d_keys);
+    NM_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 }  // extern "C"

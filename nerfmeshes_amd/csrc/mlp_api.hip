@@ -910,6 +910,18 @@ int nm_mlp_sample_points(nm_mlp* m, const float* d_points, const float* d_dirs, 
     return launch_mlp_timed(m, a, 0, static_cast<hipStream_t>(stream));
 }
 
+// MODE_POINTS with density_only = 1: every family writes out[sample] = sigma in that mode.  The point doubles as the view
+// direction (as in MODE_GRID); the density-only trunk never reads it.
+int nm_mlp_sample_density(nm_mlp* m, const float* d_points, int64_t n, float* d_sigma, void* stream) {
+    NM_REQUIRE(m && d_points && d_sigma && n >= 0, "bad argument");
+    NM_REQUIRE(m->precision == NM_PREC_F32, "sample_density: geometry is fp32 by contract (bf16x3 handle)");
+    MlpArgs a = m->base;
+    a.mode = MODE_POINTS;
+    a.a = d_points; a.b = d_points; a.c = nullptr;
+    a.n = n; a.out = d_sigma;
+    return launch_mlp_timed(m, a, 1, static_cast<hipStream_t>(stream));
+}
+
 int nm_mlp_eval_rays(nm_mlp* m, const float* d_origins, int origins_per_ray, const float* d_dirs, const float* d_t,
                      int64_t rays, int32_t samples, float* d_radiance, void* stream) {
     NM_REQUIRE(m && d_origins && d_dirs && d_t && d_radiance && rays >= 0 && samples > 0, "bad argument");

@@ -247,7 +247,7 @@ def slab_layers(n0, rank, world_size):
     return lo, hi, below, above, lo - below, hi + 1 + above
 
 
-def marching_cubes_sharded(query_fn, n0, n1, n2, iso_fn):
+def marching_cubes_sharded(query_fn, n0, n1, n2, iso_fn, refine=None):
     """Mesh of an (n0, n1, n2) density grid without assembling the grid anywhere (BASELINE north_star: "all-gather of ...
     emitted triangles"; replaces the grid all-gather in front of marching cubes, /root/reference/src/mesh_nerf.py:73-79).
     Rank r evaluates the planes of its own cube layers plus one ghost plane on either side -- `query_fn(p_lo, p_hi)` ->
@@ -257,6 +257,8 @@ def marching_cubes_sharded(query_fn, n0, n1, n2, iso_fn):
     index, vertex ids offset by the vertex counts of the lower ranks, which are all-gathered), and the four arrays travel
     in ONE all-gather of a packed byte buffer per rank: 2 collectives at any world size (+ 2 for a whole-grid iso level,
     `hip_ops.np_stats_sharded`).  The result equals the single-GPU mesh bit for bit, vertex numbering included.
+    `refine(slab, p_lo, iso, verts, keys)` (optional) may move the slab's own vertices in place before they are packed (the
+    super-sampled mesh: mesh_nerf.refine_vertices; keys = hip_ops.marching_cubes_slab's edge keys); None changes nothing.
     Returns (vertices, faces, normals, values, local slab (planes p_lo .. p_hi))."""
     from . import hip_ops
     rank, ws = world()
@@ -283,7 +285,11 @@ def marching_cubes_sharded(query_fn, n0, n1, n2, iso_fn):
     if empty:
         payload = torch.empty(0, dtype=torch.uint8, device=dev)
     else:
-        v, f, nrm, val = piece.emit(sum(nv[:rank]) - piece.ghost_vertices)       # (verts, faces, normals, values)
+        if refine is None:
+            v, f, nrm, val = piece.emit(sum(nv[:rank]) - piece.ghost_vertices)       # (verts, faces, normals, values)
+        else:
+            v, f, nrm, val, keys = piece.emit(sum(nv[:rank]) - piece.ghost_vertices, return_keys=True)
+            refine(slab, p_lo, iso, v, keys)
         payload = torch.cat([t.contiguous().view(-1).view(torch.uint8) for t in (v, nrm, val, f)])
     # every rank's part ends in a 4-byte status word: a rank whose emit disagrees with the counts it announced still joins the
     # collective (with zeros of the promised size) -- raising before it would leave the other ranks inside the all-gather for

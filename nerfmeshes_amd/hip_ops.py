@@ -154,6 +154,15 @@ class HipMLP:
               "nm_mlp_sample_points")
         return out.reshape(*lead, 4)
 
+    def sample_density(self, points):
+        """Raw sigma (n,) of the points (..., 3) (nm_mlp_sample_density): grid_query(density_only=True)'s value for the same
+        fp32 triple, at arbitrary positions (the super-sampled mesh's edge samples).  fp32 handles only."""
+        points = _dev32(points, self.device, "points").reshape(-1, 3)
+        out = torch.empty(points.shape[0], dtype=torch.float32, device=self.device)
+        check(self._lib.nm_mlp_sample_density(self._h, _ptr(points), points.shape[0], _ptr(out), _stream()),
+              "nm_mlp_sample_density")
+        return out
+
     def eval_rays(self, origins, dirs, t):
         origins, dirs, t = (_dev32(x, self.device) for x in (origins, dirs, t))
         rays, samples = t.shape
@@ -494,10 +503,11 @@ def _mc_outputs(nv, nf, dev):
     return out, ptrs, views
 
 
-def marching_cubes(volume, level):
+def marching_cubes(volume, level, return_keys=False):
     """skimage.measure.marching_cubes(volume, level) on the GPU (nm_mc_count + nm_mc_emit).
     volume: (n0,n1,n2) fp32 CUDA tensor.  Returns (verts (V,3) f32, faces (F,3) i32, normals (V,3) f32,
-    values (V,) f32) as CUDA tensors; raises ValueError / RuntimeError exactly where skimage does."""
+    values (V,) f32) as CUDA tensors; raises ValueError / RuntimeError exactly where skimage does.
+    return_keys: also return the (V,) int64 edge keys of the vertices (nm_mc_vertex_edges; see mc_edge_points)."""
     lib = _lib.load()
     if not isinstance(volume, torch.Tensor) or volume.dim() != 3:
         raise ValueError("Input volume should be a 3D tensor.")
@@ -524,6 +534,10 @@ def marching_cubes(volume, level):
     check(lib.nm_mc_emit(p_vol, n0, n1, n2, level, p_ws, _ptr(scratch), nv.value, nf.value, p_verts, p_faces, p_normals,
                          p_values, stream), "nm_mc_emit")
     verts, faces, normals, values = views()
+    if return_keys:
+        keys = torch.empty(nv.value, dtype=torch.int64, device=dev)
+        check(lib.nm_mc_vertex_edges(_ptr(scratch), nv.value, 0, n0, n1, n2, 0, _ptr(keys), stream), "nm_mc_vertex_edges")
+        return verts, faces, normals, values, keys
     return verts, faces, normals, values
 
 
@@ -531,7 +545,8 @@ def marching_cubes_slab(volume, level, z_global, ghost_below, ghost_above):
     """Marching cubes of ONE axis-0 slab of a larger grid (nm_mc_count_slab / nm_mc_emit_slab).  `volume` holds the global
     planes [z_global, z_global + n0); its first cube layer is a ghost of the slab below (`ghost_below`), its last one a ghost
     of the slab above (`ghost_above`).  Returns an object with `.vertices` (the slab's own vertex count), `.faces`,
-    `.ghost_vertices`, and `.emit(index_base)` -> (verts, faces, normals, values) with face entries = local id + index_base.
+    `.ghost_vertices`, and `.emit(index_base)` -> (verts, faces, normals, values) with face entries = local id + index_base
+    (`.emit(index_base, return_keys=True)` appends the (V,) int64 edge keys of the slab's own vertices, global voxel indices).
     Concatenating the ranks' arrays in rank order, with index_base = (own vertex counts of all lower ranks) - ghost_vertices,
     gives the mesh of the whole grid bit for bit (dist.marching_cubes_sharded does that)."""
     lib = _lib.load()
@@ -551,17 +566,76 @@ def marching_cubes_slab(volume, level, z_global, ghost_below, ghost_above):
         ghost_vertices, ghost_faces = gv.value, gf.value
 
         @staticmethod
-        def emit(index_base):
+        def emit(index_base, return_keys=False):
             verts = torch.empty(Slab.vertices, 3, dtype=torch.float32, device=dev)
             normals = torch.empty(Slab.vertices, 3, dtype=torch.float32, device=dev)
             values = torch.empty(Slab.vertices, dtype=torch.float32, device=dev)
             faces = torch.empty(Slab.faces, 3, dtype=torch.int32, device=dev)
+            keys = torch.empty(Slab.vertices, dtype=torch.int64, device=dev)
             if nv.value:
                 scratch = torch.empty(int(lib.nm_mc_vertex_scratch_bytes(nv.value, nf.value)) + 256, dtype=torch.uint8, device=dev)
                 check(lib.nm_mc_emit_slab(_ptr(vol), n0, n1, n2, level, int(z_global), int(bool(ghost_below)), int(bool(ghost_above)),
                                           _ptr(ws), _ptr(scratch), nv.value, nf.value, gv.value, gf.value, int(index_base),
                                           _ptr(verts), _ptr(faces), _ptr(normals), _ptr(values), _stream()), "nm_mc_emit_slab")
+                if return_keys:
+                    check(lib.nm_mc_vertex_edges(_ptr(scratch), nv.value, gv.value, n0, n1, n2, int(z_global), _ptr(keys), _stream()),
+                          "nm_mc_vertex_edges")
+            if return_keys:
+                return verts, faces, normals, values, keys
             return verts, faces, normals, values
 
     return Slab
 
+
+SS_MAX = 64
+
+
+def fine_axis(limit, n, ss):
+    """The fine axis of super-sampling ss over a base axis of n points: linspace(-limit, limit, (n-1)*(ss+1)+1) in fp32 on the
+    host, as mesh_nerf._axes builds the base axes; base point i is fine point i*(ss+1) (up to fp32 rounding of linspace)."""
+    return torch.linspace(-limit, limit, (n - 1) * (ss + 1) + 1)
+
+
+def check_super_sampling(nums, ss):
+    """ValueError unless 1 <= ss <= 64 and every fine axis fits int32."""
+    if not 1 <= int(ss) <= SS_MAX:
+        raise ValueError(f"--super-sampling must be in [1, {SS_MAX}] (0 = off), got {ss}")
+    if any((n - 1) * (ss + 1) + 1 > 2 ** 31 - 1 for n in nums):
+        raise ValueError(f"--super-sampling {ss}: a fine axis of the grid {tuple(nums)} does not fit int32")
+
+
+def mc_edge_points(keys, nums, ss, base, fine):
+    """(V, ss, 3) fp32: the ss interior samples of every vertex's edge (nm_mc_edge_points).  keys: (V,) int64 of a global
+    (n0,n1,n2) grid; base / fine: the three base / fine axes (any device; copied to the keys' device)."""
+    lib = _lib.load()
+    dev = keys.device
+    n0, n1, n2 = (int(n) for n in nums)
+    V = int(keys.numel())
+    base = [_dev32(a, dev) for a in base]
+    fine = [_dev32(a, dev) for a in fine]
+    if [a.numel() for a in base] != [n0, n1, n2] or [a.numel() for a in fine] != [(n - 1) * (ss + 1) + 1 for n in (n0, n1, n2)]:
+        raise ValueError("mc_edge_points: axis lengths do not match the grid and the super-sampling")
+    points = torch.empty(V, ss, 3, dtype=torch.float32, device=dev)
+    keys = keys.contiguous()
+    check(lib.nm_mc_edge_points(_ptr(keys), V, n0, n1, n2, int(ss), *[_ptr(a) for a in base], *[_ptr(a) for a in fine],
+                                _ptr(points), _stream()), "nm_mc_edge_points")
+    return points
+
+
+def mc_refine_vertices(volume, z_global, level, keys, ss, fine_sigma, verts):
+    """Moves every edge vertex of `verts` (V,3) fp32 (grid-index units, in place) along its edge to the first sign change of
+    (volume, fine_sigma (V, ss), volume) against `level` (nm_mc_refine_vertices).  `volume` holds the global planes
+    [z_global, z_global + n0).  ss = 0 reproduces marching_cubes' own vertices.  Returns verts."""
+    lib = _lib.load()
+    vol = _dev32(volume, name="volume")
+    n0, n1, n2 = vol.shape
+    if verts.dtype != torch.float32 or not verts.is_contiguous() or verts.device != vol.device:
+        raise ValueError("mc_refine_vertices: verts must be a contiguous fp32 tensor on the volume's device")
+    V = int(keys.numel())
+    if verts.shape != (V, 3) or (ss and tuple(fine_sigma.shape[:1]) != (V,)):
+        raise ValueError("mc_refine_vertices: keys, fine_sigma and verts disagree on the vertex count")
+    sig = _dev32(fine_sigma, vol.device).reshape(V, ss) if ss else None
+    keys = keys.contiguous()
+    check(lib.nm_mc_refine_vertices(_ptr(vol), n0, n1, n2, int(z_global), float(level), _ptr(keys), V, int(ss), _ptr(sig),
+                                    _ptr(verts), _stream()), "nm_mc_refine_vertices")
+    return verts
