@@ -44,6 +44,8 @@ extern "C" {
  * nm_mlp_export_xyz_weight.  No signature changed. */
 /* 6, later: + nm_mlp_sample_density, nm_mc_vertex_edges, nm_mc_edge_points, nm_mc_refine_vertices (mesh_nerf
  * --super-sampling).  Additions only: no struct and no signature changed, so the version stays 6. */
+/* 6, later: + nm_mlp_density_grad (+ _workspace_bytes): d sigma / d x at arbitrary points (mesh_nerf --normals network).
+ * Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -144,6 +146,20 @@ int nm_mlp_grid_query(nm_mlp* mlp, const float* d_ax0, const float* d_ax1, const
  * for the same fp32 triple (the point is its own view direction, as in the grid mode; sigma does not depend on it).  Every
  * fp32 kernel family; bf16x3 handles are rejected (geometry is fp32 by contract). */
 int nm_mlp_sample_density(nm_mlp* mlp, const float* d_points, int64_t n, float* d_sigma, void* stream);
+
+/* d sigma / d x of the raw sigma nm_mlp_sample_density returns, at arbitrary points: d_points (n,3) -> d_grad (n,3)
+ * (nerf_input_grad.hip).  The gradient runs through fc_alpha (row 3 of fc_out without view directions), every layers_xyz[i] and
+ * its ReLU (ReLU'(0) = 0, as torch), the skip layers' encoding columns, layer1 and the positional encoding
+ * [x | sin(b_k x_c) | cos(b_k x_c)] (src/nerf/models.py:60-80, src/nerf/modules.py:26-34); sigma does not depend on the view
+ * direction.  The matrix work is the training path's (nm_mlp_forward_train, nm_mlp_backward_ex seeded with d radiance =
+ * (0, 0, 0, 1)) plus one fp32 MFMA kernel that contracts the deltas with the weights of the encoding columns and the
+ * encoding's Jacobian, every weight out of the handle's packed image.  A point's result depends on that point and the packed
+ * weights only -- not on n, its offset or the chunking (the entry chunks internally; a layer-wise handle always runs whole
+ * fixed-size chunks).  Every fp32 handle; bf16x3 handles are rejected.  The workspace is bounded whatever n is: ask
+ * nm_mlp_density_grad_workspace_bytes (0 for n = 0). */
+int64_t nm_mlp_density_grad_workspace_bytes(const nm_mlp* mlp, int64_t n);
+int nm_mlp_density_grad(nm_mlp* mlp, const float* d_points, int64_t n, void* d_workspace, int64_t workspace_bytes,
+                        float* d_grad /* (n,3) */, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Ray-batch primitives

@@ -82,6 +82,8 @@ SIGNATURES = {
     "nm_mlp_profile_read": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nm_mlp_sample_points": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]),
     "nm_mlp_sample_density": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]),
+    "nm_mlp_density_grad_workspace_bytes": (C.c_int64, [c_void_p, C.c_int64]),
+    "nm_mlp_density_grad": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p]),
     "nm_mlp_eval_rays": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, C.c_int64, C.c_int32, c_void_p,
                                    c_void_p]),
     "nm_mlp_grid_query": (C.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, C.c_int32, C.c_int32, C.c_int32,

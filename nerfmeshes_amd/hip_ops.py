@@ -163,6 +163,20 @@ class HipMLP:
               "nm_mlp_sample_density")
         return out
 
+    def density_gradient(self, points):
+        """d sigma / d x (n, 3) of sample_density's raw sigma at the points (..., 3) (nm_mlp_density_grad): the taping forward
+        and the delta chain of the training path, then one kernel through the encoding columns and the positional encoding.  A
+        point's result depends on that point and the packed weights only (not on the count, its offset or the chunking).  fp32
+        handles only."""
+        points = _dev32(points, self.device, "points").reshape(-1, 3)
+        n = points.shape[0]
+        out = torch.empty(n, 3, dtype=torch.float32, device=self.device)
+        nbytes = int(self._lib.nm_mlp_density_grad_workspace_bytes(self._h, n))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+        check(self._lib.nm_mlp_density_grad(self._h, _ptr(points), n, _ptr(ws), max(nbytes, 0), _ptr(out), _stream()),
+              "nm_mlp_density_grad")
+        return out
+
     def eval_rays(self, origins, dirs, t):
         origins, dirs, t = (_dev32(x, self.device) for x in (origins, dirs, t))
         rays, samples = t.shape

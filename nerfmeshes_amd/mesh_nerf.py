@@ -255,10 +255,28 @@ def extract_geometry_with_super_sampling(model, device, args):
     return vertices, triangles, normals, density
 
 
+def network_normals(net, vertices, normals):
+    """`--normals network`: n = -grad / |grad| of the network's raw sigma at the world-space vertices (HipMLP.density_gradient),
+    normalised in fp32 -- towards lower density, the orientation of skimage's default (gradient_direction="descent") and so of
+    the grid normals.  A vertex whose gradient is zero or not finite keeps its grid normal.  -> (normals (V,3), kept (V,) bool:
+    the vertices that kept theirs)."""
+    normals = normals.to(dtype=torch.float32)
+    if vertices.shape[0] == 0:
+        return normals.reshape(0, 3), torch.zeros(0, dtype=torch.bool, device=normals.device)
+    g = net.density_gradient(vertices)
+    norm = torch.linalg.vector_norm(g, dim=1, keepdim=True)
+    ok = torch.isfinite(norm) & (norm > 0)
+    return torch.where(ok, -g / norm, normals.to(g.device)), ~ok[:, 0]
+
+
 def export_marching_cubes(model, args, cfg, device):
     """mesh_nerf.py:131-201.  `--super-sampling N >= 1` refines the geometry (extract_geometry_with_super_sampling); the
-    appearance, the cache and the OBJ are the same steps as without it."""
+    appearance, the cache and the OBJ are the same steps as without it.  `--normals network` replaces the geometry stage's grid
+    normals by the network's (network_normals) before the appearance query and the OBJ; the cache keeps the grid normals."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
+    normals_mode = getattr(args, "normals", "grid")
+    if normals_mode == "network" and getattr(args, "route", "kernel") == "script":
+        raise ValueError("--normals network has no --route script: the reference's script only has the grid's normals")
     from . import dist as nd
     cache_path = os.path.join(args.save_dir, args.cache_name)
     cached = os.path.exists(cache_path)
@@ -278,13 +296,21 @@ def export_marching_cubes(model, args, cfg, device):
                             density.cpu().numpy() if isinstance(density, torch.Tensor) else density), cache_path)
                 print(f"Cached mesh geometry saved to {cache_path}")
 
-    if getattr(args, "precision", "f32") != "f32":     # the geometry above is fp32 by contract; only the colours may use the mode
-        model.set_precision(args.precision)
     # Appearance: one query per vertex.  Vertices are independent, so under torch.distributed every rank queries a
     # contiguous range of them and one ragged all-gather assembles the (V,3) colours; rank 0 writes the file.
     rank, world = nd.world()
     counts = [b - a for a, b in (nd.split_range(vertices.shape[0], r, world) for r in range(world))]
     lo, hi = nd.split_range(vertices.shape[0], rank, world)
+    if normals_mode == "network":
+        # the fp32 handle whatever --precision is (as the geometry); every rank its own vertex range, one ragged all-gather
+        # (the fallback flag travels as a 4th column)
+        own, kept = network_normals(model.get_model().hip("f32"), vertices[lo:hi], normals[lo:hi])
+        rows = nd.all_gather_rows(torch.cat((own, kept[:, None].to(own.dtype)), dim=1).contiguous(), counts)
+        normals = rows[:, :3].contiguous()
+        print(f"Network normals: {int(rows[:, 3].sum())} of {vertices.shape[0]} vertices kept their grid normal "
+              "(zero or non-finite gradient)")
+    if getattr(args, "precision", "f32") != "f32":     # the geometry above is fp32 by contract; only the colours may use the mode
+        model.set_precision(args.precision)
     targets, directions = vertices[lo:hi], -normals[lo:hi]
     diffuse = []
     # --batch-size bounds the reference's per-call memory (default 1024); on a 288 GB device the per-call overhead
@@ -339,6 +365,10 @@ def build_parser():
                    help="(addition) kernel: one density-grid launch, GPU statistics and marching cubes (default); script: the "
                         "unmodified script's own call sequence -- sample_points + D2H per --batch-size points, numpy iso level, "
                         "skimage.measure.marching_cubes, the re-query in --batch-size calls (single process)")
+    p.add_argument("--normals", choices=("grid", "network"), default="grid",
+                   help="(addition) vertex normals of the appearance rays and the OBJ: grid (default) -- marching cubes' "
+                        "gradient of the density grid -- or network: -grad sigma / |grad sigma| of the network at the final "
+                        "vertices")
     p.add_argument("--gather", choices=("triangles", "grid"), default="triangles",
                    help="(addition, multi-GPU) what travels between the ranks: the emitted triangles of per-slab marching "
                         "cubes (default) or the density grid")
