@@ -46,6 +46,8 @@ extern "C" {
  * --super-sampling).  Additions only: no struct and no signature changed, so the version stays 6. */
 /* 6, later: + nm_mlp_density_grad (+ _workspace_bytes): d sigma / d x at arbitrary points (mesh_nerf --normals network).
  * Additions only. */
+/* 6, later: + nm_surface_filter (+ _workspace_bytes), nm_surface_gather, nm_export_ply (mesh_surface_ray: the ray-marched
+ * surface point cloud).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -635,6 +637,46 @@ int nm_mc_refine_vertices(const float* d_volume, int32_t n0, int32_t n1, int32_t
  * ------------------------------------------------------------------------------------------ */
 int nm_export_obj(const float* h_vertices, int64_t num_vertices, const float* h_diffuse, int64_t num_diffuse,
                   const float* h_normals, int64_t num_normals, const int32_t* h_triangles, int64_t num_triangles,
+                  const char* path);
+
+/* ------------------------------------------------------------------------------------------
+ * Surface point cloud (mesh_surface_ray; the reference's src/mesh_surface_ray.py:115-141 on the device; DESIGN.md,
+ * "Surface point cloud").  One image of height x width rays, row-major; all buffers on the device, fp32:
+ * d_origins (1,3) shared or, with per_ray_o != 0, (height*width,3); d_dirs (height*width,3); d_depth (height*width);
+ * d_opacity (height*width) or NULL.
+ *
+ * nm_surface_filter: depth used z = d_depth when d_opacity is NULL, else (opacity >= (float)min_opacity ? depth : 0).
+ *   Surface point p = o + d * z (two roundings).  votes(row, col) = number of offsets (a, b) in [-step, step]^2 whose
+ *   neighbour q at (clamp(row + a, 0, height-1), clamp(col + b, 0, width-1)) -- the centre and clamped duplicates count --
+ *   has ((qx-px)^2 + (qy-py)^2) + (qz-pz)^2 < (float)dist_threshold (a SQUARED distance).
+ *   keep = votes >= min_votes && z > 0; NaN never votes and is never kept.  Outputs, each optional (NULL): d_votes
+ *   (height*width) int32, d_keep (height*width) bytes 0 / 1, d_count (1) int64 = pixels kept.  d_workspace
+ *   (nm_surface_filter_workspace_bytes(height, width) bytes, 16-byte aligned) receives the keep bits and their prefix sums
+ *   for nm_surface_gather and must stay untouched until then.
+ * nm_surface_gather: with the same inputs and that workspace, writes the kept pixels IN ROW-MAJOR PIXEL ORDER to rows
+ *   row_offset, row_offset + 1, ... of the output arrays of `capacity` rows (rows beyond capacity are dropped, never
+ *   written): d_points (.,3) = p, d_normals (.,3) = -d, d_colors (.,3) = d_rgb's row, d_colors_u8 (.,3) bytes =
+ *   trunc(clamp(rgb * 255, 0, 255)), NaN -> 0.  Each output may be NULL; d_rgb (height*width,3) may be NULL when both colour
+ *   outputs are.
+ * step is in [0, 8], height * width <= 2^30.  No allocation and no host synchronisation: both entries can be captured
+ * into a HIP graph.  Argument errors return 2 before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+int64_t nm_surface_filter_workspace_bytes(int32_t height, int32_t width);
+int nm_surface_filter(const float* d_origins, int per_ray_o, const float* d_dirs, const float* d_depth,
+                      const float* d_opacity, double min_opacity, int32_t height, int32_t width, int32_t step,
+                      double dist_threshold, int32_t min_votes, int32_t* d_votes, uint8_t* d_keep, int64_t* d_count,
+                      void* d_workspace, void* stream);
+int nm_surface_gather(const void* d_workspace, const float* d_origins, int per_ray_o, const float* d_dirs,
+                      const float* d_depth, const float* d_opacity, double min_opacity, const float* d_rgb, int32_t height,
+                      int32_t width, int64_t row_offset, int64_t capacity, float* d_points, float* d_normals,
+                      float* d_colors, uint8_t* d_colors_u8, void* stream);
+
+/* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
+ * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex
+ * per line, floats printed as nm_export_obj prints them (they read back to the same fp32); binary != 0:
+ * "format binary_little_endian 1.0", 27 bytes per vertex.  Returns 2 for a null array with n > 0, 6 if the file cannot be
+ * opened or written. */
+int nm_export_ply(const float* h_points, const float* h_normals, const uint8_t* h_colors_u8, int64_t n, int binary,
                   const char* path);
 
 #ifdef __cplusplus

@@ -184,6 +184,12 @@ SIGNATURES = {
                                         C.c_int64, C.c_int32, c_void_p, c_void_p, c_void_p]),
     "nm_export_obj": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64,
                                 C.c_char_p]),
+    "nm_surface_filter_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "nm_surface_filter": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_double, C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_surface_gather": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, C.c_double, c_void_p, C.c_int32,
+                                    C.c_int32, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 
 _lib = None

@@ -653,3 +653,87 @@ def mc_refine_vertices(volume, z_global, level, keys, ss, fine_sigma, verts):
     check(lib.nm_mc_refine_vertices(_ptr(vol), n0, n1, n2, int(z_global), float(level), _ptr(keys), V, int(ss), _ptr(sig),
                                     _ptr(verts), _stream()), "nm_mc_refine_vertices")
     return verts
+
+
+SURFACE_STEP_MAX = 8
+
+
+def surface_min_votes(step, prob_threshold):
+    """The smallest vote count the reference's `count > ((2 step + 1)^2 - 1) * prob_threshold` (mesh_surface_ray.py:120,133)
+    accepts, the product taken in Python doubles as there (24 * 0.6 = 14.399999999999999 -> 15; 24 * 0.5 = 12.0 -> 13)."""
+    import math
+    return int(math.floor(((2 * int(step) + 1) ** 2 - 1) * prob_threshold)) + 1
+
+
+def surface_filter(origins, dirs, depth, height, width, step=2, dist_threshold=0.002, min_votes=15, opacity=None,
+                   min_opacity=None):
+    """The reference's neighbourhood vote over the surface points of one height x width image of rays (nm_surface_filter;
+    semantics in include/nerfmeshes_hip.h).  origins (1|H*W, 3), dirs (H*W, 3), depth (H*W), opacity (H*W) with min_opacity
+    or None -> dict: votes (H, W) int32, keep (H, W) bool, count (1,) int64 ON THE DEVICE (reading it is the caller's
+    synchronisation), and the state `surface_gather` needs."""
+    lib = _lib.load()
+    height, width = int(height), int(width)
+    if height <= 0 or width <= 0:
+        raise ValueError(f"surface_filter: image of {height} x {width} pixels")
+    if (opacity is None) != (min_opacity is None):
+        raise ValueError("surface_filter: opacity and min_opacity come together")
+    dirs = _dev32(dirs, name="dirs").reshape(-1, 3)
+    dev = dirs.device
+    n = height * width
+    origins = _dev32(origins, dev, "origins").reshape(-1, 3)
+    depth = _dev32(depth, dev, "depth").reshape(-1)
+    opacity = _dev32(opacity, dev, "opacity").reshape(-1) if opacity is not None else None
+    if dirs.shape[0] != n or depth.numel() != n or origins.shape[0] not in (1, n) or (opacity is not None and opacity.numel() != n):
+        raise ValueError(f"surface_filter: the inputs do not describe {height} x {width} rays")
+    per_ray_o = int(origins.shape[0] == n and n > 1)
+    votes = torch.empty(height, width, dtype=torch.int32, device=dev)
+    keep = torch.empty(height, width, dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.nm_surface_filter_workspace_bytes(height, width)), dtype=torch.uint8, device=dev)
+    mo = float(min_opacity) if min_opacity is not None else 0.0
+    check(lib.nm_surface_filter(_ptr(origins), per_ray_o, _ptr(dirs), _ptr(depth), _ptr(opacity), mo, height, width, int(step),
+                                float(dist_threshold), int(min_votes), _ptr(votes), _ptr(keep), _ptr(count), _ptr(ws), _stream()),
+          "nm_surface_filter")
+    return dict(votes=votes, keep=keep.view(torch.bool), count=count, workspace=ws, origins=origins, per_ray_o=per_ray_o,
+                dirs=dirs, depth=depth, opacity=opacity, min_opacity=mo, height=height, width=width)
+
+
+def surface_gather(flt, rgb, count=None):
+    """The pixels `surface_filter` kept, in row-major pixel order (nm_surface_gather) -> (points (N,3), normals (N,3) = -dirs,
+    colours (N,3) fp32 as rendered, colours (N,3) uint8 = trunc(clamp(rgb * 255, 0, 255)) with NaN -> 0 -- numpy's `u1` cast
+    truncates the same way inside [0, 256) and WRAPS outside it, which nobody wants in a colour: the clamp is deliberate).
+    `count` = N when the caller already read it; otherwise flt["count"] is read here (one D2H copy)."""
+    lib = _lib.load()
+    dev = flt["dirs"].device
+    n = int(flt["count"].item()) if count is None else int(count)
+    rgb = _dev32(rgb, dev, "rgb").reshape(-1, 3)
+    if rgb.shape[0] != flt["height"] * flt["width"]:
+        raise ValueError("surface_gather: rgb does not match the filtered image")
+    points, normals, colors = (torch.empty(n, 3, dtype=torch.float32, device=dev) for _ in range(3))
+    colors_u8 = torch.empty(n, 3, dtype=torch.uint8, device=dev)
+    if n:
+        check(lib.nm_surface_gather(_ptr(flt["workspace"]), _ptr(flt["origins"]), flt["per_ray_o"], _ptr(flt["dirs"]),
+                                    _ptr(flt["depth"]), _ptr(flt["opacity"]), flt["min_opacity"], _ptr(rgb), flt["height"],
+                                    flt["width"], 0, n, _ptr(points), _ptr(normals), _ptr(colors), _ptr(colors_u8), _stream()),
+              "nm_surface_gather")
+    return points, normals, colors, colors_u8
+
+
+def export_ply(points, normals, colors_u8, filename, binary=False):
+    """Point cloud -> PLY (nm_export_ply): x y z nx ny nz as float, red green blue as uchar; ascii (default, the reference's
+    `text = True`) or binary_little_endian.  Host or device arrays; colours must already be uint8."""
+    import os
+
+    def host(x, dtype):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x)
+        if dtype is np.uint8 and x.dtype != np.uint8:
+            raise ValueError("export_ply: colours must be uint8 (see surface_gather for the conversion rule)")
+        return np.ascontiguousarray(x, dtype=dtype).reshape(-1, 3)
+
+    p, nrm, c = host(points, np.float32), host(normals, np.float32), host(colors_u8, np.uint8)
+    if not len(p) == len(nrm) == len(c):
+        raise ValueError("export_ply: points, normals and colours disagree on the vertex count")
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if len(a) else C.c_void_p(None)  # noqa: E731
+    check(_lib.load().nm_export_ply(ptr(p), ptr(nrm), ptr(c), len(p), int(bool(binary)), os.fsencode(filename)), "nm_export_ply")

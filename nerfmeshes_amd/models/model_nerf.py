@@ -100,10 +100,12 @@ class NeRFModel(BaseModel):
         noise_std = vr.train_radiance_field_noise_std if vr.training else vr.val_radiance_field_noise_std
         return not (nerf_cfg.perturb or noise_std > 0.0 or self.model_coarse.needs_grad())
 
-    def query_view(self, pose, height, width, focal, bounds, first=0, count=None):
+    def query_view(self, pose, height, width, focal, bounds, first=0, count=None, keep_depth=False):
         """`query` for pixels [first, first+count) of a camera view, the rays generated inside the kernels from the
         pose (nm_render_view; get_ray_bundle + cfg.dataset.use_ndc's ndc_rays): no ray buffers, no per-chunk H2D
-        (nerf_helpers.py:128).  Bit-identical to query() on get_ray_bundle's rays.  Deterministic eval only."""
+        (nerf_helpers.py:128).  Bit-identical to query() on get_ray_bundle's rays.  Deterministic eval only.
+        `keep_depth=True` leaves the depth of rays with acc_map < 1 as composited instead of zeroing it (modules.py:108-109):
+        the only thing the compositing kernels' `training` flag changes, so nothing else of the output moves."""
         nerf_cfg = self.cfg.nerf.train if self.model_coarse.training else self.cfg.nerf.validation
         vr = self.volume_renderer
         noise_std = vr.train_radiance_field_noise_std if vr.training else vr.val_radiance_field_noise_std
@@ -116,7 +118,7 @@ class NeRFModel(BaseModel):
             self.model_coarse.hip(), fine, view, torch.as_tensor(near, dtype=torch.float32).reshape(-1),
             torch.as_tensor(far, dtype=torch.float32).reshape(-1), self.sampler.point_intervals.reshape(-1),
             self.sample_pdf.u if fine is not None else None, first=first, count=count, lindisp=bool(nerf_cfg.lindisp),
-            white_background=bool(vr.white_background), training=bool(vr.training),
+            white_background=bool(vr.white_background), training=bool(vr.training) or bool(keep_depth),
             attenuation_threshold=vr.attenuation_threshold)
         return OutputBundle(**(fb if fb is not None else cb))
 
