@@ -903,15 +903,7 @@ extern "C" int nm_buff_intersect_ex(const float* d_voxels, int32_t nvox, const f
             const int list_bytes = (2 * (la_cap + lpad) + 15) & ~15;
             const size_t lds = (size_t)key_bytes + list_bytes + 2 * npad + 2 * 2 * cap + 2 * 96 + 2 * 4 * cap;
             const void* fn = pass == 0 ? (const void*)buff_reference_ids_kernel<REF_FAST_HITS> : (const void*)buff_reference_ids_kernel<REF_MAX_HITS>;
-            static size_t attr[2][64] = {};               // hipFuncAttributeMaxDynamicSharedMemorySize is per device
-            static std::mutex attr_lock;
-            {
-                std::lock_guard<std::mutex> g(attr_lock);
-                if (dev < 0 || dev >= 64 || attr[pass][dev] < lds) {
-                    NM_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    if (dev >= 0 && dev < 64) attr[pass][dev] = lds;
-                }
-            }
+            if (int rc = ensure_dynamic_lds(fn, (int)lds)) return rc;
             // persistent, one wavefront per ray in flight, EXACTLY as many as are resident: the kernel is latency-bound (its
             // time is inversely proportional to the rays in flight: 2 / 4 / 6 / 9 per CU -> 20.9 / 11.6 / 7.9 / 5.7 ms), and a
             // grid a third larger than the residency (round 3's first version) ran 7.6 ms -- a second, mostly empty round.

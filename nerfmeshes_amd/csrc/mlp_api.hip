@@ -1,6 +1,5 @@
 // C ABI for the fused MLP: weight packing (torch.nn.Linear layout -> MFMA A-operand stream),
 // handle lifetime, and the three entry points that launch nerf_mlp.hip's kernel.
-#include <array>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -37,229 +36,10 @@ bool has_b3_kernel(int H, int FX, int FD);
 int mlp_plan_info(const MlpPlan* p, int* nw);
 int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream_t stream);
 
-// Source column (input feature) of the weight matrix that lane group g consumes at k-step s.
-using StepCols = std::array<int, 4>;  // -1 = zero padding
-
-// hidden activation of width H produced by MFMA tiles: k-step s = 4*tile + reg, group g holds
-// feature 16*tile + 4*g + reg (see nerf_mlp.hip header).
-static void hidden_steps(std::vector<StepCols>& out, int width, int col_offset) {
-    for (int s = 0; s < width / 4; ++s) {
-        StepCols c;
-        for (int g = 0; g < 4; ++g) c[g] = col_offset + 16 * (s >> 2) + 4 * g + (s & 3);
-        out.push_back(c);
-    }
-}
-
-// positional encoding [x(3) | sin(3F) | cos(3F)], coordinate-major (modules.py:26-34): k-step s
-// carries arguments a0=2s (groups 0,1 = sin,cos) and a1=2s+1 (groups 2,3); last step = identity.
-static void encoding_steps(std::vector<StepCols>& out, int F, bool include_input, int col_offset) {
-    const int base = col_offset + (include_input ? 3 : 0);
-    for (int s = 0; s < (3 * F + 1) / 2; ++s) {
-        StepCols c;
-        for (int g = 0; g < 4; ++g) {
-            const int a = 2 * s + (g >> 1);
-            c[g] = a < 3 * F ? base + ((g & 1) ? 3 * F : 0) + a : -1;
-        }
-        out.push_back(c);
-    }
-    StepCols id;
-    for (int g = 0; g < 4; ++g) id[g] = (include_input && g < 3) ? col_offset + g : -1;
-    out.push_back(id);
-}
-
-// Append the A-operand stream of one GEMM as SOURCE INDICES (tensor id << 24 | element): for k-step s,
-// block b of VW tiles, lane l, slot q: W[16*(VW*b+q) + (l&15)][cols[s][l>>4]]; `transposed` addresses W^T
-// (the backward stream: output row n is an input column of the stored nn.Linear weight).
-static void pack_gemm(std::vector<int32_t>& out, int tensor, int ld, int rows, int ntiles,
-                      const std::vector<StepCols>& steps, bool transposed = false) {
-    const int vw = ntiles >= 4 ? 4 : ntiles;
-    for (const StepCols& c : steps)
-        for (int b = 0; b < ntiles / vw; ++b)
-            for (int l = 0; l < 64; ++l)
-                for (int q = 0; q < vw; ++q) {
-                    const int n = 16 * (vw * b + q) + (l & 15);
-                    const int k = c[l >> 4];
-                    const int64_t off = transposed ? (int64_t)k * ld + n : (int64_t)n * ld + k;
-                    out.push_back((n < rows && k >= 0) ? (int32_t)((tensor << 24) | (int32_t)off) : -1);
-                }
-}
-
-static bool is_skip(const nm_mlp_desc& d, int i);
-static void pack_range(std::vector<int32_t>& out, int tensor, int count);
-static void pad_to(std::vector<int32_t>& v, size_t multiple);
-
-// ---- generic-shape family (mlp_device_g.h) -------------------------------------------------------------------------
-// hidden activation of the PADDED width 16 * nt, real width `width`: columns beyond it are zero weights
-static void hidden_steps_g(std::vector<StepCols>& out, int nt, int width, int col_offset) {
-    for (int s = 0; s < 4 * nt; ++s) {
-        StepCols c;
-        for (int g = 0; g < 4; ++g) {
-            const int k = 16 * (s >> 2) + 4 * g + (s & 3);
-            c[g] = k < width ? col_offset + k : -1;
-        }
-        out.push_back(c);
-    }
-}
-
-// an encoding's own stage: (3 F + 1) / 2 argument k-steps, the identity step only when the input is included, zero k-steps
-// up to a whole number of chunks; returns the chunk count
-static int encoding_stage_g(std::vector<StepCols>& out, int F, bool include_input, int col_offset, int kch) {
-    const int base = col_offset + (include_input ? 3 : 0);
-    int n = 0;
-    for (int s = 0; s < (3 * F + 1) / 2; ++s, ++n) {
-        StepCols c;
-        for (int g = 0; g < 4; ++g) {
-            const int a = 2 * s + (g >> 1);
-            c[g] = a < 3 * F ? base + ((g & 1) ? 3 * F : 0) + a : -1;
-        }
-        out.push_back(c);
-    }
-    if (include_input) {
-        StepCols id;
-        for (int g = 0; g < 4; ++g) id[g] = g < 3 ? col_offset + g : -1;
-        out.push_back(id);
-        ++n;
-    }
-    for (; n % kch; ++n) out.push_back(StepCols{-1, -1, -1, -1});
-    return n / kch;
-}
-
-// A-operand stream of one generic stage: per k-step ceil(ntiles / 4) blocks of 4 tiles (1 KiB each; tiles beyond ntiles and rows
-// beyond `rows` are zeros)
-static void pack_gemm_g(std::vector<int32_t>& out, int tensor, int ld, int rows, int ntiles, const std::vector<StepCols>& steps,
-                        bool transposed = false) {
-    const int nb = (ntiles + 3) / 4;
-    for (const StepCols& c : steps)
-        for (int b = 0; b < nb; ++b)
-            for (int l = 0; l < 64; ++l)
-                for (int q = 0; q < 4; ++q) {
-                    const int n = 16 * (4 * b + q) + (l & 15);
-                    const int k = c[l >> 4];
-                    const int64_t off = transposed ? (int64_t)k * ld + n : (int64_t)n * ld + k;    // transposed: W^T (the delta stream)
-                    out.push_back((4 * b + q < ntiles && n < rows && k >= 0) ? (int32_t)((tensor << 24) | (int32_t)off) : -1);
-                }
-}
-
-static void pack_range_padded(std::vector<int32_t>& out, int tensor, int count, int padded) {
-    for (int i = 0; i < padded; ++i) out.push_back(i < count ? ((tensor << 24) | i) : -1);
-}
-
-// GEMV operand of a head row over a D-layout activation of padded width 16 * nt (fc_alpha's layout): [4 lane groups][4 nt]
-static void pack_head_row_g(std::vector<int32_t>& out, int tensor, int row_offset, int nt, int width) {
-    for (int g = 0; g < 4; ++g)
-        for (int s = 0; s < 4 * nt; ++s) {
-            const int k = 16 * (s >> 2) + 4 * g + (s & 3);
-            out.push_back(k < width ? ((tensor << 24) | (row_offset + k)) : -1);
-        }
-}
-
-struct BlobLayout { size_t off_bias, off_wa, off_wr, off_bwd; uint32_t skip_mask; int chx, chd; };
-
 // ---- layer-wise path (nerf_layerwise.hip): networks beyond the fused families' limits -----------------------------------
 // A plan that launches nothing by itself: launch_mlp_timed / the training entry points route such a handle to the layer-wise
 // evaluator.  nm_mlp_kernel_variant reports 2000.
 static const MlpPlan g_layerwise_plan = {0, 0, 0, 8, 0, 2000, 0, false, nullptr, 0, 0, nullptr, 0, nullptr, nullptr};
-
-// The blob of a layer-wise handle as an index map: per Linear its transpose (in x out: the forward products' A operand), the
-// matrix itself (out x in: the delta chain's), its bias; every piece 256-byte aligned (16-byte DMA pieces need it).
-static void build_index_layerwise(std::vector<int32_t>& index, const nm_mlp_desc& d, LwNet* net) {
-    const int H = d.hidden_size, L = d.num_layers, FX = d.num_encoding_fn_xyz, FD = d.num_encoding_fn_dir;
-    const bool no_view = d.use_viewdirs == 0;
-    const int dx = 6 * FX + (d.include_input_xyz ? 3 : 0), dd = no_view ? 0 : 6 * FD + (d.include_input_dir ? 3 : 0);
-    auto linear = [&](int tw, int tb, int out, int in, int nbias) {
-        LwLinear l;
-        l.out = out; l.in = in;
-        pad_to(index, 64); l.wt = index.size();
-        for (int k = 0; k < in; ++k)
-            for (int o = 0; o < out; ++o) index.push_back((tw << 24) | (o * in + k));
-        pad_to(index, 64); l.w = index.size();
-        pack_range(index, tw, out * in);
-        pad_to(index, 64); l.b = index.size();
-        pack_range(index, tb, nbias);
-        return l;
-    };
-    net->L = L; net->H = H; net->H2 = H / 2; net->dx = dx; net->dd = dd; net->flat = no_view ? 1 : 0;
-    net->fx = FX; net->fd = no_view ? 0 : FD; net->inc_x = d.include_input_xyz ? 1 : 0; net->inc_d = d.include_input_dir ? 1 : 0;
-    net->skip_mask = 0;
-    net->layer1 = linear(T_L1W, T_L1B, H, dx, H);
-    for (int i = 0; i < L - 1; ++i) {
-        const bool skip = is_skip(d, i);
-        if (skip) net->skip_mask |= 1u << i;
-        net->xyz[i] = linear(T_XYZ0 + 2 * i, T_XYZ0 + 2 * i + 1, H, H + (skip ? dx : 0), H);
-    }
-    net->alpha = linear(T_ALPHAW, T_ALPHAB, 1, H, 1);
-    if (no_view) {
-        net->rgb = linear(T_RGBW, T_RGBB, 3, H, 3);              // rows 0..2 of fc_out (nm_mlp_weights)
-    } else {
-        net->feat = linear(T_FEATW, T_FEATB, H, H, H);
-        net->dir = linear(T_DIRW, T_DIRB, H / 2, H + dd, H / 2);
-        net->rgb = linear(T_RGBW, T_RGBB, 3, H / 2, 3);
-    }
-    index.resize(index.size() + 1024, -1);                       // what a piece's rounding may read past the last matrix
-}
-
-// The whole blob of a generic plan as an index map (layout: mlp_device_g.h's kernels): forward stream | biases | fc_alpha |
-// fc_rgb (or fc_out's colour rows) | backward stream (the transposed layers in reverse order, hidden columns only).
-static BlobLayout build_index_generic(std::vector<int32_t>& index, const nm_mlp_desc& d, const MlpPlan& plan) {
-    const int H = d.hidden_size, L = d.num_layers, FX = d.num_encoding_fn_xyz, FD = d.num_encoding_fn_dir;
-    const bool no_view = d.use_viewdirs == 0;
-    const int dx = 6 * FX + (d.include_input_xyz ? 3 : 0), dd = 6 * FD + (d.include_input_dir ? 3 : 0);
-    const int NT = plan.generic_nt, NTD = (NT + 1) / 2, HP = 16 * NT, HPD = 16 * NTD, kch = plan.KCH;
-    BlobLayout lay{};
-    std::vector<StepCols> enc_x, hid, skip_enc, dir_enc;
-    lay.chx = encoding_stage_g(enc_x, FX, d.include_input_xyz != 0, 0, kch);
-    hidden_steps_g(hid, NT, H, 0);
-    encoding_stage_g(skip_enc, FX, d.include_input_xyz != 0, H, kch);         // cat(hidden, xyz): models.py:65
-    lay.chd = no_view ? 0 : encoding_stage_g(dir_enc, FD, d.include_input_dir != 0, H, kch);   // cat(feat, view): models.py:72
-    pack_gemm_g(index, T_L1W, dx, H, NT, enc_x);
-    for (int i = 0; i < L - 1; ++i) {
-        const bool skip = is_skip(d, i);
-        const int ld = H + (skip ? dx : 0);
-        pack_gemm_g(index, T_XYZ0 + 2 * i, ld, H, NT, hid);
-        if (skip) {
-            pack_gemm_g(index, T_XYZ0 + 2 * i, ld, H, NT, skip_enc);
-            lay.skip_mask |= 1u << i;
-        }
-    }
-    if (!no_view) {
-        pack_gemm_g(index, T_FEATW, H, H, NT, hid);
-        pack_gemm_g(index, T_DIRW, H + dd, H / 2, NTD, hid);
-        pack_gemm_g(index, T_DIRW, H + dd, H / 2, NTD, dir_enc);
-    }
-    index.resize(index.size() + 8192, -1);   // DMA granularity padding: a tail fetch may run one chunk (32 KiB) past the stream
-    pad_to(index, 64);
-    lay.off_bias = index.size();
-    pack_range_padded(index, T_L1B, H, HP);
-    for (int i = 0; i < L - 1; ++i) pack_range_padded(index, T_XYZ0 + 2 * i + 1, H, HP);
-    if (no_view) index.resize(index.size() + HP + HPD, -1);
-    else {
-        pack_range_padded(index, T_FEATB, H, HP);
-        pack_range_padded(index, T_DIRB, H / 2, HPD);
-    }
-    pack_range(index, T_ALPHAB, 1);
-    pack_range(index, T_RGBB, 3);
-    pad_to(index, 64);
-    lay.off_wa = index.size();
-    pack_head_row_g(index, T_ALPHAW, 0, NT, H);
-    pad_to(index, 64);
-    lay.off_wr = index.size();
-    for (int c = 0; c < 3; ++c) {
-        if (no_view) pack_head_row_g(index, T_RGBW, c * H, NT, H);              // rows 0..2 of fc_out over the trunk output
-        else pack_head_row_g(index, T_RGBW, c * (H / 2), NTD, H / 2);
-    }
-    pad_to(index, 64);
-    lay.off_bwd = index.size();
-    std::vector<StepCols> hid_half;
-    hidden_steps_g(hid_half, NTD, H / 2, 0);
-    if (!no_view) {
-        pack_gemm_g(index, T_DIRW, H + dd, H, NT, hid_half, true);     // delta_v (H/2 columns) -> delta at relu(fc_feat) (H rows)
-        pack_gemm_g(index, T_FEATW, H, H, NT, hid, true);
-    }
-    for (int i = L - 2; i >= 0; --i) pack_gemm_g(index, T_XYZ0 + 2 * i, H + (is_skip(d, i) ? dx : 0), H, NT, hid, true);
-    index.resize(index.size() + 8192, -1);
-    pad_to(index, 64);
-    return lay;
-}
 
 // the per-argument table of one encoding (GEncArg: band, coordinate)
 static void fill_enc_table(float* tab /* [parts * G_ENC_ARGS][2] */, int parts, int F, const float* bands) {
@@ -269,44 +49,6 @@ static void fill_enc_table(float* tab /* [parts * G_ENC_ARGS][2] */, int parts, 
         tab[2 * a] = real ? bands[a % F] : 0.0f;
         memcpy(&tab[2 * a + 1], &coord, 4);
     }
-}
-
-// ---- bf16x3 stream (mlp_device_b3.h): per (k-block m, tile nt) unit the fp32 image [lane][j = 0..7] =
-// W[16 nt + (l & 15)][column of slot (m, l >> 4, j)]; a device kernel splits it into the three bf16 planes.
-using SlotCols = std::array<int, 32>;   // source column of slot 8 g + j of one k-block (-1 = zero)
-
-static void hidden_blocks(std::vector<SlotCols>& out, int width, int col_offset) {
-    for (int m = 0; m < width / 32; ++m) {
-        SlotCols c;
-        for (int g = 0; g < 4; ++g)
-            for (int j = 0; j < 8; ++j) c[8 * g + j] = col_offset + 16 * (2 * m + j / 4) + 4 * g + (j % 4);
-        out.push_back(c);
-    }
-}
-
-// slots 2a, 2a+1 = sin, cos of argument a < 3F (reference columns base + a, base + 3F + a); then the identity coordinates
-static void encoding_blocks(std::vector<SlotCols>& out, int F, bool include_input, int col_offset, int blocks) {
-    const int base = col_offset + (include_input ? 3 : 0);
-    for (int m = 0; m < blocks; ++m) {
-        SlotCols c;
-        for (int q = 0; q < 32; ++q) {
-            const int s = 32 * m + q;
-            if (s < 6 * F) c[q] = base + ((s & 1) ? 3 * F : 0) + s / 2;
-            else if (include_input && s - 6 * F < 3) c[q] = col_offset + (s - 6 * F);
-            else c[q] = -1;
-        }
-        out.push_back(c);
-    }
-}
-
-static void pack_gemm_b3(std::vector<int32_t>& out, int tensor, int ld, int rows, int ntiles, const std::vector<SlotCols>& blocks) {
-    for (const SlotCols& c : blocks)
-        for (int nt = 0; nt < ntiles; ++nt)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int n = 16 * nt + (l & 15), k = c[8 * (l >> 4) + j];
-                    out.push_back((n < rows && k >= 0) ? (int32_t)((tensor << 24) | (int32_t)((int64_t)n * ld + k)) : -1);
-                }
 }
 
 // fp32 image [unit][lane][8] -> three planes of packed bf16 [unit][plane][lane][8]: x1 = bf16(x), x2 = bf16(x - x1), ...
@@ -332,14 +74,6 @@ __global__ void split_b3_kernel(const float* __restrict__ src, uint4* __restrict
         p[2][q] = pack(sx, sy);
     }
     for (int k = 0; k < 3; ++k) dst[(unit * 3 + k) * 64 + lane] = uint4{p[k][0], p[k][1], p[k][2], p[k][3]};
-}
-
-static void pack_range(std::vector<int32_t>& out, int tensor, int count) {
-    for (int i = 0; i < count; ++i) out.push_back((tensor << 24) | i);
-}
-
-static void pad_to(std::vector<int32_t>& v, size_t multiple) {
-    while (v.size() % multiple) v.push_back(-1);
 }
 
 // blob[i] = parameter element index[i] names (or 0): the whole packing, on the device.  Every pass also folds what it read into
@@ -391,21 +125,18 @@ __global__ __launch_bounds__(256) void scatter_layer1_t(const int32_t* __restric
     else if (tensor == T_L1B) out[(int64_t)dx * H + e] = blob[p];
 }
 
-static bool is_skip(const nm_mlp_desc& d, int i) {   // models.py:37,63
-    return i % d.skip_step == 0 && i > 0 && i != d.num_layers - 1;
-}
-
-static void weight_pointers(const nm_mlp_desc& d, const nm_mlp_weights& w, WeightPtrs& p) {
+// The caller's tensors behind the handle's network (the layer walk: mlp_pack.h); every one of them must be there.
+static int weight_pointers(const nm_mlp_desc& d, const nm_mlp_weights& w, WeightPtrs& p, const char* who) {
     std::memset(&p, 0, sizeof(p));
-    p.p[T_L1W] = w.layer1_w; p.p[T_L1B] = w.layer1_b;
-    for (int i = 0; i < d.num_layers - 1; ++i) {
-        p.p[T_XYZ0 + 2 * i] = w.layers_xyz_w[i];
-        p.p[T_XYZ0 + 2 * i + 1] = w.layers_xyz_b[i];
-    }
-    p.p[T_FEATW] = w.fc_feat_w; p.p[T_FEATB] = w.fc_feat_b;
-    p.p[T_ALPHAW] = w.fc_alpha_w; p.p[T_ALPHAB] = w.fc_alpha_b;
-    p.p[T_DIRW] = w.layers_dir0_w; p.p[T_DIRB] = w.layers_dir0_b;
-    p.p[T_RGBW] = w.fc_rgb_w; p.p[T_RGBB] = w.fc_rgb_b;
+    for (const Linear& l : network_layers(d))
+        for (int t : {l.w, l.b}) {
+            p.p[t] = weight_tensor(w, t);
+            if (!p.p[t]) {
+                set_error(std::string(who) + ": missing tensor [!used || ptrs.p[t]]");
+                return 2;
+            }
+        }
+    return 0;
 }
 
 static int launch_gather(nm_mlp* m, const WeightPtrs& ptrs, hipStream_t stream) {
@@ -423,6 +154,16 @@ static int launch_gather(nm_mlp* m, const WeightPtrs& ptrs, hipStream_t stream) 
     NM_HIP_CHECK(hipGetLastError());
     ++m->refresh_count;
     return 0;
+}
+
+MlpArgs ray_mode_args(const nm_mlp* m, const float* d_origins, int origins_per_ray, const float* d_dirs, const float* d_t, int64_t rays,
+                      int32_t samples, float* d_radiance) {
+    MlpArgs a = m->base;
+    a.mode = MODE_RAYS;
+    a.a = d_origins; a.b = d_dirs; a.c = d_t;
+    a.origins_per_ray = origins_per_ray; a.samples = samples;
+    a.n = rays * samples; a.out = d_radiance;
+    return a;
 }
 
 // ---- optional per-launch timing of the dominant kernel (bench.py's roofline leg) ---------------
@@ -447,17 +188,158 @@ static int launch_mlp_timed(const nm_mlp* m, const MlpArgs& a, int density_only,
     return rc;
 }
 
-static int64_t mlp_macs(const nm_mlp_desc& d, bool density_only) {
-    const int64_t H = d.hidden_size, dx = 6 * d.num_encoding_fn_xyz + (d.include_input_xyz ? 3 : 0);
-    const int64_t dd = 6 * d.num_encoding_fn_dir + (d.include_input_dir ? 3 : 0);
-    int64_t macs = dx * H;
-    for (int i = 0; i < d.num_layers - 1; ++i) {
-        const bool skip = i % d.skip_step == 0 && i > 0 && i != d.num_layers - 1;
-        macs += (H + (skip ? dx : 0)) * H;
+// ---- nm_mlp_create_ex, step by step ------------------------------------------------------------------------------------
+static int validate_create(const nm_mlp_desc& d, const nm_mlp_weights* w, int precision, bool force_generic) {
+    NM_REQUIRE(precision == NM_PREC_F32 || precision == NM_PREC_BF16X3, "unknown precision");
+    NM_REQUIRE(!force_generic || precision == NM_PREC_F32, "NM_KERNEL_GENERIC goes with NM_PREC_F32");
+    NM_REQUIRE(d.use_viewdirs == 0 || d.use_viewdirs == 1, "use_viewdirs is 0 or 1");
+    const bool no_view = d.use_viewdirs == 0;      // models.py:77-79: trunk -> fc_out (4 rows), no view branch
+    NM_REQUIRE(!no_view || precision == NM_PREC_F32, "use_viewdirs=0 networks run in fp32 only");
+    NM_REQUIRE(d.num_layers >= 2 && d.num_layers <= 32, "num_layers out of range");
+    NM_REQUIRE(d.skip_step >= 1, "skip_step must be >= 1");
+    NM_REQUIRE(d.hidden_size >= 1 && d.num_encoding_fn_xyz >= 0 && d.num_encoding_fn_dir >= 0, "negative network dimension");
+    NM_REQUIRE(no_view || d.hidden_size >= 2, "hidden_size = 1 with view directions: layers_dir[0] would have hidden_size // 2 = 0 rows");
+    NM_REQUIRE(d.num_encoding_fn_xyz > 0 || d.include_input_xyz,
+               "the xyz encoding is empty (num_encoding_fn_xyz = 0 without include_input_xyz): layer1 would have no input");
+    // every tensor the packer will read, checked before anything dereferences one
+    NM_REQUIRE(w->layer1_w && w->layer1_b && w->fc_alpha_w && w->fc_alpha_b && w->fc_rgb_w && w->fc_rgb_b, "missing weight tensor");
+    NM_REQUIRE(no_view || (w->fc_feat_w && w->fc_feat_b && w->layers_dir0_w && w->layers_dir0_b), "missing view-branch weight tensor");
+    NM_REQUIRE(w->layers_xyz_w && w->layers_xyz_b, "missing layers_xyz tensor tables");
+    for (int i = 0; i < d.num_layers - 1; ++i)
+        NM_REQUIRE(w->layers_xyz_w[i] && w->layers_xyz_b[i], "missing layers_xyz weight tensor");
+    NM_REQUIRE(d.num_encoding_fn_xyz == 0 || w->freq_xyz, "missing xyz frequency bands");
+    NM_REQUIRE(no_view || d.num_encoding_fn_dir == 0 || w->freq_dir, "missing direction frequency bands");
+    return 0;
+}
+
+// A tuned plan for exactly this shape, else the generic family (mlp_device_g.h): every shape FlexibleNeRFModel's
+// constructor accepts up to hidden_size 512 and 24 k-steps per encoding, else the layer-wise plan.  (A network without view
+// directions has no direction encoding: any tuned kernel of that width / xyz encoding runs it.)
+static int choose_plan(const nm_mlp_desc& d, int precision, bool force_generic, const MlpPlan** out) {
+    static const char* const b3_shapes = "precision bf16x3 is instantiated for hidden_size 64 / 128 / 256 with 6 or 10 xyz / 4 direction frequencies only";
+    const int H = d.hidden_size, L = d.num_layers, FX = d.num_encoding_fn_xyz, FD = d.num_encoding_fn_dir;
+    const bool no_view = d.use_viewdirs == 0;
+    const MlpPlan* plan = (!force_generic && FX <= MAX_FREQ_XYZ && (no_view || FD <= MAX_FREQ_DIR)) ? find_mlp_plan(H, FX, no_view ? 4 : FD) : nullptr;
+    if (!plan) {
+        const int steps_x = (3 * FX + 1) / 2 + (d.include_input_xyz ? 1 : 0), steps_d = (3 * FD + 1) / 2 + (d.include_input_dir ? 1 : 0);
+        const int steps = (!no_view && steps_d > steps_x) ? steps_d : steps_x;
+        const bool long_encoding = steps > G_ENC_PARTS * G_ENC_STEPS;      // beyond what the fused kernels take even in two parts
+        plan = find_generic_plan(H, L, steps > G_ENC_STEPS);
+        if (precision != NM_PREC_F32) {
+            set_error(b3_shapes);
+            return 3;
+        }
+        if (!plan || long_encoding) {
+            // beyond the fused families -- hidden_size > 512 (half of a wider layer's activations does not fit the register file of
+            // one wavefront), an encoding of more than 48 MFMA k-steps (31 functions), or so many layers that their biases no longer
+            // fit the LDS next to the weight ring --: the layer-wise path (nerf_layerwise.hip)
+            if (FX > LW_MAX_FREQ || (!no_view && FD > LW_MAX_FREQ)) {
+                set_error("an encoding of " + std::to_string(FX) + " / " + std::to_string(FD) + " functions: the limit is " +
+                          std::to_string(LW_MAX_FREQ) + " per input (frequency 2^31 is past fp32's integer range)");
+                return 3;
+            }
+            if ((int64_t)H * (H + encoded_width(FX, d.include_input_xyz)) >= (1 << 24)) {
+                set_error("hidden_size=" + std::to_string(H) + ": a weight matrix of more than 2^24 elements exceeds the packer's index map");
+                return 3;
+            }
+            plan = &g_layerwise_plan;
+        }
     }
-    macs += H;  // fc_alpha (use_viewdirs = 0: row 3 of fc_out)
-    if (!density_only) macs += d.use_viewdirs ? H * H + (H + dd) * (H / 2) + (H / 2) * 3 : 3 * H;   // else: rows 0..2 of fc_out
-    return macs;
+    if (precision == NM_PREC_BF16X3 && !has_b3_kernel(H, FX, FD)) {
+        set_error(b3_shapes);
+        return 3;
+    }
+    *out = plan;
+    return 0;
+}
+
+// the packed images as index maps (mlp_pack.h); `lw`: the layer-wise handle's description, filled here
+struct PackedIndex { std::vector<int32_t> index, index_b3; BlobLayout lay; size_t plain_off; };
+
+static void build_indices(const nm_mlp_desc& d, const MlpPlan& plan, int precision, LwNet* lw, PackedIndex& px) {
+    px.lay = BlobLayout{};
+    if (lw) build_index_layerwise(px.index, d, lw);
+    else px.lay = build_index_f32(px.index, d, StreamGeometry{plan.generic_nt ? plan.generic_nt : d.hidden_size / 16, plan.KCH, plan.generic_nt == 0});
+    if (precision == NM_PREC_BF16X3) build_index_b3(px.index_b3, d);         // opt-in: the same stages as units of (k-block, tile)
+    px.plain_off = append_plain_copies(px.index, d);
+}
+
+static int upload_indices(nm_mlp* m, const PackedIndex& px) {
+    m->plain_off = px.plain_off;
+    m->blob_floats = px.index.size();
+    m->blob_bytes = px.index.size() * 4;
+    NM_HIP_CHECK(hipMalloc(&m->d_blob, m->blob_bytes));
+    NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_check), 16));
+    NM_HIP_CHECK(hipMemset(m->d_check, 0, 16));
+    NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_index), m->blob_bytes));
+    NM_HIP_CHECK(hipMemcpy(m->d_index, px.index.data(), m->blob_bytes, hipMemcpyHostToDevice));
+    if (m->precision == NM_PREC_BF16X3) {
+        const std::vector<int32_t>& index_b3 = px.index_b3;
+        m->b3_units = index_b3.size() / 512;
+        NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_index_b3), index_b3.size() * 4));
+        NM_HIP_CHECK(hipMemcpy(m->d_index_b3, index_b3.data(), index_b3.size() * 4, hipMemcpyHostToDevice));
+        NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_tmp_b3), index_b3.size() * 4));
+        NM_HIP_CHECK(hipMalloc(&m->d_stream_b3, m->b3_units * 3072));
+    }
+    return 0;
+}
+
+// the weight-related fields of MlpArgs / MlpBwdArgs, and a generic plan's encoding table
+static int fill_args(nm_mlp* m, const nm_mlp_weights* w, const BlobLayout& lay) {
+    const nm_mlp_desc& d = m->desc;
+    const int H = d.hidden_size, FX = d.num_encoding_fn_xyz, FD = d.num_encoding_fn_dir;
+    const bool no_view = d.use_viewdirs == 0;
+    const float* base = static_cast<const float*>(m->d_blob);
+    MlpArgs& a = m->base;
+    a.wstream = reinterpret_cast<const char*>(base);
+    a.bias = base + lay.off_bias;
+    a.walpha = base + lay.off_wa;
+    a.wrgb = base + lay.off_wr;
+    for (int f = 0; f < FX && f < MAX_FREQ_XYZ; ++f) a.bands_xyz[f] = w->freq_xyz[f];
+    for (int f = 0; f < FD && f < MAX_FREQ_DIR && !no_view; ++f) a.bands_dir[f] = w->freq_dir[f];
+    a.skip_mask = lay.skip_mask;
+    if (m->plan->generic_nt) {      // the encodings' run-time description (mlp_device_g.h)
+        const int parts = m->plan->variant == G_LONG_VARIANT ? G_ENC_PARTS : 1;     // [xyz, dir][parts][G_ENC_ARGS] (band, coordinate)
+        float tab[2 * 2 * G_ENC_PARTS * G_ENC_ARGS];
+        fill_enc_table(tab, parts, FX, w->freq_xyz);
+        fill_enc_table(tab + 2 * parts * G_ENC_ARGS, parts, no_view ? 0 : FD, w->freq_dir);
+        const size_t tab_bytes = sizeof(float) * 2 * 2 * parts * G_ENC_ARGS;
+        NM_HIP_CHECK(hipMalloc(&m->d_enc_tab, tab_bytes));
+        NM_HIP_CHECK(hipMemcpy(m->d_enc_tab, tab, tab_bytes, hipMemcpyHostToDevice));
+        a.g_tab = m->d_enc_tab;
+        a.g_nsx = (3 * FX + 1) / 2; a.g_idx = d.include_input_xyz ? 1 : 0; a.g_chx = lay.chx;
+        a.g_nsd = no_view ? 0 : (3 * FD + 1) / 2; a.g_idd = (!no_view && d.include_input_dir) ? 1 : 0; a.g_chd = lay.chd;
+        a.g_h = H; a.g_hd = H / 2;
+        m->bwd.g_h = H; m->bwd.g_hd = H / 2;
+    }
+    m->bwd.wstream = reinterpret_cast<const char*>(base + lay.off_bwd);
+    m->bwd.walpha = a.walpha;
+    m->bwd.wrgb = a.wrgb;
+    m->flops_full = 2 * mlp_macs(d, false);
+    m->flops_density = 2 * mlp_macs(d, true);
+    return 0;
+}
+
+// fill the blob from the host tensors: stage them on the device (*d_flat: the caller frees it) and run the same gather
+// nm_mlp_refresh uses
+static int stage_and_gather(nm_mlp* m, const nm_mlp_weights* w, float** d_flat) {
+    const std::vector<Linear> layers = network_layers(m->desc);
+    std::vector<float> flat;
+    std::vector<size_t> offs(T_COUNT, 0);
+    auto stage = [&](int t, size_t count) {
+        const float* src = weight_tensor(*w, t);
+        offs[t] = flat.size();
+        flat.insert(flat.end(), src, src + count);
+    };
+    for (const Linear& l : layers) { stage(l.w, (size_t)l.out * l.in); stage(l.b, l.out); }
+    NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(d_flat), flat.size() * 4));
+    NM_HIP_CHECK(hipMemcpy(*d_flat, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
+    WeightPtrs ptrs;
+    std::memset(&ptrs, 0, sizeof(ptrs));
+    for (const Linear& l : layers) { ptrs.p[l.w] = *d_flat + offs[l.w]; ptrs.p[l.b] = *d_flat + offs[l.b]; }
+    int rc = launch_gather(m, ptrs, nullptr);
+    if (rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("parameter gather failed"); rc = 1; }
+    return rc;
 }
 
 }  // namespace nm
@@ -505,159 +387,17 @@ int nm_mlp_create_ex(const nm_mlp_desc* desc, const nm_mlp_weights* w, int devic
     NM_REQUIRE(desc && w && out, "null argument");
     const bool force_generic = (precision & NM_KERNEL_GENERIC) != 0;
     precision &= ~NM_KERNEL_GENERIC;
-    NM_REQUIRE(precision == NM_PREC_F32 || precision == NM_PREC_BF16X3, "unknown precision");
-    NM_REQUIRE(!force_generic || precision == NM_PREC_F32, "NM_KERNEL_GENERIC goes with NM_PREC_F32");
     const nm_mlp_desc& d = *desc;
-    NM_REQUIRE(d.use_viewdirs == 0 || d.use_viewdirs == 1, "use_viewdirs is 0 or 1");
-    const bool no_view = d.use_viewdirs == 0;      // models.py:77-79: trunk -> fc_out (4 rows), no view branch
-    NM_REQUIRE(!no_view || precision == NM_PREC_F32, "use_viewdirs=0 networks run in fp32 only");
-    NM_REQUIRE(d.num_layers >= 2 && d.num_layers <= 32, "num_layers out of range");
-    NM_REQUIRE(d.skip_step >= 1, "skip_step must be >= 1");
-    NM_REQUIRE(d.hidden_size >= 1 && d.num_encoding_fn_xyz >= 0 && d.num_encoding_fn_dir >= 0, "negative network dimension");
-    NM_REQUIRE(no_view || d.hidden_size >= 2, "hidden_size = 1 with view directions: layers_dir[0] would have hidden_size // 2 = 0 rows");
-    NM_REQUIRE(d.num_encoding_fn_xyz > 0 || d.include_input_xyz,
-               "the xyz encoding is empty (num_encoding_fn_xyz = 0 without include_input_xyz): layer1 would have no input");
-    // every tensor the packer will read, checked before anything dereferences one
-    NM_REQUIRE(w->layer1_w && w->layer1_b && w->fc_alpha_w && w->fc_alpha_b && w->fc_rgb_w && w->fc_rgb_b, "missing weight tensor");
-    NM_REQUIRE(no_view || (w->fc_feat_w && w->fc_feat_b && w->layers_dir0_w && w->layers_dir0_b), "missing view-branch weight tensor");
-    NM_REQUIRE(w->layers_xyz_w && w->layers_xyz_b, "missing layers_xyz tensor tables");
-    for (int i = 0; i < d.num_layers - 1; ++i)
-        NM_REQUIRE(w->layers_xyz_w[i] && w->layers_xyz_b[i], "missing layers_xyz weight tensor");
-    NM_REQUIRE(d.num_encoding_fn_xyz == 0 || w->freq_xyz, "missing xyz frequency bands");
-    NM_REQUIRE(no_view || d.num_encoding_fn_dir == 0 || w->freq_dir, "missing direction frequency bands");
-    const int H = d.hidden_size, L = d.num_layers, FX = d.num_encoding_fn_xyz, FD = d.num_encoding_fn_dir;
-    const int dx = 6 * FX + (d.include_input_xyz ? 3 : 0), dd = 6 * FD + (d.include_input_dir ? 3 : 0);
-    // A tuned plan for exactly this shape, else the generic family (mlp_device_g.h): every shape FlexibleNeRFModel's
-    // constructor accepts up to hidden_size 512 and 24 k-steps per encoding.  (A network without view directions has no
-    // direction encoding: any tuned kernel of that width / xyz encoding runs it.)
-    const MlpPlan* plan = (!force_generic && FX <= MAX_FREQ_XYZ && (no_view || FD <= MAX_FREQ_DIR)) ? find_mlp_plan(H, FX, no_view ? 4 : FD) : nullptr;
+    if (int rc = validate_create(d, w, precision, force_generic)) return rc;
+    const MlpPlan* plan = nullptr;
+    if (int rc = choose_plan(d, precision, force_generic, &plan)) return rc;
     LwNet* lw_net = nullptr;
-    if (!plan) {
-        const int steps_x = (3 * FX + 1) / 2 + (d.include_input_xyz ? 1 : 0), steps_d = (3 * FD + 1) / 2 + (d.include_input_dir ? 1 : 0);
-        const int steps = (!no_view && steps_d > steps_x) ? steps_d : steps_x;
-        const bool long_encoding = steps > G_ENC_PARTS * G_ENC_STEPS;      // beyond what the fused kernels take even in two parts
-        plan = find_generic_plan(H, L, steps > G_ENC_STEPS);
-        if (precision != NM_PREC_F32) {
-            set_error("precision bf16x3 is instantiated for hidden_size 64 / 128 / 256 with 6 or 10 xyz / 4 direction frequencies only");
-            return 3;
-        }
-        if (!plan || long_encoding) {
-            // beyond the fused families -- hidden_size > 512 (half of a wider layer's activations does not fit the register file of
-            // one wavefront), an encoding of more than 48 MFMA k-steps (31 functions), or so many layers that their biases no longer
-            // fit the LDS next to the weight ring --: the layer-wise path (nerf_layerwise.hip)
-            if (FX > LW_MAX_FREQ || (!no_view && FD > LW_MAX_FREQ)) {
-                set_error("an encoding of " + std::to_string(FX) + " / " + std::to_string(FD) + " functions: the limit is " +
-                          std::to_string(LW_MAX_FREQ) + " per input (frequency 2^31 is past fp32's integer range)");
-                return 3;
-            }
-            if ((int64_t)H * (H + dx) >= (1 << 24)) {
-                set_error("hidden_size=" + std::to_string(H) + ": a weight matrix of more than 2^24 elements exceeds the packer's index map");
-                return 3;
-            }
-            plan = &g_layerwise_plan;
-            lw_net = new LwNet();
-            std::memset(lw_net, 0, sizeof(*lw_net));
-        }
+    if (plan == &g_layerwise_plan) {
+        lw_net = new LwNet();
+        std::memset(lw_net, 0, sizeof(*lw_net));
     }
-    const int NT = H / 16, NTD = H / 32;
-
-    std::vector<int32_t> index;
-    BlobLayout lay{};
-    if (lw_net) {
-        build_index_layerwise(index, d, lw_net);
-    } else if (plan->generic_nt) {
-        lay = build_index_generic(index, d, *plan);
-    } else {
-    std::vector<StepCols> enc_x, hid, hid_half, hid_skip_enc, dir_steps;
-    encoding_steps(enc_x, FX, d.include_input_xyz != 0, 0);
-    hidden_steps(hid, H, 0);
-    hidden_steps(hid_half, H / 2, 0);
-    encoding_steps(hid_skip_enc, FX, d.include_input_xyz != 0, H);  // cat(hidden, xyz): models.py:65
-    hidden_steps(dir_steps, H, 0);
-    encoding_steps(dir_steps, FD, d.include_input_dir != 0, H);     // cat(feat, view): models.py:72
-
-    // ---- the blob as an index map: forward stream | biases | fc_alpha | fc_rgb | backward stream
-    uint32_t skip_mask = 0;
-    pack_gemm(index, T_L1W, dx, H, NT, enc_x);
-    for (int i = 0; i < L - 1; ++i) {
-        const bool skip = is_skip(d, i);
-        const int ld = H + (skip ? dx : 0);
-        pack_gemm(index, T_XYZ0 + 2 * i, ld, H, NT, hid);
-        if (skip) {
-            pack_gemm(index, T_XYZ0 + 2 * i, ld, H, NT, hid_skip_enc);
-            skip_mask |= 1u << i;
-        }
-    }
-    if (!no_view) {
-        pack_gemm(index, T_FEATW, H, H, NT, hid);
-        pack_gemm(index, T_DIRW, H + dd, H / 2, NTD, dir_steps);
-    }
-    index.resize(index.size() + 1024, -1);  // DMA granularity padding (4 KiB)
-    pad_to(index, 64);
-    const size_t off_bias = index.size();
-    pack_range(index, T_L1B, H);
-    for (int i = 0; i < L - 1; ++i) pack_range(index, T_XYZ0 + 2 * i + 1, H);
-    if (no_view) index.resize(index.size() + H + H / 2, -1);       // the kernels' bias layout is the same for both kinds
-    else {
-        pack_range(index, T_FEATB, H);
-        pack_range(index, T_DIRB, H / 2);
-    }
-    pack_range(index, T_ALPHAB, 1);
-    pack_range(index, T_RGBB, 3);
-    pad_to(index, 64);
-    // fc_alpha / fc_rgb as per-lane-group GEMV operands
-    const size_t off_wa = index.size();
-    for (int g = 0; g < 4; ++g)
-        for (int s = 0; s < H / 4; ++s) index.push_back((T_ALPHAW << 24) | (16 * (s >> 2) + 4 * g + (s & 3)));
-    pad_to(index, 64);
-    const size_t off_wr = index.size();
-    if (no_view) {     // rows 0..2 of fc_out over the trunk output: three GEMV operands in fc_alpha's layout
-        for (int c = 0; c < 3; ++c)
-            for (int g = 0; g < 4; ++g)
-                for (int s = 0; s < H / 4; ++s) index.push_back((T_RGBW << 24) | (c * H + 16 * (s >> 2) + 4 * g + (s & 3)));
-    } else {
-        for (int c = 0; c < 3; ++c)
-            for (int g = 0; g < 4; ++g)
-                for (int s = 0; s < H / 8; ++s)
-                    index.push_back((T_RGBW << 24) | (c * (H / 2) + 16 * (s >> 2) + 4 * g + (s & 3)));
-    }
-    pad_to(index, 64);
-    // backward (delta propagation): the same layers transposed, in reverse order, hidden columns only
-    const size_t off_bwd = index.size();
-    if (!no_view) {
-        pack_gemm(index, T_DIRW, H + dd, H, NT, hid_half, true);
-        pack_gemm(index, T_FEATW, H, H, NT, hid, true);
-    }
-    for (int i = L - 2; i >= 0; --i) pack_gemm(index, T_XYZ0 + 2 * i, H + (is_skip(d, i) ? dx : 0), H, NT, hid, true);
-    index.resize(index.size() + 1024, -1);
-    pad_to(index, 64);
-    lay = BlobLayout{off_bias, off_wa, off_wr, off_bwd, skip_mask, 0, 0};
-    }
-
-    // opt-in bf16x3 stream: the same stages as units of (k-block, tile)
-    std::vector<int32_t> index_b3;
-    if (precision == NM_PREC_BF16X3) {
-        if (!has_b3_kernel(H, FX, FD)) {
-            set_error("precision bf16x3 is instantiated for hidden_size 64 / 128 / 256 with 6 or 10 xyz / 4 direction frequencies only");
-            return 3;
-        }
-        std::vector<SlotCols> bx, bh, bskip, bdir;
-        encoding_blocks(bx, FX, d.include_input_xyz != 0, 0, 2);
-        hidden_blocks(bh, H, 0);
-        encoding_blocks(bskip, FX, d.include_input_xyz != 0, H, 2);
-        hidden_blocks(bdir, H, 0);
-        encoding_blocks(bdir, FD, d.include_input_dir != 0, H, 1);
-        pack_gemm_b3(index_b3, T_L1W, dx, H, NT, bx);
-        for (int i = 0; i < L - 1; ++i) {
-            const bool skip = is_skip(d, i);
-            const int ld = H + (skip ? dx : 0);
-            pack_gemm_b3(index_b3, T_XYZ0 + 2 * i, ld, H, NT, bh);
-            if (skip) pack_gemm_b3(index_b3, T_XYZ0 + 2 * i, ld, H, NT, bskip);
-        }
-        pack_gemm_b3(index_b3, T_FEATW, H, H, NT, bh);
-        pack_gemm_b3(index_b3, T_DIRW, H + dd, H / 2, NTD, bdir);
-        index_b3.resize(index_b3.size() + 16 * 512, -1);      // DMA granularity / chunk padding
-    }
+    PackedIndex px;
+    build_indices(d, *plan, precision, lw_net, px);
 
     nm_mlp* m = new nm_mlp();
     std::memset(m, 0, sizeof(*m));
@@ -667,8 +407,8 @@ int nm_mlp_create_ex(const nm_mlp_desc* desc, const nm_mlp_weights* w, int devic
     m->precision = precision;
     m->lw = lw_net;          // freed with the handle (also by the rollback below)
     if (lw_net) {
-        for (int f = 0; f < FX; ++f) lw_net->bands_x[f] = w->freq_xyz[f];
-        for (int f = 0; f < FD && !no_view; ++f) lw_net->bands_d[f] = w->freq_dir[f];
+        for (int f = 0; f < d.num_encoding_fn_xyz; ++f) lw_net->bands_x[f] = w->freq_xyz[f];
+        for (int f = 0; f < d.num_encoding_fn_dir && d.use_viewdirs; ++f) lw_net->bands_d[f] = w->freq_dir[f];
     }
     int prev_device = -1;
     (void)hipGetDevice(&prev_device);
@@ -686,88 +426,9 @@ int nm_mlp_create_ex(const nm_mlp_desc* desc, const nm_mlp_weights* w, int devic
     hipDeviceProp_t prop;
     NM_HIP_CHECK(hipGetDeviceProperties(&prop, device));
     m->num_cus = prop.multiProcessorCount;
-    // behind everything the kernels stream: PLAIN copies of the three tensors nm_mlp_linear_layer1_finish multiplies with, filled by
-    // the same gather -- layers_xyz[0].weight (H, H) row-major, layer1.weight TRANSPOSED (dx, H), layer1.bias (H)
-    if (!index.empty() && desc->num_layers >= 2) {
-        const int Hh = desc->hidden_size, dxx = 6 * desc->num_encoding_fn_xyz + (desc->include_input_xyz ? 3 : 0);
-        while (index.size() % 64) index.push_back(-1);
-        m->plain_off = index.size();
-        for (int e = 0; e < Hh * Hh; ++e) index.push_back((T_XYZ0 << 24) | e);
-        for (int j = 0; j < dxx; ++j)
-            for (int i = 0; i < Hh; ++i) index.push_back((T_L1W << 24) | (i * dxx + j));
-        for (int i = 0; i < Hh; ++i) index.push_back((T_L1B << 24) | i);
-    }
-    m->blob_floats = index.size();
-    m->blob_bytes = index.size() * 4;
-    NM_HIP_CHECK(hipMalloc(&m->d_blob, m->blob_bytes));
-    NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_check), 16));
-    NM_HIP_CHECK(hipMemset(m->d_check, 0, 16));
-    NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_index), m->blob_bytes));
-    NM_HIP_CHECK(hipMemcpy(m->d_index, index.data(), m->blob_bytes, hipMemcpyHostToDevice));
-    if (precision == NM_PREC_BF16X3) {
-        m->b3_units = index_b3.size() / 512;
-        NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_index_b3), index_b3.size() * 4));
-        NM_HIP_CHECK(hipMemcpy(m->d_index_b3, index_b3.data(), index_b3.size() * 4, hipMemcpyHostToDevice));
-        NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_tmp_b3), index_b3.size() * 4));
-        NM_HIP_CHECK(hipMalloc(&m->d_stream_b3, m->b3_units * 3072));
-    }
-    const float* base = static_cast<const float*>(m->d_blob);
-    MlpArgs& a = m->base;
-    a.wstream = reinterpret_cast<const char*>(base);
-    a.bias = base + lay.off_bias;
-    a.walpha = base + lay.off_wa;
-    a.wrgb = base + lay.off_wr;
-    for (int f = 0; f < FX && f < MAX_FREQ_XYZ; ++f) a.bands_xyz[f] = w->freq_xyz[f];
-    for (int f = 0; f < FD && f < MAX_FREQ_DIR && !no_view; ++f) a.bands_dir[f] = w->freq_dir[f];
-    a.skip_mask = lay.skip_mask;
-    if (plan->generic_nt) {      // the encodings' run-time description (mlp_device_g.h)
-        const int parts = plan->variant == G_LONG_VARIANT ? G_ENC_PARTS : 1;     // [xyz, dir][parts][G_ENC_ARGS] (band, coordinate)
-        float tab[2 * 2 * G_ENC_PARTS * G_ENC_ARGS];
-        fill_enc_table(tab, parts, FX, w->freq_xyz);
-        fill_enc_table(tab + 2 * parts * G_ENC_ARGS, parts, no_view ? 0 : FD, w->freq_dir);
-        const size_t tab_bytes = sizeof(float) * 2 * 2 * parts * G_ENC_ARGS;
-        NM_HIP_CHECK(hipMalloc(&m->d_enc_tab, tab_bytes));
-        NM_HIP_CHECK(hipMemcpy(m->d_enc_tab, tab, tab_bytes, hipMemcpyHostToDevice));
-        a.g_tab = m->d_enc_tab;
-        a.g_nsx = (3 * FX + 1) / 2; a.g_idx = d.include_input_xyz ? 1 : 0; a.g_chx = lay.chx;
-        a.g_nsd = no_view ? 0 : (3 * FD + 1) / 2; a.g_idd = (!no_view && d.include_input_dir) ? 1 : 0; a.g_chd = lay.chd;
-        a.g_h = H; a.g_hd = H / 2;
-        m->bwd.g_h = H; m->bwd.g_hd = H / 2;
-    }
-    m->bwd.wstream = reinterpret_cast<const char*>(base + lay.off_bwd);
-    m->bwd.walpha = a.walpha;
-    m->bwd.wrgb = a.wrgb;
-    m->flops_full = 2 * mlp_macs(d, false);
-    m->flops_density = 2 * mlp_macs(d, true);
-
-    // ---- fill it from the host tensors: stage them on the device and run the same gather nm_mlp_refresh uses
-    std::vector<float> flat;
-    std::vector<size_t> offs(T_COUNT, 0);
-    auto stage = [&](int t, const float* src, size_t count) { offs[t] = flat.size(); flat.insert(flat.end(), src, src + count); };
-    stage(T_L1W, w->layer1_w, (size_t)H * dx); stage(T_L1B, w->layer1_b, H);
-    for (int i = 0; i < L - 1; ++i) {
-        stage(T_XYZ0 + 2 * i, w->layers_xyz_w[i], (size_t)H * (H + (is_skip(d, i) ? dx : 0)));
-        stage(T_XYZ0 + 2 * i + 1, w->layers_xyz_b[i], H);
-    }
-    stage(T_ALPHAW, w->fc_alpha_w, H); stage(T_ALPHAB, w->fc_alpha_b, 1);
-    if (no_view) stage(T_RGBW, w->fc_rgb_w, (size_t)3 * H);
-    else {
-        stage(T_FEATW, w->fc_feat_w, (size_t)H * H); stage(T_FEATB, w->fc_feat_b, H);
-        stage(T_DIRW, w->layers_dir0_w, (size_t)(H / 2) * (H + dd)); stage(T_DIRB, w->layers_dir0_b, H / 2);
-        stage(T_RGBW, w->fc_rgb_w, (size_t)3 * (H / 2));
-    }
-    stage(T_RGBB, w->fc_rgb_b, 3);
-    NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&rollback.d_flat), flat.size() * 4));
-    float* const d_flat = rollback.d_flat;
-    NM_HIP_CHECK(hipMemcpy(d_flat, flat.data(), flat.size() * 4, hipMemcpyHostToDevice));
-    WeightPtrs ptrs;
-    std::memset(&ptrs, 0, sizeof(ptrs));
-    ptrs.p[T_L1W] = d_flat + offs[T_L1W]; ptrs.p[T_L1B] = d_flat + offs[T_L1B];
-    for (int t = T_XYZ0; t < T_XYZ0 + 2 * (L - 1); ++t) ptrs.p[t] = d_flat + offs[t];
-    for (int t = T_FEATW; t < T_COUNT; ++t) ptrs.p[t] = d_flat + offs[t];
-    int rc = launch_gather(m, ptrs, nullptr);
-    if (rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) { set_error("parameter gather failed"); rc = 1; }
-    if (rc) return rc;
+    if (int rc = upload_indices(m, px)) return rc;
+    if (int rc = fill_args(m, w, px.lay)) return rc;
+    if (int rc = stage_and_gather(m, w, &rollback.d_flat)) return rc;
     rollback.keep = true;
     *out = m;
     return 0;
@@ -776,12 +437,7 @@ int nm_mlp_create_ex(const nm_mlp_desc* desc, const nm_mlp_weights* w, int devic
 int nm_mlp_refresh(nm_mlp* m, const nm_mlp_weights* d_weights, void* stream) {
     NM_REQUIRE(m && d_weights, "null argument");
     WeightPtrs ptrs;
-    weight_pointers(m->desc, *d_weights, ptrs);
-    for (int t = 0; t < T_COUNT; ++t) {
-        const bool view_branch = t == T_FEATW || t == T_FEATB || t == T_DIRW || t == T_DIRB;
-        const bool used = (t < T_XYZ0 + 2 * (m->desc.num_layers - 1) || t >= T_FEATW) && !(view_branch && !m->desc.use_viewdirs);
-        NM_REQUIRE(!used || ptrs.p[t], "nm_mlp_refresh: missing tensor");
-    }
+    if (int rc = weight_pointers(m->desc, *d_weights, ptrs, "nm_mlp_refresh")) return rc;
     return launch_gather(m, ptrs, static_cast<hipStream_t>(stream));
 }
 
@@ -858,12 +514,7 @@ int nm_mlp_export_xyz_weight(nm_mlp* m, int32_t layer, float* d_out, void* strea
 int nm_mlp_weights_current(nm_mlp* m, const nm_mlp_weights* d_weights, void* stream_, int32_t* differs) {
     NM_REQUIRE(m && d_weights && differs, "null argument");
     WeightPtrs ptrs;
-    weight_pointers(m->desc, *d_weights, ptrs);
-    for (int t = 0; t < T_COUNT; ++t) {
-        const bool view_branch = t == T_FEATW || t == T_FEATB || t == T_DIRW || t == T_DIRB;
-        const bool used = (t < T_XYZ0 + 2 * (m->desc.num_layers - 1) || t >= T_FEATW) && !(view_branch && !m->desc.use_viewdirs);
-        NM_REQUIRE(!used || ptrs.p[t], "nm_mlp_weights_current: missing tensor");
-    }
+    if (int rc = weight_pointers(m->desc, *d_weights, ptrs, "nm_mlp_weights_current")) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const int64_t n = (int64_t)m->blob_floats;
     NM_HIP_CHECK(hipMemsetAsync(m->d_check + 1, 0, 8, stream));
@@ -925,12 +576,7 @@ int nm_mlp_sample_density(nm_mlp* m, const float* d_points, int64_t n, float* d_
 int nm_mlp_eval_rays(nm_mlp* m, const float* d_origins, int origins_per_ray, const float* d_dirs, const float* d_t,
                      int64_t rays, int32_t samples, float* d_radiance, void* stream) {
     NM_REQUIRE(m && d_origins && d_dirs && d_t && d_radiance && rays >= 0 && samples > 0, "bad argument");
-    MlpArgs a = m->base;
-    a.mode = MODE_RAYS;
-    a.a = d_origins; a.b = d_dirs; a.c = d_t;
-    a.origins_per_ray = origins_per_ray; a.samples = samples;
-    a.n = rays * samples; a.out = d_radiance;
-    return launch_mlp_timed(m, a, 0, static_cast<hipStream_t>(stream));
+    return launch_mlp_timed(m, ray_mode_args(m, d_origins, origins_per_ray, d_dirs, d_t, rays, samples, d_radiance), 0, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -16,8 +16,8 @@
 //   B (activ.) : lane l holds act[k = l>>4][sample = l&15]      (one VGPR)
 //   D          : lane l, reg r holds out[row = 4*(l>>4)+r][sample = l&15]
 // so D of tile nt, register r is exactly the B operand of the NEXT layer's k-step s = 4*nt + r, in
-// which lane group g = l>>4 supplies input feature k = 16*nt + 4*g + r.  The packer (mlp_api.hip: an
-// index map built once on the host + one gather kernel) permutes the weight columns accordingly, which
+// which lane group g = l>>4 supplies input feature k = 16*nt + 4*g + r.  The packer (mlp_pack.h: an
+// index map built once on the host; mlp_api.hip: one gather kernel) permutes the weight columns accordingly, which
 // is why bias+ReLU'd accumulators feed the next layer's MFMAs directly: no LDS round trip, no transposes, no HBM traffic for
 // activations.  Weights (2.4 MB / model, L2-resident) are the only streamed operand:
 // every workgroup pulls the same linear "A-operand stream" through a 2-deep LDS ring in 8-k-step
@@ -29,7 +29,6 @@
 #include <stdlib.h>
 
 #include <iterator>
-#include <mutex>
 #include <vector>
 
 #include "nm_internal.h"
@@ -188,7 +187,7 @@ const MlpPlan* find_generic_plan(int H, int L, bool long_encoding) {
         if (!long_encoding) want = (atoi(v) == 200 || atoi(v) == 201 || atoi(v) == 310) ? atoi(v) : 0;
 #endif
     for (const MlpPlan& p : all_plans())
-        if (p.generic_nt && p.variant == want && p.H >= H && g_lds_bytes(p.ring_bytes, p.generic_nt, L, p.variant == G_LONG_VARIANT ? G_ENC_PARTS : 1) <= 160 * 1024) return &p;
+        if (p.generic_nt && p.variant == want && p.H >= H && forward_lds_bytes(p, H, L, 0) <= 160 * 1024) return &p;
     return nullptr;
 }
 
@@ -197,16 +196,11 @@ int mlp_plan_info(const MlpPlan* p, int* nw) {
     return p->generic_nt ? 1000 + p->generic_nt : p->variant;     // generic family: 1000 + width class
 }
 
-// The handle's device must be current for the launch (the stream belongs to it): a model on cuda:1 used from a process
-// whose current device is cuda:0 is switched to for the call and switched back.
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int want) {
-        int cur = -1;
-        if (hipGetDevice(&cur) == hipSuccess && cur != want && hipSetDevice(want) == hipSuccess) prev = cur;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+int forward_lds_bytes(const MlpPlan& p, int H, int L, int head_floats) {
+    if (p.generic_nt)      // padded widths, both head layouts, the two argument tables (mlp_device_g.h)
+        return g_lds_bytes(p.ring_bytes, p.generic_nt, L, p.variant == G_LONG_VARIANT ? G_ENC_PARTS : 1);
+    return p.ring_bytes + (p.lds_bias ? tuned_cache_bytes(H, L, head_floats) : 0);
+}
 
 int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream_t stream) {
     const MlpPlan* p = m->plan;
@@ -218,7 +212,7 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream
     if (m->precision == NM_PREC_BF16X3) {
         const B3Plan* b = find_b3_plan(H, m->desc.num_encoding_fn_xyz, m->desc.num_encoding_fn_dir);
         NM_REQUIRE(b && m->d_stream_b3, "no bf16x3 kernel for this network");
-        const int lds_bytes = 3 * b->chunk_units * B3_UNIT + (((H * (1 + L) + H / 2 + 4 + H + 3 * H / 2 + 32) * 4 + 255) & ~255);   // + the two band tables
+        const int lds_bytes = 3 * b->chunk_units * B3_UNIT + tuned_cache_bytes(H, L, 3 * H / 2 + 32);   // + the two band tables
         NM_REQUIRE(lds_bytes <= 160 * 1024, "LDS budget exceeded (bf16x3 ring + bias cache): too many layers");
         auto b3_kernel = b->kernel;
         unsigned b3_threads = 512;
@@ -226,51 +220,21 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream
         if (const char* v = getenv("NM_MLP_VARIANT"))       // experiment: 4 waves x 32 samples, the same 128-sample workgroup
             if (atoi(v) == 300) { b3_kernel = b->kernel_w; b3_threads = 256; }
 #endif
-        NM_HIP_CHECK(hipFuncSetAttribute((const void*)b3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        if (int rc = ensure_dynamic_lds((const void*)b3_kernel, lds_bytes)) return rc;
         MlpArgs a = args;
         a.wstream = static_cast<const char*>(m->d_stream_b3);
-        const int64_t wg_iters = (a.n + 127) / 128;
-        int64_t grid = wg_iters < (int64_t)m->num_cus * 4 ? wg_iters : (int64_t)m->num_cus * 4;
-        if (wg_iters > grid) {
-            const int64_t rounds = (wg_iters + grid - 1) / grid;
-            grid = (wg_iters + rounds - 1) / rounds;
-        }
-        hipLaunchKernelGGL(b3_kernel, dim3((unsigned)grid), dim3(b3_threads), lds_bytes, stream, a, L, density_only);
+        const unsigned grid = persistent_grid((a.n + 127) / 128, m->num_cus);
+        hipLaunchKernelGGL(b3_kernel, dim3(grid), dim3(b3_threads), lds_bytes, stream, a, L, density_only);
         NM_HIP_CHECK(hipGetLastError());
         return 0;
     }
-    // bias cache + fc_alpha + fc_rgb rows; a use_viewdirs = 0 network (mode 2) keeps three H-wide fc_out rows where fc_rgb's
-    // three H/2-wide ones go
-    const int rgb_floats = density_only == 2 ? 3 * H : 3 * H / 2;
-    int lds_bytes = p->ring_bytes + (p->lds_bias ? (((H * (1 + L) + H / 2 + 4 + H + rgb_floats) * 4 + 255) & ~255) : 0);
-    if (p->generic_nt) {    // padded widths, both head layouts, the two argument tables (mlp_device_g.h)
-        lds_bytes = g_lds_bytes(p->ring_bytes, p->generic_nt, L, p->variant == G_LONG_VARIANT ? G_ENC_PARTS : 1);
-    }
+    // a use_viewdirs = 0 network (mode 2) keeps three H-wide fc_out rows where fc_rgb's three H/2-wide ones go
+    const int lds_bytes = forward_lds_bytes(*p, H, L, density_only == 2 ? 3 * H : 3 * H / 2);
     NM_REQUIRE(lds_bytes <= 160 * 1024, "LDS budget exceeded (ring + bias cache)");
-    // the dynamic-LDS attribute is per device: tracked per (device, plan)
-    // (two host threads creating / launching models race on it otherwise: the table is read and written under a lock)
-    static std::vector<int> attr_bytes(64 * 2 * all_plans().size(), 0);
-    static std::mutex attr_lock;
-    const int idx = 2 * (int)(p - all_plans().data()) + (density_only == 2 ? 1 : 0), dev = (m->device >= 0 && m->device < 64) ? m->device : 0;
-    {
-        std::lock_guard<std::mutex> hold(attr_lock);
-        int& have = attr_bytes[(size_t)dev * 2 * all_plans().size() + idx];
-        if (have < lds_bytes) {
-            NM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-            have = lds_bytes;
-        }
-    }
+    if (int rc = ensure_dynamic_lds((const void*)kernel, lds_bytes)) return rc;
     const int64_t wg_iters = (args.n + p->wg_samples - 1) / p->wg_samples;
-    const int64_t resident = (int64_t)m->num_cus * p->wg_per_cu;   // workgroups co-resident on the chip
-    // persistent-style launch: a few workgroups per CU queue so the tail is balanced.
-    int64_t grid = wg_iters < resident * 4 ? wg_iters : resident * 4;
-    // keep the per-workgroup iteration count even across the grid where possible
-    if (wg_iters > grid) {
-        const int64_t rounds = (wg_iters + grid - 1) / grid;
-        grid = (wg_iters + rounds - 1) / rounds;
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(p->NW * 64), lds_bytes, stream, args,
-                       (int)m->desc.num_layers, density_only);
+    const unsigned grid = persistent_grid(wg_iters, (int64_t)m->num_cus * p->wg_per_cu);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(p->NW * 64), lds_bytes, stream, args, (int)m->desc.num_layers, density_only);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }

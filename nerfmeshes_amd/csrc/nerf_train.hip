@@ -13,7 +13,6 @@
 // Roofline: MFMA.  557 056 MAC / sample for the 8x256 net (vs 593 408 forward).
 #include <cstdlib>
 #include <map>
-#include <mutex>
 #include <utility>
 
 #include "nm_internal.h"
@@ -273,27 +272,6 @@ static const BwdPlan g_bwd_plans[] = {
     {64, &mlp_backward_kernel<64, 8, KC>, &mlp_backward_kernel<64, 8, KC, true>},
 };
 
-static unsigned persistent_grid(int64_t wg_iters, int num_cus) {
-    const int64_t resident = num_cus;   // one 8-wave workgroup per CU (2 waves / SIMD)
-    int64_t grid = wg_iters < resident * 4 ? wg_iters : resident * 4;
-    if (wg_iters > grid) {
-        const int64_t rounds = (wg_iters + grid - 1) / grid;
-        grid = (wg_iters + rounds - 1) / rounds;
-    }
-    return (unsigned)grid;
-}
-
-struct DeviceGuardT {        // the handle's device current for the call (as nerf_mlp.hip's DeviceGuard)
-    int prev = -1;
-    explicit DeviceGuardT(int want) {
-        int cur = -1;
-        if (hipGetDevice(&cur) == hipSuccess && cur != want && hipSetDevice(want) == hipSuccess) prev = cur;
-    }
-    ~DeviceGuardT() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-static int set_lds(const void* fn, int bytes) { return ensure_dynamic_lds(fn, bytes); }
-
 }  // namespace nm
 
 using namespace nm;
@@ -320,28 +298,19 @@ int nm_mlp_forward_train(nm_mlp* m, const float* d_origins, int origins_per_ray,
     NM_REQUIRE(tape->v_stride >= 0 && (tape->v_stride == 0 || tape->v_stride >= d.hidden_size / 2), "nm_mlp_tape.v_stride is smaller than a row of d_v");
     NM_REQUIRE(!generic || tape->v_stride == 0 || tape->v_stride == d.hidden_size / 2, "only the tuned family writes d_v with a row stride (v_stride)");
     NM_REQUIRE(!tape->skip_h0 || (!generic && d.num_layers >= 2), "nm_mlp_tape.skip_h0 is a tuned-family option");
+    MlpArgs a = ray_mode_args(m, d_origins, origins_per_ray, d_dirs, d_t, rays, samples, d_radiance);
     if (m->lw) {             // beyond the fused families: layer by layer (nerf_layerwise.hip); the tape is rows, no masks
-        MlpArgs a = m->base;
-        a.mode = MODE_RAYS;
-        a.a = d_origins; a.b = d_dirs; a.c = d_t;
-        a.origins_per_ray = origins_per_ray; a.samples = samples;
-        a.n = rays * samples; a.out = d_radiance;
-        DeviceGuardT guard(m->device);
+        DeviceGuard guard(m->device);
         return layerwise_forward_train(m, a, tape, static_cast<hipStream_t>(stream));
     }
     if (generic) {
-        MlpArgs a = m->base;
-        a.mode = MODE_RAYS;
-        a.a = d_origins; a.b = d_dirs; a.c = d_t;
-        a.origins_per_ray = origins_per_ray; a.samples = samples;
-        a.n = rays * samples; a.out = d_radiance;
         if (a.n == 0) return 0;
         a.tape_h = tape->d_h; a.tape_feat = tape->d_feat; a.tape_v = tape->d_v;
         a.tiles = (a.n + 15) / 16;
         const MlpPlan* p = m->plan;
         const int L = d.num_layers;
-        const int lds_bytes = g_lds_bytes(p->ring_bytes, p->generic_nt, L, p->variant == G_LONG_VARIANT ? G_ENC_PARTS : 1);
-        if (int rc = set_lds((const void*)p->kernel_tape, lds_bytes)) return rc;
+        const int lds_bytes = forward_lds_bytes(*p, d.hidden_size, L, 0);
+        if (int rc = ensure_dynamic_lds((const void*)p->kernel_tape, lds_bytes)) return rc;
         const int64_t wg_iters = (a.n + p->wg_samples - 1) / p->wg_samples;
         hipLaunchKernelGGL(p->kernel_tape, dim3(persistent_grid(wg_iters, m->num_cus)), dim3(p->NW * 64), lds_bytes,
                            static_cast<hipStream_t>(stream), a, L, flat ? 2 : 0);
@@ -358,11 +327,6 @@ int nm_mlp_forward_train(nm_mlp* m, const float* d_origins, int origins_per_ray,
             for (const TrainPlan& p : g_train_plans3)
                 if (p.H == plan->H && p.FX == plan->FX && p.FD == plan->FD) { plan = &p; break; }
 #endif
-    MlpArgs a = m->base;
-    a.mode = MODE_RAYS;
-    a.a = d_origins; a.b = d_dirs; a.c = d_t;
-    a.origins_per_ray = origins_per_ray; a.samples = samples;
-    a.n = rays * samples; a.out = d_radiance;
     if (a.n == 0) return 0;
     a.tape_h = tape->d_h; a.tape_feat = tape->d_feat; a.tape_v = tape->d_v;
     a.tape_v_ld = tape->v_stride > 0 ? tape->v_stride : d.hidden_size / 2;
@@ -375,9 +339,9 @@ int nm_mlp_forward_train(nm_mlp* m, const float* d_origins, int origins_per_ray,
     }
     const int H = d.hidden_size, L = d.num_layers;
     const int ring = plan->ring_slots * KC * (H / 16) * 256;
-    const int lds_bytes = ring + (((H * (1 + L) + H / 2 + 4 + H + (flat ? 3 * H : 3 * H / 2)) * 4 + 255) & ~255);
+    const int lds_bytes = ring + tuned_cache_bytes(H, L, flat ? 3 * H : 3 * H / 2);
     const auto kernel = flat ? plan->forward_flat : plan->forward;
-    if (int rc = set_lds((const void*)kernel, lds_bytes)) return rc;
+    if (int rc = ensure_dynamic_lds((const void*)kernel, lds_bytes)) return rc;
     const int64_t wg_iters = (a.n + 127) / 128;
     hipLaunchKernelGGL(kernel, dim3(persistent_grid(wg_iters, m->num_cus)), dim3(512), lds_bytes,
                        static_cast<hipStream_t>(stream), a, L, flat ? 2 : 0);
@@ -409,7 +373,7 @@ int nm_mlp_backward_ex(nm_mlp* m, int64_t n, const nm_mlp_tape* tape, const floa
     NM_REQUIRE(m->precision == NM_PREC_F32, "training runs in fp32: create the handle with NM_PREC_F32");
     if (n == 0) return 0;
     if (m->lw) {
-        DeviceGuardT guard(m->device);
+        DeviceGuard guard(m->device);
         return layerwise_backward(m, n, tape, d_radiance, d_grad_radiance, deltas, static_cast<hipStream_t>(stream));
     }
     if (generic) {
@@ -420,7 +384,7 @@ int nm_mlp_backward_ex(nm_mlp* m, int64_t n, const nm_mlp_tape* tape, const floa
         a.tape_h = tape->d_h; a.tape_feat = tape->d_feat; a.tape_v = tape->d_v;
         const MlpPlan* p = m->plan;
         const int lds_bytes = g_bwd_lds_bytes(p->ring_bytes, p->generic_nt);
-        if (int rc = set_lds((const void*)p->kernel_bwd, lds_bytes)) return rc;
+        if (int rc = ensure_dynamic_lds((const void*)p->kernel_bwd, lds_bytes)) return rc;
         const int64_t wg_iters = (n + p->wg_samples - 1) / p->wg_samples;
         hipLaunchKernelGGL(p->kernel_bwd, dim3(persistent_grid(wg_iters, m->num_cus)), dim3(p->NW * 64), lds_bytes,
                            static_cast<hipStream_t>(stream), a, (int)d.num_layers, flat ? 1 : 0);
@@ -440,7 +404,7 @@ int nm_mlp_backward_ex(nm_mlp* m, int64_t n, const nm_mlp_tape* tape, const floa
     const int H = d.hidden_size;
     const int lds_bytes = 2 * KC * (H / 16) * 256 + (((H + (flat ? 3 * H : 3 * H / 2)) * 4 + 255) & ~255);
     const auto kernel = flat ? plan->backward_flat : plan->backward;
-    if (int rc = set_lds((const void*)kernel, lds_bytes)) return rc;
+    if (int rc = ensure_dynamic_lds((const void*)kernel, lds_bytes)) return rc;
     const int64_t wg_iters = (n + 127) / 128;
     hipLaunchKernelGGL(kernel, dim3(persistent_grid(wg_iters, m->num_cus)), dim3(512), lds_bytes,
                        static_cast<hipStream_t>(stream), a, (int)d.num_layers);

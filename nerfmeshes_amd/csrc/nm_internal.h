@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/nerfmeshes_hip.h"
+#include "mlp_pack.h"
 
 namespace nm {
 
@@ -151,11 +152,7 @@ struct MlpBwdArgs {
     int32_t stop_at_xyz0;    // tuned delta kernel: do not apply layers_xyz[0]^T (d_h[0] is not produced; NM_BACKWARD_STOP_AT_XYZ0)
 };
 
-// Flat addressing of the trainable tensors (index maps of the packed blob: tensor id << 24 | element)
-enum TensorId : int {
-    T_L1W = 0, T_L1B = 1, T_XYZ0 = 2 /* + 2i weight, + 2i + 1 bias */, T_FEATW = 66, T_FEATB, T_ALPHAW, T_ALPHAB,
-    T_DIRW, T_DIRB, T_RGBW, T_RGBB, T_COUNT
-};
+// Flat addressing of the trainable tensors (index maps of the packed blob: TensorId << 24 | element, mlp_pack.h)
 struct WeightPtrs { const float* p[T_COUNT]; };
 
 // host-side description of one template instantiation of the fused forward kernel
@@ -175,6 +172,41 @@ struct MlpPlan {
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, raised once per (device, kernel) and whenever a launch needs more --
 // not on every launch --, under a lock (the attribute is per device; two host threads would otherwise race on it).
 int ensure_dynamic_lds(const void* kernel, int bytes);
+
+// ---- launch helpers shared by nerf_mlp.hip, nerf_train.hip and mlp_api.hip ---------------------------------------------
+// The handle's device must be current for the launch (the stream belongs to it): a model on cuda:1 used from a process
+// whose current device is cuda:0 is switched to for the call and switched back.
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int want) {
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur != want && hipSetDevice(want) == hipSuccess) prev = cur;
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// Persistent-style grid for wg_iters workgroup iterations with `resident` workgroups co-resident on the chip: a few workgroups
+// per CU queue so the tail is balanced, and the per-workgroup iteration count is even across the grid where possible.
+inline unsigned persistent_grid(int64_t wg_iters, int64_t resident) {
+    int64_t grid = wg_iters < resident * 4 ? wg_iters : resident * 4;
+    if (wg_iters > grid) {
+        const int64_t rounds = (wg_iters + grid - 1) / grid;
+        grid = (wg_iters + rounds - 1) / rounds;
+    }
+    return (unsigned)grid;
+}
+
+// What a tuned kernel keeps in LDS behind its weight ring: every bias, fc_alpha and `head_floats` of colour-head rows (3 H / 2:
+// fc_rgb; 3 H: the fc_out rows of a use_viewdirs = 0 network)
+inline int tuned_cache_bytes(int H, int L, int head_floats) { return ((H * (1 + L) + H / 2 + 4 + H + head_floats) * 4 + 255) & ~255; }
+
+// Dynamic LDS of a plan's forward kernels for an L-layer network: the generic family's own layout (g_lds_bytes, mlp_device_g.h),
+// else the plan's ring + the tuned cache (nerf_mlp.hip)
+int forward_lds_bytes(const MlpPlan& p, int H, int L, int head_floats);
+
+// the handle's MlpArgs for MODE_RAYS (mlp_api.hip)
+MlpArgs ray_mode_args(const nm_mlp* m, const float* d_origins, int origins_per_ray, const float* d_dirs, const float* d_t, int64_t rays,
+                      int32_t samples, float* d_radiance);
 
 // The general weight-gradient kernel (nerf_dw_g.hip) as a plain GEMM C = A^T B with a short contraction and a wide output:
 // the engine of the layer-wise network path (nerf_layerwise.hip).  `partial` receives the (out_pad x in_pad) result.
