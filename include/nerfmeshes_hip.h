@@ -671,6 +671,43 @@ int nm_surface_gather(const void* d_workspace, const float* d_origins, int per_r
                       int32_t width, int64_t row_offset, int64_t capacity, float* d_points, float* d_normals,
                       float* d_colors, uint8_t* d_colors_u8, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh components (mesh_nerf --min-component-faces / --keep-largest; DESIGN.md, "Mesh components").  An indexed triangle
+ * mesh on the device: d_faces (F,3) int32 with entries in [0, V).  Two vertices are connected when a triangle holds both; a
+ * component is a connected set of vertices plus the triangles on them.  Its LABEL is its smallest vertex index, its SIZE its
+ * number of triangles; a vertex in no triangle is a component of size 0.
+ *
+ * nm_mesh_components: d_labels (V,) int32 = the label of every vertex; d_face_counts (V,) int32 = the size of the component
+ *   at its label's entry, 0 everywhere else.  No host synchronisation.  A face with an index outside [0, V) joins nothing
+ *   and is counted in the first 8 bytes of the workspace (uint64), which nm_mesh_components_select turns into an error.
+ * nm_mesh_components_select: with those two arrays and the same workspace, decides what stays: components with fewer than
+ *   min_faces triangles are dropped; of the rest, with keep_largest = K > 0, the K with most triangles stay, ties going to
+ *   the smaller label (all of them when fewer than K are left); K = 0 keeps them all.  Returns on the HOST the numbers of
+ *   vertices and faces kept, of components in the mesh and of components kept (the one synchronisation of the stream),
+ *   and leaves the keep bits and their prefix sums in the workspace.  May be called again with other limits.
+ * nm_mesh_components_compact: with that workspace, writes the kept rows IN THEIR ORIGINAL ORDER: d_out_faces
+ *   (faces_kept,3) with vertices renumbered by the exclusive prefix sum of the vertex keep mask (numpy:
+ *   new = cumsum(keep_v) - 1; out = new[faces[keep_f]]), and for every input that is not NULL -- d_verts (V,3), d_normals (V,3),
+ *   d_values (V,) fp32, d_keys (V,) int64 -- its kept rows.  vertices_kept / faces_kept are the select call's and bound
+ *   every write.  No host synchronisation.
+ * V and F are in [0, 2^31 - 64); keep_largest is at most NM_MESH_KEEP_LARGEST_MAX.  The workspace
+ * (nm_mesh_components_workspace_bytes, 0 for sizes out of range; 256-byte aligned) must stay untouched between the calls.
+ * Argument errors return 2 before any HIP call.  Everything is integer work: the results do not depend on the order the
+ * workgroups ran in.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_MESH_KEEP_LARGEST_MAX 1024
+int64_t nm_mesh_components_workspace_bytes(int64_t num_vertices, int64_t num_faces);
+int nm_mesh_components(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t* d_labels,
+                       int32_t* d_face_counts, void* d_workspace, void* stream);
+int nm_mesh_components_select(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, const int32_t* d_labels,
+                              const int32_t* d_face_counts, int64_t min_faces, int32_t keep_largest, void* d_workspace,
+                              int64_t* h_vertices_kept, int64_t* h_faces_kept, int64_t* h_components,
+                              int64_t* h_components_kept, void* stream);
+int nm_mesh_components_compact(const void* d_workspace, const int32_t* d_faces, int64_t num_faces, int64_t num_vertices,
+                               const float* d_verts, const float* d_normals, const float* d_values, const int64_t* d_keys,
+                               int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
+                               float* d_out_normals, float* d_out_values, int64_t* d_out_keys, void* stream);
+
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex
  * per line, floats printed as nm_export_obj prints them (they read back to the same fp32); binary != 0:

@@ -189,6 +189,13 @@ SIGNATURES = {
                                     C.c_double, C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nm_surface_gather": (C.c_int, [c_void_p, c_void_p, C.c_int, c_void_p, c_void_p, c_void_p, C.c_double, c_void_p, C.c_int32,
                                     C.c_int32, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_components_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "nm_mesh_components": (C.c_int, [c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_components_select": (C.c_int, [c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, C.c_int64, C.c_int32, c_void_p,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), c_void_p]),
+    "nm_mesh_components_compact": (C.c_int, [c_void_p, c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 

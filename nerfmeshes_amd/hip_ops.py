@@ -655,6 +655,93 @@ def mc_refine_vertices(volume, z_global, level, keys, ss, fine_sigma, verts):
     return verts
 
 
+KEEP_LARGEST_MAX = 1024
+
+
+def _mesh_faces(faces, num_vertices):
+    """(F,3) contiguous int32 faces on the GPU + the two sizes, checked."""
+    if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+        raise _lib.HipLibraryError("faces must live in GPU memory; there is no CPU path")
+    if faces.dtype is not torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be an (F,3) int32 tensor, got {tuple(faces.shape)} {faces.dtype}")
+    nv, nf = int(num_vertices), int(faces.shape[0])
+    if nv < 0 or (nf and not nv):
+        raise ValueError(f"a mesh of {nf} faces over {nv} vertices")
+    return faces.detach().contiguous(), nv, nf
+
+
+def _mesh_components(lib, faces, nv, nf):
+    dev = faces.device
+    labels = torch.empty(nv, dtype=torch.int32, device=dev)
+    counts = torch.empty(nv, dtype=torch.int32, device=dev)
+    nbytes = int(lib.nm_mesh_components_workspace_bytes(nv, nf))
+    if nbytes == 0:
+        raise ValueError(f"mesh components: {nv} vertices / {nf} faces are beyond the supported sizes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib.nm_mesh_components(_ptr(faces), nf, nv, _ptr(labels), _ptr(counts), _ptr(ws), _stream()), "nm_mesh_components")
+    return labels, counts, ws
+
+
+def mesh_components(faces, num_vertices):
+    """Connected components of an indexed triangle mesh (nm_mesh_components; semantics in include/nerfmeshes_hip.h).
+    faces: (F,3) int32 CUDA tensor with entries in [0, num_vertices) -> (labels (V,) int32: every vertex's component, named by
+    its smallest vertex index; face_counts (V,) int32: the component's number of triangles at that index, 0 elsewhere).
+    Raises ValueError for a face index out of range (the one read-back of this call)."""
+    lib = _lib.load()
+    faces, nv, nf = _mesh_faces(faces, num_vertices)
+    labels, counts, ws = _mesh_components(lib, faces, nv, nf)
+    bad = int(ws[:8].view(torch.int64).item())
+    if bad:
+        raise ValueError(f"mesh components: {bad} faces have a vertex index outside [0, {nv})")
+    return labels, counts
+
+
+def mesh_filter_components(verts, faces, normals, values=None, keys=None, min_faces=0, keep_largest=0):
+    """Drops whole components of a mesh (nm_mesh_components + _select + _compact): those with fewer than `min_faces` triangles,
+    and, with keep_largest = K > 0, all but the K with most triangles of the rest (ties to the smaller label; fewer than K:
+    all of them).  verts (V,3) f32, faces (F,3) i32, normals (V,3) f32, values (V,) f32 or None, keys (V,) i64 or None, all on
+    the GPU -> (verts, faces, normals, values, keys, info): the kept rows in their original order, faces renumbered
+    (numpy: new = cumsum(keep_v) - 1; new[faces[keep_f]]), None where None came in; info = dict(components, components_kept,
+    faces, faces_kept, vertices, vertices_kept).  Nothing left gives empty (0,3) arrays."""
+    lib = _lib.load()
+    min_faces, keep_largest = int(min_faces), int(keep_largest)
+    if min_faces < 0 or keep_largest < 0:
+        raise ValueError("min_faces and keep_largest must be >= 0")
+    if keep_largest > KEEP_LARGEST_MAX:
+        raise ValueError(f"keep_largest is at most {KEEP_LARGEST_MAX}, got {keep_largest}")
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = _dev32(verts, dev, "verts")
+    normals = _dev32(normals, dev, "normals")
+    values = _dev32(values, dev, "values") if values is not None else None
+    if keys is not None:
+        if keys.dtype is not torch.int64 or keys.device != dev:
+            raise ValueError("keys must be an int64 tensor on the faces' device")
+        keys = keys.contiguous()
+    if verts.shape != (nv, 3) or normals.shape != (nv, 3) or (values is not None and values.shape != (nv,)) or \
+            (keys is not None and keys.shape != (nv,)):
+        raise ValueError("mesh_filter_components: the per-vertex arrays disagree on the vertex count")
+    labels, counts, ws = _mesh_components(lib, faces, nv, nf)
+    kv, kf, comps, kept = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    rc = lib.nm_mesh_components_select(_ptr(faces), nf, nv, _ptr(labels), _ptr(counts), min_faces, keep_largest, _ptr(ws),
+                                       C.byref(kv), C.byref(kf), C.byref(comps), C.byref(kept), _stream())
+    if rc == 2:
+        raise ValueError((lib.nm_last_error() or b"nm_mesh_components_select: bad argument").decode())
+    check(rc, "nm_mesh_components_select")
+    out_verts = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
+    out_normals = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
+    out_faces = torch.empty(kf.value, 3, dtype=torch.int32, device=dev)
+    out_values = torch.empty(kv.value, dtype=torch.float32, device=dev) if values is not None else None
+    out_keys = torch.empty(kv.value, dtype=torch.int64, device=dev) if keys is not None else None
+    if kv.value:
+        check(lib.nm_mesh_components_compact(_ptr(ws), _ptr(faces), nf, nv, _ptr(verts), _ptr(normals), _ptr(values), _ptr(keys),
+                                             kv.value, kf.value, _ptr(out_verts), _ptr(out_faces), _ptr(out_normals),
+                                             _ptr(out_values), _ptr(out_keys), _stream()), "nm_mesh_components_compact")
+    info = dict(components=comps.value, components_kept=kept.value, faces=nf, faces_kept=kf.value, vertices=nv,
+                vertices_kept=kv.value)
+    return out_verts, out_faces, out_normals, out_values, out_keys, info
+
+
 SURFACE_STEP_MAX = 8
 
 

@@ -269,14 +269,37 @@ def network_normals(net, vertices, normals):
     return torch.where(ok, -g / norm, normals.to(g.device)), ~ok[:, 0]
 
 
+def filter_components(vertices, triangles, normals, min_faces, keep_largest):
+    """`--min-component-faces N` / `--keep-largest K` on the device (hip_ops.mesh_filter_components): components -- vertices
+    joined by triangles -- with fewer than N triangles go; of the rest the K with most triangles stay (ties: the one holding
+    the smaller vertex index).  Kept vertices and triangles stay in their order.  ValueError when nothing is left."""
+    vertices, triangles, normals, _, _, info = hip_ops.mesh_filter_components(
+        vertices, triangles.to(torch.int32), normals, min_faces=min_faces, keep_largest=keep_largest)
+    if info["faces_kept"] == 0:
+        raise ValueError(f"no mesh component has at least {max(min_faces, 1)} faces: the filter (--min-component-faces {min_faces}, "
+                         f"--keep-largest {keep_largest}) leaves nothing of {info['components']} components / {info['faces']} faces")
+    print(f"Component filter: kept {info['components_kept']} of {info['components']} components, {info['faces_kept']} of "
+          f"{info['faces']} faces, {info['vertices_kept']} of {info['vertices']} vertices")
+    return vertices, triangles, normals
+
+
 def export_marching_cubes(model, args, cfg, device):
     """mesh_nerf.py:131-201.  `--super-sampling N >= 1` refines the geometry (extract_geometry_with_super_sampling); the
     appearance, the cache and the OBJ are the same steps as without it.  `--normals network` replaces the geometry stage's grid
-    normals by the network's (network_normals) before the appearance query and the OBJ; the cache keeps the grid normals."""
+    normals by the network's (network_normals) before the appearance query and the OBJ; the cache keeps the grid normals.
+    `--min-component-faces` / `--keep-largest` drop whole connected components (filter_components) right after the geometry stage
+    or the cache load -- before the network normals and the appearance query, so no ray is spent on a dropped vertex; the cache
+    keeps the unfiltered geometry.  Under torch.distributed every rank filters the gathered mesh redundantly."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
     normals_mode = getattr(args, "normals", "grid")
     if normals_mode == "network" and getattr(args, "route", "kernel") == "script":
         raise ValueError("--normals network has no --route script: the reference's script only has the grid's normals")
+    min_faces, keep_largest = int(getattr(args, "min_component_faces", 0)), int(getattr(args, "keep_largest", 0))
+    if min_faces or keep_largest:
+        if getattr(args, "route", "kernel") == "script":
+            raise ValueError("--min-component-faces / --keep-largest have no --route script: the reference's script has no such step")
+        if min_faces < 0 or not 0 <= keep_largest <= hip_ops.KEEP_LARGEST_MAX:
+            raise ValueError(f"--min-component-faces must be >= 0 and --keep-largest in [0, {hip_ops.KEEP_LARGEST_MAX}]")
     from . import dist as nd
     cache_path = os.path.join(args.save_dir, args.cache_name)
     cached = os.path.exists(cache_path)
@@ -285,15 +308,20 @@ def export_marching_cubes(model, args, cfg, device):
         print("Loading cached mesh geometry...")
         vertices, triangles, normals, density = torch.load(cache_path, weights_only=False)
         vertices, triangles, normals = (torch.as_tensor(t).to(device) for t in (vertices, triangles, normals))
+        if min_faces or keep_largest:
+            vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
     else:
         print("Generating mesh geometry...")
         vertices, triangles, normals, density = geometry(model, device, args)
+        unfiltered = vertices, triangles, normals          # what the cache keeps, so that the filter can be tuned on it
+        if min_faces or keep_largest:                      # first: a filter that leaves nothing raises before anything is written
+            vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
         if cache_new or args.override_cache_mesh:
             if nd.world()[1] > 1 and getattr(args, "gather", "triangles") == "triangles":
                 density = _assemble_grid_from_slabs(density, _nums(args.res), device)   # the cache holds the whole grid
             if nd.world()[0] == 0:
-                torch.save((vertices.cpu(), triangles.cpu(), normals.cpu(),
-                            density.cpu().numpy() if isinstance(density, torch.Tensor) else density), cache_path)
+                torch.save(tuple(t.cpu() for t in unfiltered) + (
+                            density.cpu().numpy() if isinstance(density, torch.Tensor) else density,), cache_path)
                 print(f"Cached mesh geometry saved to {cache_path}")
 
     # Appearance: one query per vertex.  Vertices are independent, so under torch.distributed every rank queries a
@@ -341,6 +369,13 @@ def export_marching_cubes(model, args, cfg, device):
     return vertices, triangles, normals, diffuse
 
 
+def _non_negative(text):
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError(f"must be >= 0, got {n}")
+    return n
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--log-checkpoint", type=str, default=None)
@@ -369,6 +404,11 @@ def build_parser():
                    help="(addition) vertex normals of the appearance rays and the OBJ: grid (default) -- marching cubes' "
                         "gradient of the density grid -- or network: -grad sigma / |grad sigma| of the network at the final "
                         "vertices")
+    p.add_argument("--min-component-faces", type=_non_negative, default=0,
+                   help="(addition) drop every connected component of the mesh with fewer than this many triangles (0 = off)")
+    p.add_argument("--keep-largest", type=_non_negative, default=0,
+                   help="(addition) of the components left, keep only this many with the most triangles, ties going to the one "
+                        "that holds the smaller vertex index (0 = off)")
     p.add_argument("--gather", choices=("triangles", "grid"), default="triangles",
                    help="(addition, multi-GPU) what travels between the ranks: the emitted triangles of per-slab marching "
                         "cubes (default) or the density grid")
