@@ -708,6 +708,42 @@ int nm_mesh_components_compact(const void* d_workspace, const int32_t* d_faces, 
                                int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
                                float* d_out_normals, float* d_out_values, int64_t* d_out_keys, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh quality: chamfer distance (mesh_chamfer, mesh_nerf --target-mesh, the validation chamfer branch; DESIGN.md, "Mesh
+ * quality: chamfer distance").  All arrays on the device; d_verts (V,3) fp32, d_faces (F,3) int32.  Every fp32 operation
+ * below is rounded on its own (no fused multiply-add), sqrt and division correctly rounded, in the order written, so a
+ * numpy fp32 restatement (tests/mesh_metrics.py) reproduces every output bit for bit.
+ *
+ * nm_mesh_face_weights: area-proportional sampling weights as integers.  With e1 = v1 - v0, e2 = v2 - v0 and
+ *   c = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x): area = 0.5f * sqrt((cx cx + cy cy) + cz cz); a non-finite
+ *   area, and the area of a face with an index outside [0, V) (never dereferenced), is 0.  With m the largest area and
+ *   m = f * 2^e, f in [0.5, 1): weight_i = (uint64) trunc((double) area_i * 2^(32-e)), so the largest weight lies in
+ *   [2^31, 2^32) and A FACE WHOSE AREA IS BELOW m * 2^-32 HAS WEIGHT 0 AND IS NEVER SAMPLED.  d_areas (F,) fp32 (may be NULL);
+ *   d_cdf (F,) uint64 = the inclusive prefix sums of the weights: exact, whatever order the workgroups ran in.  The workspace
+ *   (nm_mesh_face_weights_workspace_bytes(), 16-byte aligned) begins with uint64 bad_faces (faces with an index out of
+ *   range), uint64 total = d_cdf[F-1] (0 for F = 0), uint32 float bits of m.  No host synchronisation.
+ * nm_mesh_sample_points: d_u (N,3) fp32 draws in [0, 1).  t = (uint64) trunc((double) u0 * (double) total); face = the first
+ *   i with d_cdf[i] > t (binary search; t is clamped to total - 1 for a draw outside [0, 1)); s = sqrt(u1), w0 = 1 - s,
+ *   w1 = s (1 - u2), w2 = s u2 (pytorch3d's barycentric weights); p = (w0 v0 + w1 v1) + w2 v2 per component.  Outputs, each
+ *   may be NULL: d_points (N,3), d_face_ids (N,) int32, d_normals (N,3) = c / |c| of the face.  total = 0 writes nothing:
+ *   read it from nm_mesh_face_weights' workspace first.  No host synchronisation.
+ * nm_points_nearest: d_x (N,3), d_y (M,3) fp32.  For every row i of x: d_dist2[i] = min over j of
+ *   ((dx dx + dy dy) + dz dz) with dx = x_i.x - y_j.x, ...; d_index[i] (int32) = the smallest j that attains it.  A pair whose
+ *   d2 is NaN never wins; a row that no pair wins (a NaN query, M = 0) gets (+inf, -1).  Brute force over all N * M pairs with
+ *   no N x M intermediate: the workspace is nm_points_nearest_workspace_bytes(N, M) = O(N) bytes (0 for sizes out of
+ *   range; 256-byte aligned).  The result does not depend on the order the workgroups ran in.  No host synchronisation.
+ * V, F, N and M are in [0, 2^31 - 64).  Argument errors return 2 before any HIP call.  Nothing allocates.
+ * ------------------------------------------------------------------------------------------ */
+int64_t nm_mesh_face_weights_workspace_bytes(void);
+int nm_mesh_face_weights(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces, float* d_areas,
+                         uint64_t* d_cdf, void* d_workspace, void* stream);
+int nm_mesh_sample_points(const float* d_u, int64_t num_points, const float* d_verts, int64_t num_vertices, const int32_t* d_faces,
+                          int64_t num_faces, const uint64_t* d_cdf, float* d_points, int32_t* d_face_ids, float* d_normals,
+                          void* stream);
+int64_t nm_points_nearest_workspace_bytes(int64_t num_x, int64_t num_y);
+int nm_points_nearest(const float* d_x, int64_t num_x, const float* d_y, int64_t num_y, float* d_dist2, int32_t* d_index,
+                      void* d_workspace, void* stream);
+
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex
  * per line, floats printed as nm_export_obj prints them (they read back to the same fp32); binary != 0:

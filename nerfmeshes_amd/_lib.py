@@ -196,6 +196,12 @@ SIGNATURES = {
                                             C.POINTER(C.c_int64), c_void_p]),
     "nm_mesh_components_compact": (C.c_int, [c_void_p, c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                              C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_face_weights_workspace_bytes": (C.c_int64, []),
+    "nm_mesh_face_weights": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_sample_points": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    "nm_points_nearest_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "nm_points_nearest": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 

@@ -48,10 +48,19 @@ class SynthesizableDataset(Dataset):
     """datasets.py:82-133: `synthesis()` replaces the images by a 360-degree orbit of novel views (no targets)."""
 
     STEP_SIZE = 3
+    target_mesh = None          # (verts (V,3) f32, faces (F,3) i32) host tensors once load_target_mesh() found <basedir>/model.obj
 
     def __init__(self):
         super().__init__()
         self.synthetic_bundle = None
+
+    def load_target_mesh(self):
+        """datasets.py:88-103 (commented out there): the ground-truth mesh `<dataset.basedir>/model.obj`, when the scene has
+        one, for the validation chamfer loss (`experiment.chamfer_loss`).  -> `target_mesh`, None when there is no such file."""
+        from ..nerf.nerf_helpers import load_obj
+        path = os.path.join(self.cfg.dataset.basedir, "model.obj")
+        self.target_mesh = load_obj(path) if os.path.exists(path) else None
+        return self.target_mesh
 
     def synthesis(self):
         print("Synthesizing dataset...")

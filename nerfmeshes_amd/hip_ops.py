@@ -742,6 +742,133 @@ def mesh_filter_components(verts, faces, normals, values=None, keys=None, min_fa
     return out_verts, out_faces, out_normals, out_values, out_keys, info
 
 
+def _mesh_arrays(verts, faces, what):
+    """(V,3) fp32 vertices and (F,3) int32 faces of one mesh on the GPU (host arrays are copied over), checked."""
+    verts = _dev32(verts if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.as_tensor(verts).cuda(), name="verts")
+    if not isinstance(faces, torch.Tensor):
+        faces = torch.as_tensor(faces)
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{what}: faces must be an integer tensor, got {faces.dtype}")
+    faces = faces.to(device=verts.device, dtype=torch.int32)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: verts must be (V,3) and faces (F,3), got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    return verts, faces, nv, nf
+
+
+def _mesh_face_weights(lib, verts, faces, nv, nf, what):
+    """areas, cdf and the total weight of a checked mesh; the header read-back is the one synchronisation."""
+    dev = verts.device
+    areas = torch.empty(nf, dtype=torch.float32, device=dev)
+    cdf = torch.empty(nf, dtype=torch.int64, device=dev)             # uint64 on the device; every prefix is below 2^63
+    hdr = torch.empty(int(lib.nm_mesh_face_weights_workspace_bytes()), dtype=torch.uint8, device=dev)
+    rc = lib.nm_mesh_face_weights(_ptr(verts), nv, _ptr(faces), nf, _ptr(areas), _ptr(cdf), _ptr(hdr), _stream())
+    if rc == 2:
+        raise ValueError((lib.nm_last_error() or b"nm_mesh_face_weights: bad argument").decode())
+    check(rc, "nm_mesh_face_weights")
+    bad, total = (int(v) for v in hdr[:16].view(torch.int64).tolist())
+    if bad:
+        raise ValueError(f"{what}: {bad} faces have a vertex index outside [0, {nv})")
+    return areas, cdf, total
+
+
+def mesh_face_weights(verts, faces):
+    """Area-proportional sampling weights of a triangle mesh (nm_mesh_face_weights; arithmetic in include/nerfmeshes_hip.h).
+    verts (V,3) f32, faces (F,3) i32 -> (areas (F,) f32, cdf (F,) int64: the inclusive prefix sums of the integer weights
+    trunc(area * 2^(32-e)), exact).  Raises ValueError for a face index out of range (the one read-back of this call)."""
+    lib = _lib.load()
+    verts, faces, nv, nf = _mesh_arrays(verts, faces, "mesh_face_weights")
+    areas, cdf, _ = _mesh_face_weights(lib, verts, faces, nv, nf, "mesh_face_weights")
+    return areas, cdf
+
+
+def mesh_sample_points(verts, faces, n=None, u=None, generator=None, return_normals=False):
+    """Points distributed uniformly over the surface of a triangle mesh (nm_mesh_face_weights + nm_mesh_sample_points):
+    draw row (u0, u1, u2) picks the face whose cdf interval holds trunc(u0 * total) and the barycentric weights
+    (1 - sqrt(u1), sqrt(u1) (1 - u2), sqrt(u1) u2), pytorch3d's.  `u` (N,3) in [0, 1) defaults to
+    torch.rand(n, 3, device=..., generator=generator).  -> (points (N,3) f32, face_ids (N,) i32[, normals (N,3): the face's
+    unit normal]).  ValueError when nothing can be sampled (no face, or only degenerate ones) or a face index is out of range."""
+    lib = _lib.load()
+    verts, faces, nv, nf = _mesh_arrays(verts, faces, "mesh_sample_points")
+    dev = verts.device
+    if u is None:
+        if n is None:
+            raise ValueError("mesh_sample_points: give the number of points n or the draws u")
+        u = torch.rand(int(n), 3, device=dev, generator=generator)
+    u = _dev32(u, dev, "u")
+    if u.dim() != 2 or u.shape[1] != 3 or (n is not None and u.shape[0] != int(n)):
+        raise ValueError(f"mesh_sample_points: u must be (n,3) draws, got {tuple(u.shape)}")
+    _, cdf, total = _mesh_face_weights(lib, verts, faces, nv, nf, "mesh_sample_points")
+    if total == 0:
+        raise ValueError(f"mesh_sample_points: a mesh of {nf} faces with no area cannot be sampled")
+    count = int(u.shape[0])
+    points = torch.empty(count, 3, dtype=torch.float32, device=dev)
+    face_ids = torch.empty(count, dtype=torch.int32, device=dev)
+    normals = torch.empty(count, 3, dtype=torch.float32, device=dev) if return_normals else None
+    rc = lib.nm_mesh_sample_points(_ptr(u), count, _ptr(verts), nv, _ptr(faces), nf, _ptr(cdf), _ptr(points), _ptr(face_ids),
+                                   _ptr(normals), _stream())
+    if rc == 2:
+        raise ValueError((lib.nm_last_error() or b"nm_mesh_sample_points: bad argument").decode())
+    check(rc, "nm_mesh_sample_points")
+    return (points, face_ids, normals) if return_normals else (points, face_ids)
+
+
+def _points(t, device, name):
+    t = _dev32(t, device, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be an (N,3) point cloud, got {tuple(t.shape)}")
+    return t
+
+
+def points_nearest(x, y):
+    """Exact nearest neighbour of every row of x (N,3) among the rows of y (M,3) (nm_points_nearest: brute force, no N x M
+    intermediate) -> (dist2 (N,) f32: the squared distance ((dx dx + dy dy) + dz dz), index (N,) i32: the smallest j that
+    attains it).  NaN pairs never win; a row without a winner (a NaN query, M = 0) gets (+inf, -1)."""
+    lib = _lib.load()
+    x = _points(x, None, "x")
+    dev = x.device
+    y = _points(y, dev, "y")
+    n, m = int(x.shape[0]), int(y.shape[0])
+    nbytes = int(lib.nm_points_nearest_workspace_bytes(n, m))
+    if nbytes == 0:
+        raise ValueError(f"points_nearest: {n} x {m} points are beyond the supported sizes")
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev)
+    index = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = _workspace(nbytes, dev)
+    check(lib.nm_points_nearest(_ptr(x), n, _ptr(y), m, _ptr(dist2), _ptr(index), _ptr(ws), _stream()), "nm_points_nearest")
+    return dist2, index
+
+
+def _nearest_dist2_sharded(x, y):
+    """dist2 of `points_nearest(x, y)`, the queries split over the ranks of torch.distributed: every rank searches its
+    dist.split_range slice against the whole of y and one dist.all_gather_rows assembles the (N,) array on every rank."""
+    from . import dist as nd
+    rank, world = nd.world()
+    if world == 1:
+        return points_nearest(x, y)[0]
+    n = int(x.shape[0])
+    counts = [b - a for a, b in (nd.split_range(n, r, world) for r in range(world))]
+    lo, hi = nd.split_range(n, rank, world)
+    return nd.all_gather_rows(points_nearest(x[lo:hi], y)[0].contiguous(), counts)
+
+
+def chamfer_distance(x, y):
+    """Chamfer distance of two point clouds x (N,3), y (M,3) with pytorch3d's `chamfer_distance` defaults (squared L2,
+    point_reduction="mean"): chamfer = mean_i min_j |x_i - y_j|^2 + mean_j min_i |y_j - x_i|^2.  -> dict: chamfer, x_to_y,
+    y_to_x (Python floats; the means are fp64 sums of the gathered (N,) / (M,) arrays only), dist2_x (N,), dist2_y (M,)
+    (device tensors).  Under torch.distributed every rank searches a slice of the queries and then reduces the same gathered
+    arrays: any number of ranks gives the single-rank result bit for bit."""
+    x = _points(x, None, "x")
+    y = _points(y, x.device, "y")
+    if x.shape[0] == 0 or y.shape[0] == 0:
+        raise ValueError(f"chamfer_distance: empty point cloud ({x.shape[0]} and {y.shape[0]} points)")
+    dist2_x = _nearest_dist2_sharded(x, y)
+    dist2_y = _nearest_dist2_sharded(y, x)
+    x_to_y = float(dist2_x.double().sum().item()) / dist2_x.shape[0]
+    y_to_x = float(dist2_y.double().sum().item()) / dist2_y.shape[0]
+    return dict(chamfer=x_to_y + y_to_x, x_to_y=x_to_y, y_to_x=y_to_x, dist2_x=dist2_x, dist2_y=dist2_y)
+
+
 SURFACE_STEP_MAX = 8
 
 

@@ -34,6 +34,13 @@ def create_mesh(vertices, faces_idx):
     return Meshes(verts=[vertices / max(vertices.abs().max(0)[0])], faces=[faces_idx])
 
 
+def normalize_vertices(vertices):
+    """`create_mesh`'s rule on plain tensors, wherever they live: subtract the vertex mean, then divide by the largest absolute
+    coordinate, so the mesh fits [-1, 1]^3 around its vertex centroid (what the chamfer measure compares, mesh_chamfer)."""
+    vertices = vertices - vertices.mean(0)
+    return vertices / vertices.abs().max()
+
+
 def _nums(nums):
     assert isinstance(nums, (tuple, list, int)), "Nums arg should be either iterable or int."
     if isinstance(nums, int):
@@ -283,6 +290,26 @@ def filter_components(vertices, triangles, normals, min_faces, keep_largest):
     return vertices, triangles, normals
 
 
+def chamfer_to_target(vertices, triangles, args, device):
+    """`--target-mesh PATH`: the chamfer distance between the extracted mesh and an OBJ file, both in world coordinates
+    (mesh_chamfer.compare_meshes with --chamfer-samples / --chamfer-seed), printed; rank 0 writes
+    <save-dir>/<mesh-name stem>.chamfer.json.  Under torch.distributed the searches are shared out over the ranks."""
+    from . import dist as nd
+    from . import mesh_chamfer
+    from .nerf.nerf_helpers import load_obj
+    target_vertices, target_faces = load_obj(args.target_mesh)
+    report = mesh_chamfer.compare_meshes(vertices, triangles, target_vertices, target_faces, samples=args.chamfer_samples,
+                                         seed=args.chamfer_seed, device=device)
+    report["target"]["path"] = args.target_mesh
+    for line in mesh_chamfer.format_report(report):
+        print(line)
+    if nd.world()[0] == 0:
+        path = os.path.join(args.save_dir, os.path.splitext(args.mesh_name)[0] + ".chamfer.json")
+        mesh_chamfer.write_report(report, path)
+        print(f"Chamfer report saved to {path}")
+    return report
+
+
 def export_marching_cubes(model, args, cfg, device):
     """mesh_nerf.py:131-201.  `--super-sampling N >= 1` refines the geometry (extract_geometry_with_super_sampling); the
     appearance, the cache and the OBJ are the same steps as without it.  `--normals network` replaces the geometry stage's grid
@@ -300,6 +327,12 @@ def export_marching_cubes(model, args, cfg, device):
             raise ValueError("--min-component-faces / --keep-largest have no --route script: the reference's script has no such step")
         if min_faces < 0 or not 0 <= keep_largest <= hip_ops.KEEP_LARGEST_MAX:
             raise ValueError(f"--min-component-faces must be >= 0 and --keep-largest in [0, {hip_ops.KEEP_LARGEST_MAX}]")
+    target_mesh = getattr(args, "target_mesh", None)
+    if target_mesh:
+        if getattr(args, "route", "kernel") == "script":
+            raise ValueError("--target-mesh has no --route script: the reference's script has no such step")
+        if int(args.chamfer_samples) < 1:
+            raise ValueError(f"--chamfer-samples must be >= 1, got {args.chamfer_samples}")
     from . import dist as nd
     cache_path = os.path.join(args.save_dir, args.cache_name)
     cached = os.path.exists(cache_path)
@@ -323,6 +356,9 @@ def export_marching_cubes(model, args, cfg, device):
                 torch.save(tuple(t.cpu() for t in unfiltered) + (
                             density.cpu().numpy() if isinstance(density, torch.Tensor) else density,), cache_path)
                 print(f"Cached mesh geometry saved to {cache_path}")
+
+    if target_mesh:                                        # the geometry is final here: judge it before any ray is spent
+        chamfer_to_target(vertices, triangles, args, device)
 
     # Appearance: one query per vertex.  Vertices are independent, so under torch.distributed every rank queries a
     # contiguous range of them and one ragged all-gather assembles the (V,3) colours; rank 0 writes the file.
@@ -409,6 +445,11 @@ def build_parser():
     p.add_argument("--keep-largest", type=_non_negative, default=0,
                    help="(addition) of the components left, keep only this many with the most triangles, ties going to the one "
                         "that holds the smaller vertex index (0 = off)")
+    p.add_argument("--target-mesh", type=str, default=None,
+                   help="(addition) an OBJ file: print the chamfer distance between the extracted mesh and it (sampled and searched "
+                        "on the GPU, world coordinates) and write <save-dir>/<mesh-name stem>.chamfer.json")
+    p.add_argument("--chamfer-samples", type=int, default=100000, help="(addition) points sampled on each mesh for --target-mesh")
+    p.add_argument("--chamfer-seed", type=int, default=0, help="(addition) seed of the device generator the samples are drawn from")
     p.add_argument("--gather", choices=("triangles", "grid"), default="triangles",
                    help="(addition, multi-GPU) what travels between the ranks: the emitted triangles of per-slab marching "
                         "cubes (default) or the density grid")

@@ -145,3 +145,47 @@ def export_obj(vertices, triangles, diffuse, normals, filename):
     _lib.check(_lib.load().nm_export_obj(ptr(v), len(v), ptr(c), len(c), ptr(n), len(n), ptr(t), len(t),
                                          os.fsencode(filename)), "nm_export_obj")
     print(f"Finished writing to {filename} with {len(v)} vertices")
+
+
+def load_obj(path):
+    """Wavefront OBJ -> (verts (V,3) f32, faces (F,3) i32, 0-based) as host tensors: the reader `export_obj` lacked (the
+    reference's loader for `<basedir>/model.obj` is commented out, datasets.py:88-103).  `v x y z [r g b]` lines give the
+    vertices (colour columns are dropped); `f` lines take `i`, `i/t`, `i//n` and `i/t/n` entries, negative indices count back
+    from the vertices read so far, polygons are fan-triangulated (a, b, c, d -> abc, acd).  Every other line is ignored.
+    ValueError with the line number for a face index out of range or a line that cannot be read."""
+    verts, faces, forward = [], [], []
+    with open(path, "r", errors="replace") as fh:
+        for lineno, line in enumerate(fh, 1):
+            if line.startswith("v ") or line.startswith("v\t"):
+                parts = line.split()
+                try:
+                    verts.append((float(parts[1]), float(parts[2]), float(parts[3])))
+                except (IndexError, ValueError):
+                    raise ValueError(f"{path}:{lineno}: a vertex needs three numbers: {line.strip()!r}") from None
+            elif line.startswith("f ") or line.startswith("f\t"):
+                nv, corners = len(verts), []
+                for entry in line.split()[1:]:
+                    try:
+                        i = int(entry.split("/", 1)[0])
+                    except ValueError:
+                        raise ValueError(f"{path}:{lineno}: cannot read the face entry {entry!r}") from None
+                    if i > 0:                              # absolute: may name a vertex that a later line defines
+                        i -= 1
+                        if i >= nv:
+                            forward.append((lineno, i))
+                    else:                                  # relative to the vertices read so far; 0 is no index
+                        i = nv + i if i < 0 else -1
+                        if i < 0:
+                            raise ValueError(f"{path}:{lineno}: face index {entry.split('/', 1)[0]} is out of range "
+                                             f"({nv} vertices so far)")
+                    corners.append(i)
+                if len(corners) < 3:
+                    raise ValueError(f"{path}:{lineno}: a face needs at least three vertices: {line.strip()!r}")
+                for k in range(1, len(corners) - 1):
+                    faces.append((corners[0], corners[k], corners[k + 1]))
+    for lineno, i in forward:
+        if i >= len(verts):
+            raise ValueError(f"{path}:{lineno}: face index {i + 1} is out of range ({len(verts)} vertices)")
+    v = np.asarray(verts, dtype=np.float64).astype(np.float32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).astype(np.int32).reshape(-1, 3)
+    return torch.from_numpy(v), torch.from_numpy(f)
