@@ -48,6 +48,8 @@ extern "C" {
  * Additions only. */
 /* 6, later: + nm_surface_filter (+ _workspace_bytes), nm_surface_gather, nm_export_ply (mesh_surface_ray: the ray-marched
  * surface point cloud).  Additions only. */
+/* 6, later: + nm_mesh_simplify_cluster (+ _workspace_bytes), nm_mesh_simplify_emit: mesh simplification by vertex clustering
+ * (mesh_nerf --simplify-cell).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -743,6 +745,62 @@ int nm_mesh_sample_points(const float* d_u, int64_t num_points, const float* d_v
 int64_t nm_points_nearest_workspace_bytes(int64_t num_x, int64_t num_y);
 int nm_points_nearest(const float* d_x, int64_t num_x, const float* d_y, int64_t num_y, float* d_dist2, int32_t* d_index,
                       void* d_workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Mesh simplification by vertex clustering (mesh_nerf --simplify-cell; DESIGN.md, "Mesh simplification").  All arrays on
+ * the device: d_verts (V,3) fp32, d_faces (F,3) int32, d_normals (V,3) fp32 or NULL.  The grid is (origin, cell): cell is
+ * finite and > 0, the origin finite.  Every fp32 / fp64 operation below is rounded on its own (no fused multiply-add), sqrt
+ * and division correctly rounded, so a numpy restatement (tests/mesh_simplify.py) reproduces every output bit for bit; all
+ * sums are exact integer sums, so the outputs do not depend on the order the workgroups ran in.
+ *
+ *   cell      c = floorf((x - origin) / cell) per axis.  A vertex with a non-finite coordinate or a c outside [0, 2^21) is BAD:
+ *             counted, in no cluster.  A face with an index outside [0, V) (never dereferenced) or with a bad vertex is BAD:
+ *             counted, left out.  A caller should treat either count as an error (hip_ops.mesh_simplify raises).
+ *   cluster   all vertices of one cell; its REPRESENTATIVE is its smallest vertex index.
+ *   position  one member: that member's row, bit for bit (position and normal).  More: with lo = origin + c * cell,
+ *             t = (x - lo) / cell, q = (int64) rint((double) t * 2^30) clamped to [-2^31, 2^31] (t lies in [0, 1] up to
+ *             rounding; the clamp makes the bound hold for every input), S = the int64 sum of q over the n members (fewer
+ *             than 2^31 of them, so |S| < 2^62: exact):  p = (float)((double) lo + (double) cell * ((double) S / ((double) n * 2^30))).
+ *   normal    q = (int64) rint((double) component * 2^30) of the members whose three components are finite and at most 2 in
+ *             magnitude (|q| <= 2^31, the same bound); any other member contributes nothing.  With s = (float) S per
+ *             component: normal = s / sqrt((sx sx + sy sy) + sz sz) in fp32, or the representative's own normal when S is
+ *             the zero vector.
+ *   faces     every corner is replaced by its cluster.  A face with two equal corners is DEGENERATE and goes.  Two of the
+ *             others are DUPLICATES when they have the same corners in the same cyclic order (compare with the smallest
+ *             corner rotated to the front); opposite windings are not duplicates.  Of duplicates the smallest face index
+ *             stays.  Kept faces stay in input order, corners in their own order.
+ *   vertices  a cluster no kept face references goes; the others are numbered by ascending representative (numpy:
+ *             new = cumsum(used) - 1 over the representatives' indices).
+ *
+ * nm_mesh_simplify_cluster: clusters, filters and scans; returns on the HOST (the one synchronisation of the stream)
+ *   h_counts[NM_MESH_SIMPLIFY_COUNTS]: clusters, vertices kept, faces kept, degenerate faces, duplicate faces, bad vertices,
+ *   bad faces (the NM_MESH_SIMPLIFY_* indices below).  flags: 0, or NM_MESH_SIMPLIFY_AGGREGATE to sum the lanes of a wave
+ *   that share a cluster in registers before the atomics (the same results; another speed).
+ * nm_mesh_simplify_emit: with that workspace and THE SAME mesh and grid, writes d_out_verts (vertices_kept,3), d_out_faces
+ *   (faces_kept,3) and d_out_normals (vertices_kept,3; NULL when d_normals is NULL).  vertices_kept / faces_kept are the
+ *   cluster call's and bound every write.  No host synchronisation.
+ * V and F are in [0, 2^31 - 64).  The workspace (nm_mesh_simplify_workspace_bytes, 0 for sizes out of range; 256-byte
+ * aligned; 64 bytes per slot of a table of the smallest power of two >= 2 V slots, 4 per slot of one of >= 2 F) must stay
+ * untouched between the two calls.  Argument errors -- a null array with a non-zero size, a cell that is not finite or
+ * <= 0, a non-finite origin -- return 2 before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_MESH_SIMPLIFY_AGGREGATE 1
+#define NM_MESH_SIMPLIFY_CLUSTERS 0
+#define NM_MESH_SIMPLIFY_VERTICES_KEPT 1
+#define NM_MESH_SIMPLIFY_FACES_KEPT 2
+#define NM_MESH_SIMPLIFY_DEGENERATE 3
+#define NM_MESH_SIMPLIFY_DUPLICATE 4
+#define NM_MESH_SIMPLIFY_BAD_VERTICES 5
+#define NM_MESH_SIMPLIFY_BAD_FACES 6
+#define NM_MESH_SIMPLIFY_COUNTS 7
+int64_t nm_mesh_simplify_workspace_bytes(int64_t num_vertices, int64_t num_faces);
+int nm_mesh_simplify_cluster(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
+                             const float* d_normals, float origin_x, float origin_y, float origin_z, float cell, int32_t flags,
+                             void* d_workspace, int64_t* h_counts, void* stream);
+int nm_mesh_simplify_emit(const void* d_workspace, const float* d_verts, int64_t num_vertices, const int32_t* d_faces,
+                          int64_t num_faces, const float* d_normals, float origin_x, float origin_y, float origin_z, float cell,
+                          int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
+                          float* d_out_normals, void* stream);
 
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex

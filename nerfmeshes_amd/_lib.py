@@ -202,6 +202,11 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p]),
     "nm_points_nearest_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "nm_points_nearest": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_simplify_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "nm_mesh_simplify_cluster": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float, C.c_float, C.c_float,
+                                           C.c_float, C.c_int32, c_void_p, C.POINTER(C.c_int64), c_void_p]),
+    "nm_mesh_simplify_emit": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 

@@ -742,6 +742,66 @@ def mesh_filter_components(verts, faces, normals, values=None, keys=None, min_fa
     return out_verts, out_faces, out_normals, out_values, out_keys, info
 
 
+SIMPLIFY_CELLS = 1 << 21                 # cells per axis of the clustering grid (nm_mesh_simplify_cluster)
+SIMPLIFY_AGGREGATE = False               # wave aggregation of equal clusters before the atomics: the same bytes, another speed
+                                         # (tests/tools/time_mesh_simplify.py measures both)
+
+
+def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=None):
+    """Vertex clustering on the device (nm_mesh_simplify_cluster + _emit; semantics in include/nerfmeshes_hip.h): the vertices in
+    one cell of the grid (origin, cell) become one vertex -- the exact mean of its members, a single member unchanged bit for bit
+    --, degenerate and duplicate faces go (opposite windings are not duplicates), and so do the clusters no face is left on.
+    verts (V,3) f32, faces (F,3) i32, normals (V,3) f32 or None, all on the GPU; cell: the cell edge (> 0, finite); origin: three
+    floats, None = the per-axis minimum of the vertices.  -> (verts, faces, normals, info): kept faces in input order, vertices
+    by ascending smallest member index, normals None where None came in; info = dict(vertices, faces, clusters, vertices_kept,
+    faces_kept, degenerate_faces, duplicate_faces).  Nothing left gives empty (0,3) arrays.  Raises ValueError for a vertex with
+    a non-finite coordinate or beyond 2^21 cells from the origin and for a face index out of range (the one read-back)."""
+    lib = _lib.load()
+    if cell is None:
+        raise ValueError("mesh_simplify: the cell size is required")
+    cell = float(np.float32(cell))
+    if not (np.isfinite(cell) and cell > 0):
+        raise ValueError(f"mesh_simplify: the cell size must be finite and > 0, got {cell}")
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = _dev32(verts, dev, "verts")
+    normals = _dev32(normals, dev, "normals") if normals is not None else None
+    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)):
+        raise ValueError("mesh_simplify: the per-vertex arrays disagree on the vertex count")
+    if origin is None:
+        # the minimum of the finite coordinates: a NaN or infinite vertex is reported below with its count, not as a bad origin
+        low = torch.where(torch.isfinite(verts), verts, torch.full_like(verts, float("inf"))).min(dim=0).values if nv else None
+        origin = [x if np.isfinite(x) else 0.0 for x in low.tolist()] if nv else (0.0, 0.0, 0.0)
+    origin = [float(np.float32(x)) for x in (origin.tolist() if isinstance(origin, (torch.Tensor, np.ndarray)) else origin)]
+    if len(origin) != 3 or not all(np.isfinite(x) for x in origin):
+        raise ValueError(f"mesh_simplify: the origin must be three finite numbers, got {origin}")
+    nbytes = int(lib.nm_mesh_simplify_workspace_bytes(nv, nf))
+    if nbytes == 0:
+        raise ValueError(f"mesh simplify: {nv} vertices / {nf} faces are beyond the supported sizes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = (C.c_int64 * 7)()
+    flags = 1 if (SIMPLIFY_AGGREGATE if aggregate is None else aggregate) else 0
+    rc = lib.nm_mesh_simplify_cluster(_ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin, cell, flags, _ptr(ws), counts,
+                                      _stream())
+    if rc == 2:
+        raise ValueError((lib.nm_last_error() or b"nm_mesh_simplify_cluster: bad argument").decode())
+    check(rc, "nm_mesh_simplify_cluster")
+    clusters, kv, kf, degenerate, duplicate, bad_v, bad_f = (int(x) for x in counts)
+    if bad_v:
+        raise ValueError(f"mesh simplify: {bad_v} vertices have a non-finite coordinate or a cell index outside [0, {SIMPLIFY_CELLS})")
+    if bad_f:
+        raise ValueError(f"mesh simplify: {bad_f} faces have a vertex index outside [0, {nv})")
+    out_verts = torch.empty(kv, 3, dtype=torch.float32, device=dev)
+    out_faces = torch.empty(kf, 3, dtype=torch.int32, device=dev)
+    out_normals = torch.empty(kv, 3, dtype=torch.float32, device=dev) if normals is not None else None
+    if kv:
+        check(lib.nm_mesh_simplify_emit(_ptr(ws), _ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin, cell, kv, kf,
+                                        _ptr(out_verts), _ptr(out_faces), _ptr(out_normals), _stream()), "nm_mesh_simplify_emit")
+    info = dict(vertices=nv, faces=nf, clusters=clusters, vertices_kept=kv, faces_kept=kf, degenerate_faces=degenerate,
+                duplicate_faces=duplicate)
+    return out_verts, out_faces, out_normals, info
+
+
 def _mesh_arrays(verts, faces, what):
     """(V,3) fp32 vertices and (F,3) int32 faces of one mesh on the GPU (host arrays are copied over), checked."""
     verts = _dev32(verts if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.as_tensor(verts).cuda(), name="verts")

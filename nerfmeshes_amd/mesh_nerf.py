@@ -290,6 +290,22 @@ def filter_components(vertices, triangles, normals, min_faces, keep_largest):
     return vertices, triangles, normals
 
 
+def simplify_mesh(vertices, triangles, normals, cell_voxels, args):
+    """`--simplify-cell K` on the device (hip_ops.mesh_simplify): vertex clustering on a grid of K-voxel cells, K * (2 * limit /
+    res) world units, anchored at (-limit,)*3 -- the vertices of one cell become their exact mean (one alone stays bit for bit),
+    degenerate and duplicate triangles go, kept ones stay in their order.  ValueError when no triangle is left."""
+    cell = float(cell_voxels) * (2.0 * args.limit / args.res)
+    v0, f0 = vertices.shape[0], triangles.shape[0]
+    vertices, triangles, normals, info = hip_ops.mesh_simplify(vertices, triangles.to(torch.int32), normals, cell=cell,
+                                                               origin=(-args.limit,) * 3)
+    if info["faces_kept"] == 0:
+        raise ValueError(f"--simplify-cell {cell_voxels:g} leaves no triangle of {f0}: every one has two corners in one cell "
+                         f"({info['clusters']} clusters of {v0} vertices)")
+    print(f"Simplify: cell {cell_voxels:g} voxels: {v0} -> {info['vertices_kept']} vertices, {f0} -> {info['faces_kept']} faces "
+          f"({info['degenerate_faces']} degenerate, {info['duplicate_faces']} duplicate)")
+    return vertices, triangles, normals
+
+
 def chamfer_to_target(vertices, triangles, args, device):
     """`--target-mesh PATH`: the chamfer distance between the extracted mesh and an OBJ file, both in world coordinates
     (mesh_chamfer.compare_meshes with --chamfer-samples / --chamfer-seed), printed; rank 0 writes
@@ -316,7 +332,10 @@ def export_marching_cubes(model, args, cfg, device):
     normals by the network's (network_normals) before the appearance query and the OBJ; the cache keeps the grid normals.
     `--min-component-faces` / `--keep-largest` drop whole connected components (filter_components) right after the geometry stage
     or the cache load -- before the network normals and the appearance query, so no ray is spent on a dropped vertex; the cache
-    keeps the unfiltered geometry.  Under torch.distributed every rank filters the gathered mesh redundantly."""
+    keeps the unfiltered geometry.  Under torch.distributed every rank filters the gathered mesh redundantly.
+    `--simplify-cell K` clusters the vertices (simplify_mesh) after that filter -- its thresholds count original triangles -- and
+    before `--target-mesh`, the network normals and the appearance query, which all see the final geometry; the cache keeps the
+    unsimplified mesh, and every rank simplifies redundantly."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
     normals_mode = getattr(args, "normals", "grid")
     if normals_mode == "network" and getattr(args, "route", "kernel") == "script":
@@ -327,6 +346,12 @@ def export_marching_cubes(model, args, cfg, device):
             raise ValueError("--min-component-faces / --keep-largest have no --route script: the reference's script has no such step")
         if min_faces < 0 or not 0 <= keep_largest <= hip_ops.KEEP_LARGEST_MAX:
             raise ValueError(f"--min-component-faces must be >= 0 and --keep-largest in [0, {hip_ops.KEEP_LARGEST_MAX}]")
+    simplify_cell = float(getattr(args, "simplify_cell", 0.0))
+    if simplify_cell:
+        if getattr(args, "route", "kernel") == "script":
+            raise ValueError("--simplify-cell has no --route script: the reference's script has no such step")
+        if not 0.0 < simplify_cell < float("inf"):
+            raise ValueError(f"--simplify-cell must be finite and >= 0, got {simplify_cell}")
     target_mesh = getattr(args, "target_mesh", None)
     if target_mesh:
         if getattr(args, "route", "kernel") == "script":
@@ -343,12 +368,16 @@ def export_marching_cubes(model, args, cfg, device):
         vertices, triangles, normals = (torch.as_tensor(t).to(device) for t in (vertices, triangles, normals))
         if min_faces or keep_largest:
             vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
+        if simplify_cell:
+            vertices, triangles, normals = simplify_mesh(vertices, triangles, normals, simplify_cell, args)
     else:
         print("Generating mesh geometry...")
         vertices, triangles, normals, density = geometry(model, device, args)
         unfiltered = vertices, triangles, normals          # what the cache keeps, so that the filter can be tuned on it
         if min_faces or keep_largest:                      # first: a filter that leaves nothing raises before anything is written
             vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
+        if simplify_cell:                                  # likewise: no triangle left raises here
+            vertices, triangles, normals = simplify_mesh(vertices, triangles, normals, simplify_cell, args)
         if cache_new or args.override_cache_mesh:
             if nd.world()[1] > 1 and getattr(args, "gather", "triangles") == "triangles":
                 density = _assemble_grid_from_slabs(density, _nums(args.res), device)   # the cache holds the whole grid
@@ -412,6 +441,13 @@ def _non_negative(text):
     return n
 
 
+def _cell_size(text):
+    k = float(text)
+    if not 0.0 <= k < float("inf"):                        # a NaN fails both comparisons
+        raise argparse.ArgumentTypeError(f"must be finite and >= 0, got {text}")
+    return k
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--log-checkpoint", type=str, default=None)
@@ -445,6 +481,10 @@ def build_parser():
     p.add_argument("--keep-largest", type=_non_negative, default=0,
                    help="(addition) of the components left, keep only this many with the most triangles, ties going to the one "
                         "that holds the smaller vertex index (0 = off)")
+    p.add_argument("--simplify-cell", type=_cell_size, default=0.0,
+                   help="(addition) simplify the mesh by vertex clustering: the vertices in one cell of a grid of this many voxels "
+                        "per edge become their mean, degenerate and duplicate triangles go; after the component filter, before "
+                        "the normals and the appearance query (0 = off)")
     p.add_argument("--target-mesh", type=str, default=None,
                    help="(addition) an OBJ file: print the chamfer distance between the extracted mesh and it (sampled and searched "
                         "on the GPU, world coordinates) and write <save-dir>/<mesh-name stem>.chamfer.json")
