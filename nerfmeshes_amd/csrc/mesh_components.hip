@@ -16,11 +16,11 @@
 //                       (count descending, label ascending) as K rounds of a 64-bit max-reduction over the key
 //                       count << 32 | (2^32 - 1 - label): round r takes the largest key below round r-1's.  The keep bits of
 //                       vertices and faces leave each wave as one ballot word.
-//   4. cc_scan / cc_compact_*   popcounts, exclusive prefix sums, scatter: the output order is the input order by construction,
-//                       whatever order the workgroups ran in (no atomic queue) -- the surface_scan / marching-cubes idiom.  A
-//                       kept vertex's new index is the prefix of its word + the popcount of the lower bits, which is numpy's
-//                       cumsum(keep) - 1.
+//   4. cc_scan / cc_compact_*   the ordered compaction of compact.h over both sets of words: the output order is the input
+//                       order, whatever order the workgroups ran in, and a kept vertex's new index is its rank among the set
+//                       bits, which is numpy's cumsum(keep) - 1.
 // The only host round trip is the one that returns the output sizes (nm_mesh_components_select).
+#include "compact.h"
 #include "nm_internal.h"
 
 namespace nm {
@@ -76,18 +76,12 @@ __global__ __launch_bounds__(256) void cc_init(int* __restrict__ parent, int* __
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr->bad_faces = 0;
 }
 
-__device__ __forceinline__ bool cc_face(const int32_t* faces, int64_t f, int nv, int (&v)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = faces[3 * f + k];
-    return (unsigned)v[0] < (unsigned)nv && (unsigned)v[1] < (unsigned)nv && (unsigned)v[2] < (unsigned)nv;
-}
-
 __global__ __launch_bounds__(256) void cc_union_faces(const int32_t* __restrict__ faces, int64_t nf, int nv, int* parent,
                                                       CcHeader* hdr) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < nf; f += stride) {
         int v[3];
-        if (!cc_face(faces, f, nv, v)) {
+        if (!load_face(faces, f, nv, v)) {
             atomicAdd(&hdr->bad_faces, 1ull);
             continue;
         }
@@ -112,7 +106,7 @@ __global__ __launch_bounds__(256) void cc_count(const int32_t* __restrict__ face
     for (int64_t it = 0; it < rounds; ++it) {
         const int64_t f = it * stride + (int64_t)blockIdx.x * 256 + threadIdx.x;
         int v[3];
-        bool todo = f < nf && cc_face(faces, f, nv, v);
+        bool todo = f < nf && load_face(faces, f, nv, v);
         const int label = todo ? labels[v[0]] : -1;
         unsigned long long left = __ballot(todo);
         while (left) {                                               // uniform over the wave
@@ -190,49 +184,19 @@ __global__ __launch_bounds__(256) void cc_mask_faces(const int32_t* __restrict__
     const unsigned long long threshold = keep_largest ? best[keep_largest - 1] : 0ull;
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int v[3];
-    const bool keep = f < nf && cc_face(faces, f, nv, v) && cc_keeps(counts, nv, labels[v[0]], min_faces, threshold);
+    const bool keep = f < nf && load_face(faces, f, nv, v) && cc_keeps(counts, nv, labels[v[0]], min_faces, threshold);
     const unsigned long long word = __ballot(keep);
     if ((threadIdx.x & 63) == 0 && (f >> 6) < (nf + 63) / 64) words[f >> 6] = word;
 }
 
-// exclusive prefix sums of the words' popcounts and their total: workgroup 0 the vertex words, workgroup 1 the face words;
-// 1024 threads walk 1024 words at a time with a running carry (surface_scan's scheme)
-__global__ __launch_bounds__(1024) void cc_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
-                                                uint32_t* __restrict__ vprefix, const unsigned long long* __restrict__ fwords,
-                                                int64_t nfw, uint32_t* __restrict__ fprefix, CcHeader* hdr) {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    const unsigned long long* words = blockIdx.x ? fwords : vwords;
-    uint32_t* prefix = blockIdx.x ? fprefix : vprefix;
-    const int64_t nwords = blockIdx.x ? nfw : nvw;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t start = 0; start < nwords; start += 1024) {
-        const int64_t i = start + threadIdx.x;
-        const uint32_t own = i < nwords ? (uint32_t)__popcll(words[i]) : 0u;
-        uint32_t inc = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += up;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < nwords) prefix[i] = before + inc - own;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = s_carry;
-}
-
-// rank of a set bit among the kept: numpy's cumsum(keep) - 1
-__device__ __forceinline__ int64_t cc_rank(const unsigned long long* __restrict__ words, const uint32_t* __restrict__ prefix,
-                                           int64_t i) {
-    return (int64_t)prefix[i >> 6] + __popcll(words[i >> 6] & ((1ull << (i & 63)) - 1ull));
+// workgroup 0 the vertex words, workgroup 1 the face words (compact.h)
+__global__ __launch_bounds__(SCAN_THREADS) void cc_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
+                                                        uint32_t* __restrict__ vprefix,
+                                                        const unsigned long long* __restrict__ fwords, int64_t nfw,
+                                                        uint32_t* __restrict__ fprefix, CcHeader* hdr) {
+    const bool f = blockIdx.x != 0;
+    const uint32_t kept = popcount_prefix_sums(f ? fwords : vwords, f ? nfw : nvw, f ? fprefix : vprefix);
+    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = kept;
 }
 
 struct CcRows {
@@ -244,8 +208,8 @@ __global__ __launch_bounds__(256) void cc_compact_vertices(CcRows a, int nv, int
                                                            const unsigned long long* __restrict__ words,
                                                            const uint32_t* __restrict__ prefix) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv || !((words[v >> 6] >> (v & 63)) & 1ull)) return;
-    const int64_t dst = cc_rank(words, prefix, v);
+    if (v >= nv || !bit_test(words, v)) return;
+    const int64_t dst = bit_rank(words, prefix, v);
     if (dst >= capacity) return;                                     // never past the caller's arrays
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -262,18 +226,13 @@ __global__ __launch_bounds__(256) void cc_compact_faces(const int32_t* __restric
                                                         const unsigned long long* __restrict__ vwords,
                                                         const uint32_t* __restrict__ vprefix, int32_t* __restrict__ out_faces) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || !((fwords[f >> 6] >> (f & 63)) & 1ull)) return;
+    if (f >= nf || !bit_test(fwords, f)) return;
     int v[3];
-    if (!cc_face(faces, f, nv, v)) return;                           // such a face never has its bit set
-    const int64_t dst = cc_rank(fwords, fprefix, f);
+    if (!load_face(faces, f, nv, v)) return;                         // such a face never has its bit set
+    const int64_t dst = bit_rank(fwords, fprefix, f);
     if (dst >= capacity) return;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)cc_rank(vwords, vprefix, v[k]);
-}
-
-static int64_t cc_align(int64_t b) { return (b + 255) / 256 * 256; }
-static bool cc_sizes_ok(int64_t nv, int64_t nf) {
-    return nv >= 0 && nf >= 0 && nv < (int64_t(1) << 31) - 64 && nf < (int64_t(1) << 31) - 64;
+    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)bit_rank(vwords, vprefix, v[k]);
 }
 
 struct CcWorkspace {
@@ -287,27 +246,21 @@ struct CcWorkspace {
     int64_t nvw, nfw, bytes;
 };
 
-static CcWorkspace cc_carve(void* ws, int64_t nv, int64_t nf) {
-    char* base = static_cast<char*>(ws);
+static CcWorkspace cc_carve(const void* ws, int64_t nv, int64_t nf) {
+    Carver c(ws, 256);
     CcWorkspace w;
     w.nvw = (nv + 63) / 64;
     w.nfw = (nf + 63) / 64;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char* p = base + off; off += cc_align(bytes); return p; };
-    w.hdr = reinterpret_cast<CcHeader*>(take(sizeof(CcHeader)));
-    w.parent = reinterpret_cast<int*>(take(nv * 4));
-    w.best = reinterpret_cast<unsigned long long*>(take((CC_KMAX + 1) * 8));
-    w.vwords = reinterpret_cast<unsigned long long*>(take(w.nvw * 8));
-    w.vprefix = reinterpret_cast<uint32_t*>(take(w.nvw * 4));
-    w.fwords = reinterpret_cast<unsigned long long*>(take(w.nfw * 8));
-    w.fprefix = reinterpret_cast<uint32_t*>(take(w.nfw * 4));
-    w.bytes = off;
+    w.hdr = c.take<CcHeader>(1);
+    w.parent = c.take<int>(nv);
+    w.best = c.take<unsigned long long>(CC_KMAX + 1);
+    w.vwords = c.take<unsigned long long>(w.nvw);
+    w.vprefix = c.take<uint32_t>(w.nvw);
+    w.fwords = c.take<unsigned long long>(w.nfw);
+    w.fprefix = c.take<uint32_t>(w.nfw);
+    w.bytes = c.offset;
     return w;
 }
-
-// one thread per element up to 2048 workgroups, a grid-stride loop beyond
-static unsigned cc_grid(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : g > 2048 ? 2048 : g); }
-static unsigned cc_grid_flat(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : g); }
 
 }  // namespace nm
 
@@ -316,30 +269,32 @@ using namespace nm;
 extern "C" {
 
 int64_t nm_mesh_components_workspace_bytes(int64_t num_vertices, int64_t num_faces) {
-    if (!cc_sizes_ok(num_vertices, num_faces)) return 0;
+    if (!mesh_size_ok(num_vertices) || !mesh_size_ok(num_faces)) return 0;
     return cc_carve(nullptr, num_vertices, num_faces).bytes;
 }
 
 int nm_mesh_components(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t* d_labels,
                        int32_t* d_face_counts, void* d_workspace, void* stream) {
-    NM_REQUIRE(cc_sizes_ok(num_vertices, num_faces), "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
+    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
+               "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
     NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh components: faces without vertices");
     NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces) && (num_vertices == 0 || (d_labels && d_face_counts)), "bad argument");
     const CcWorkspace w = cc_carve(d_workspace, num_vertices, num_faces);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
-    hipLaunchKernelGGL(cc_init, dim3(cc_grid(num_vertices)), dim3(256), 0, s, w.parent, d_face_counts, nv, w.hdr);
+    const unsigned vgrid = launch_grid(num_vertices, GRID_CAP), fgrid = launch_grid(num_faces, GRID_CAP);
+    hipLaunchKernelGGL(cc_init, dim3(vgrid), dim3(256), 0, s, w.parent, d_face_counts, nv, w.hdr);
     NM_HIP_CHECK(hipGetLastError());
     if (num_faces) {
-        hipLaunchKernelGGL(cc_union_faces, dim3(cc_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, w.parent, w.hdr);
+        hipLaunchKernelGGL(cc_union_faces, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.parent, w.hdr);
         NM_HIP_CHECK(hipGetLastError());
     }
     if (num_vertices) {
-        hipLaunchKernelGGL(cc_flatten, dim3(cc_grid(num_vertices)), dim3(256), 0, s, w.parent, d_labels, nv);
+        hipLaunchKernelGGL(cc_flatten, dim3(vgrid), dim3(256), 0, s, w.parent, d_labels, nv);
         NM_HIP_CHECK(hipGetLastError());
     }
     if (num_faces) {
-        hipLaunchKernelGGL(cc_count, dim3(cc_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, d_labels, d_face_counts);
+        hipLaunchKernelGGL(cc_count, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, d_labels, d_face_counts);
         NM_HIP_CHECK(hipGetLastError());
     }
     return 0;
@@ -349,7 +304,8 @@ int nm_mesh_components_select(const int32_t* d_faces, int64_t num_faces, int64_t
                               const int32_t* d_face_counts, int64_t min_faces, int32_t keep_largest, void* d_workspace,
                               int64_t* h_vertices_kept, int64_t* h_faces_kept, int64_t* h_components,
                               int64_t* h_components_kept, void* stream) {
-    NM_REQUIRE(cc_sizes_ok(num_vertices, num_faces), "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
+    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
+               "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
     NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh components: faces without vertices");
     NM_REQUIRE(min_faces >= 0, "mesh components: min_faces must be >= 0");
     NM_REQUIRE(keep_largest >= 0 && keep_largest <= CC_KMAX, "mesh components: keep_largest must be in [0, 1024]");
@@ -360,17 +316,17 @@ int nm_mesh_components_select(const int32_t* d_faces, int64_t num_faces, int64_t
     const int nv = (int)num_vertices;
     hipLaunchKernelGGL(cc_select_init, dim3(1), dim3(256), 0, s, w.best, w.hdr);
     for (int r = 0; r < keep_largest && nv; ++r)
-        hipLaunchKernelGGL(cc_round, dim3(cc_grid(num_vertices)), dim3(256), 0, s, d_labels, d_face_counts, nv, (long long)min_faces, r,
-                           w.best);
+        hipLaunchKernelGGL(cc_round, dim3(launch_grid(num_vertices, GRID_CAP)), dim3(256), 0, s, d_labels, d_face_counts, nv,
+                           (long long)min_faces, r, w.best);
     NM_HIP_CHECK(hipGetLastError());
     if (nv)
-        hipLaunchKernelGGL(cc_mask_vertices, dim3(cc_grid_flat(num_vertices)), dim3(256), 0, s, d_labels, d_face_counts, nv,
+        hipLaunchKernelGGL(cc_mask_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_labels, d_face_counts, nv,
                            (long long)min_faces, (int)keep_largest, w.best, w.vwords, w.hdr);
     if (num_faces)
-        hipLaunchKernelGGL(cc_mask_faces, dim3(cc_grid_flat(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, d_labels,
+        hipLaunchKernelGGL(cc_mask_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, d_labels,
                            d_face_counts, (long long)min_faces, (int)keep_largest, w.best, w.fwords);
     NM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(cc_scan, dim3(2), dim3(1024), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
+    hipLaunchKernelGGL(cc_scan, dim3(2), dim3(SCAN_THREADS), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
     NM_HIP_CHECK(hipGetLastError());
     CcHeader h;
     NM_HIP_CHECK(hipMemcpyAsync(&h, w.hdr, sizeof(CcHeader), hipMemcpyDeviceToHost, s));
@@ -390,7 +346,8 @@ int nm_mesh_components_compact(const void* d_workspace, const int32_t* d_faces, 
                                const float* d_verts, const float* d_normals, const float* d_values, const int64_t* d_keys,
                                int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
                                float* d_out_normals, float* d_out_values, int64_t* d_out_keys, void* stream) {
-    NM_REQUIRE(cc_sizes_ok(num_vertices, num_faces), "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
+    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
+               "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
     NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh components: faces without vertices");
     NM_REQUIRE(vertices_kept >= 0 && vertices_kept <= num_vertices && faces_kept >= 0 && faces_kept <= num_faces,
                "mesh components: the kept counts must lie within the mesh's");
@@ -398,18 +355,18 @@ int nm_mesh_components_compact(const void* d_workspace, const int32_t* d_faces, 
     NM_REQUIRE(vertices_kept == 0 || ((!d_verts || d_out_verts) && (!d_normals || d_out_normals) && (!d_values || d_out_values) &&
                                       (!d_keys || d_out_keys)), "mesh components: an input array without its output");
     NM_REQUIRE(faces_kept == 0 || d_out_faces, "mesh components: null face output");
-    const CcWorkspace w = cc_carve(const_cast<void*>(d_workspace), num_vertices, num_faces);
+    const CcWorkspace w = cc_carve(d_workspace, num_vertices, num_faces);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
     if (vertices_kept && (d_verts || d_normals || d_values || d_keys)) {
         const CcRows rows{d_verts, d_normals, d_values, reinterpret_cast<const long long*>(d_keys),
                           d_out_verts, d_out_normals, d_out_values, reinterpret_cast<long long*>(d_out_keys)};
-        hipLaunchKernelGGL(cc_compact_vertices, dim3(cc_grid_flat(num_vertices)), dim3(256), 0, s, rows, nv, vertices_kept, w.vwords,
+        hipLaunchKernelGGL(cc_compact_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, rows, nv, vertices_kept, w.vwords,
                            w.vprefix);
         NM_HIP_CHECK(hipGetLastError());
     }
     if (faces_kept) {
-        hipLaunchKernelGGL(cc_compact_faces, dim3(cc_grid_flat(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, faces_kept,
+        hipLaunchKernelGGL(cc_compact_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, faces_kept,
                            w.fwords, w.fprefix, w.vwords, w.vprefix, d_out_faces);
         NM_HIP_CHECK(hipGetLastError());
     }

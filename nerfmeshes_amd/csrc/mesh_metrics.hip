@@ -5,8 +5,7 @@
 //                       of a face is 0.5 * |e1 x e2|; the largest area m = f * 2^e (f in [0.5, 1)) is an exact reduction
 //                       (non-negative float bits compare as unsigned integers: one atomicMax); the weight of face i is
 //                       trunc(area_i * 2^(32-e)), a power-of-two scaling, exact in fp64.  Their inclusive prefix sums (uint64,
-//                       one workgroup walking 1024 entries at a time with a running carry -- cc_scan's scheme) are exact and
-//                       independent of the order anything ran in.
+//                       the one-workgroup scan of compact.h) are exact and independent of the order anything ran in.
 //   2. mm_sample        one thread per draw (u0, u1, u2): t = trunc(u0 * total), face = first i with cdf[i] > t by binary
 //                       search (a zero-weight face can never be chosen), pytorch3d's barycentric weights from (u1, u2).
 //   3. mm_nearest       the hot kernel: for every query row of x the smallest squared distance to a row of y and the smallest
@@ -25,6 +24,7 @@
 // Nothing here allocates or synchronises; the wrappers read the 32-byte header of nm_mesh_face_weights once.
 #include <math.h>
 
+#include "compact.h"
 #include "nm_internal.h"
 
 namespace nm {
@@ -35,12 +35,6 @@ struct MmHeader {                      // the first 32 bytes of nm_mesh_face_wei
     unsigned int max_bits;             // float bits of the largest area
     unsigned int pad[3];
 };
-
-__device__ __forceinline__ bool mm_face(const int32_t* __restrict__ faces, int64_t f, int nv, int (&v)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) v[k] = faces[3 * f + k];
-    return (unsigned)v[0] < (unsigned)nv && (unsigned)v[1] < (unsigned)nv && (unsigned)v[2] < (unsigned)nv;
-}
 
 // c = e1 x e2 with e1 = v1 - v0, e2 = v2 - v0; returns |c| = sqrt((cx cx + cy cy) + cz cz)
 __device__ __forceinline__ float mm_cross(const float* __restrict__ verts, const int (&v)[3], float (&p)[3][3], float (&c)[3]) {
@@ -60,7 +54,7 @@ __device__ __forceinline__ float mm_cross(const float* __restrict__ verts, const
 __device__ __forceinline__ float mm_area(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t f, int nv,
                                          bool& bad) {
     int v[3];
-    bad = !mm_face(faces, f, nv, v);
+    bad = !load_face(faces, f, nv, v);
     if (bad) return 0.0f;
     float p[3][3], c[3];
     const float area = 0.5f * mm_cross(verts, v, p, c);
@@ -108,31 +102,16 @@ __global__ __launch_bounds__(256) void mm_face_weights(const float* __restrict__
     }
 }
 
-// in-place inclusive prefix sums, one workgroup
-__global__ __launch_bounds__(1024) void mm_scan(unsigned long long* __restrict__ cdf, int64_t n, MmHeader* hdr) {
-    __shared__ unsigned long long s_wave[16];
-    __shared__ unsigned long long s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0ull;
-    __syncthreads();
-    for (int64_t start = 0; start < n; start += 1024) {
+// in-place inclusive prefix sums: compact.h's scan on the 64-bit weights themselves, one workgroup
+__global__ __launch_bounds__(SCAN_THREADS) void mm_scan(unsigned long long* __restrict__ cdf, int64_t n, MmHeader* hdr) {
+    __shared__ alignas(16) ScanLds<unsigned long long> lds;
+    scan_reset(lds);
+    for (int64_t start = 0; start < n; start += SCAN_THREADS) {
         const int64_t i = start + threadIdx.x;
-        unsigned long long inc = i < n ? cdf[i] : 0ull;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned long long up = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += up;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        unsigned long long before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < n) cdf[i] = before + inc;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + inc;
-        __syncthreads();
+        const unsigned long long inclusive = scan_step(i < n ? cdf[i] : 0ull, lds);
+        if (i < n) cdf[i] = inclusive;
     }
-    if (threadIdx.x == 0) hdr->total = s_carry;
+    if (threadIdx.x == 0) hdr->total = lds.carry;
 }
 
 __global__ __launch_bounds__(256) void mm_sample(const float* __restrict__ u, int64_t n, const float* __restrict__ verts, int nv,
@@ -155,7 +134,7 @@ __global__ __launch_bounds__(256) void mm_sample(const float* __restrict__ u, in
         if (!points && !normals) continue;
         int v[3];
         float p[3][3], c[3];
-        const bool ok = mm_face(faces, lo, nv, v);                   // false only for a cdf that is not this mesh's
+        const bool ok = load_face(faces, lo, nv, v);                   // false only for a cdf that is not this mesh's
         const float len = ok ? mm_cross(verts, v, p, c) : 0.0f;
         const float s = sqrtf(u1);
         const float w0 = 1.0f - s, w1 = s * (1.0f - u2), w2 = s * u2;
@@ -291,9 +270,6 @@ __global__ __launch_bounds__(NN_THREADS) void mm_nearest(const float* __restrict
     }
 }
 
-static bool mm_size_ok(int64_t n) { return n >= 0 && n < (int64_t(1) << 31) - 64; }
-static unsigned mm_grid(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : g > 2048 ? 2048 : g); }
-
 // rows of y per blockIdx.y: all of them unless the queries alone leave the device idle
 static int64_t nn_chunk(int64_t n, int64_t m) {
     const int64_t bx = (n + NN_BLOCK_Q - 1) / NN_BLOCK_Q;
@@ -316,7 +292,8 @@ int64_t nm_mesh_face_weights_workspace_bytes(void) { return 256; }
 
 int nm_mesh_face_weights(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces, float* d_areas,
                          uint64_t* d_cdf, void* d_workspace, void* stream) {
-    NM_REQUIRE(mm_size_ok(num_vertices) && mm_size_ok(num_faces), "mesh face weights: vertex and face counts must be in [0, 2^31 - 64)");
+    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
+               "mesh face weights: vertex and face counts must be in [0, 2^31 - 64)");
     NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh face weights: faces without vertices");
     NM_REQUIRE(d_workspace && (num_faces == 0 || (d_faces && d_verts && d_cdf)), "bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -325,12 +302,13 @@ int nm_mesh_face_weights(const float* d_verts, int64_t num_vertices, const int32
     hipLaunchKernelGGL(mm_header_init, dim3(1), dim3(64), 0, s, hdr);
     NM_HIP_CHECK(hipGetLastError());
     if (num_faces == 0) return 0;
-    hipLaunchKernelGGL(mm_face_areas, dim3(mm_grid(num_faces)), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, d_areas, hdr);
+    const unsigned grid = launch_grid(num_faces, GRID_CAP);
+    hipLaunchKernelGGL(mm_face_areas, dim3(grid), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, d_areas, hdr);
     NM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(mm_face_weights, dim3(mm_grid(num_faces)), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, hdr,
+    hipLaunchKernelGGL(mm_face_weights, dim3(grid), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, hdr,
                        reinterpret_cast<unsigned long long*>(d_cdf));
     NM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(mm_scan, dim3(1), dim3(1024), 0, s, reinterpret_cast<unsigned long long*>(d_cdf), num_faces, hdr);
+    hipLaunchKernelGGL(mm_scan, dim3(1), dim3(SCAN_THREADS), 0, s, reinterpret_cast<unsigned long long*>(d_cdf), num_faces, hdr);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -338,32 +316,32 @@ int nm_mesh_face_weights(const float* d_verts, int64_t num_vertices, const int32
 int nm_mesh_sample_points(const float* d_u, int64_t num_points, const float* d_verts, int64_t num_vertices, const int32_t* d_faces,
                           int64_t num_faces, const uint64_t* d_cdf, float* d_points, int32_t* d_face_ids, float* d_normals,
                           void* stream) {
-    NM_REQUIRE(mm_size_ok(num_vertices) && mm_size_ok(num_faces) && mm_size_ok(num_points),
+    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces) && mesh_size_ok(num_points),
                "mesh sample points: point, vertex and face counts must be in [0, 2^31 - 64)");
     NM_REQUIRE(num_points == 0 || (num_faces > 0 && num_vertices > 0), "mesh sample points: a mesh without faces cannot be sampled");
     NM_REQUIRE(num_points == 0 || (d_u && d_verts && d_faces && d_cdf), "bad argument");
     if (num_points == 0 || (!d_points && !d_face_ids && !d_normals)) return 0;
-    hipLaunchKernelGGL(mm_sample, dim3(mm_grid(num_points)), dim3(256), 0, static_cast<hipStream_t>(stream), d_u, num_points,
-                       d_verts, (int)num_vertices, d_faces, num_faces, reinterpret_cast<const unsigned long long*>(d_cdf), d_points,
-                       d_face_ids, d_normals);
+    hipLaunchKernelGGL(mm_sample, dim3(launch_grid(num_points, GRID_CAP)), dim3(256), 0, static_cast<hipStream_t>(stream), d_u,
+                       num_points, d_verts, (int)num_vertices, d_faces, num_faces, reinterpret_cast<const unsigned long long*>(d_cdf),
+                       d_points, d_face_ids, d_normals);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 int64_t nm_points_nearest_workspace_bytes(int64_t num_x, int64_t num_y) {
-    if (!mm_size_ok(num_x) || !mm_size_ok(num_y)) return 0;
-    return (num_x * 8 + 255) / 256 * 256 + 256;
+    if (!mesh_size_ok(num_x) || !mesh_size_ok(num_y)) return 0;
+    return align_up(num_x * 8, 256) + 256;
 }
 
 int nm_points_nearest(const float* d_x, int64_t num_x, const float* d_y, int64_t num_y, float* d_dist2, int32_t* d_index,
                       void* d_workspace, void* stream) {
-    NM_REQUIRE(mm_size_ok(num_x) && mm_size_ok(num_y), "points nearest: both point counts must be in [0, 2^31 - 64)");
+    NM_REQUIRE(mesh_size_ok(num_x) && mesh_size_ok(num_y), "points nearest: both point counts must be in [0, 2^31 - 64)");
     NM_REQUIRE(num_x == 0 || (d_x && d_dist2 && d_index && d_workspace), "bad argument");
     NM_REQUIRE(num_y == 0 || d_y, "bad argument");
     if (num_x == 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned long long* keys = static_cast<unsigned long long*>(d_workspace);
-    const unsigned flat = (unsigned)((num_x + 255) / 256);
+    const unsigned flat = launch_grid(num_x);
     const int64_t chunk = nn_chunk(num_x, num_y);
     const bool split = num_y == 0 || chunk < num_y;                  // no rows of y: the empty keys are the answer
     if (split) {

@@ -34,14 +34,15 @@
 //                       no key to store and no bound on V.  Same rules: agent-scope atomics only, bounded walks, no waiting.
 //   4. ms_mark          a face stays when it is the index its slot ended with: of duplicates the smallest.  Keep bits leave
 //                       each wave as one ballot word; the representatives of kept faces' corners get their bit by atomicOr.
-//   5. ms_scan / ms_emit_*   popcounts, exclusive prefix sums, scatter (the cc_scan / cc_compact_* idiom, local copies so that
-//                       mesh_components.hip stays as it is): kept faces in input order with their corners in their own order;
-//                       kept clusters by ascending representative (numpy: new = cumsum(used) - 1), which is marching cubes'
-//                       scan order.  A cluster of ONE member emits that member's rows bit for bit; a larger one
+//   5. ms_scan / ms_emit_*   the ordered compaction of compact.h over both sets of words: kept faces in input order with
+//                       their corners in their own order; kept clusters by ascending representative (numpy: new =
+//                       cumsum(used) - 1), which is marching cubes' scan order.  A cluster of ONE member emits that member's
+//                       rows bit for bit; a larger one
 //                         p = (float)((double) lo + (double) cell * ((double) S / ((double) n * 2^30)))
 //                         normal = s / sqrt((sx sx + sy sy) + sz sz) with s = (float) S per component, or the representative's
 //                                  own normal when S is the zero vector
 // The only host round trip is the one that returns the counts (nm_mesh_simplify_cluster).
+#include "compact.h"
 #include "nm_internal.h"
 
 namespace nm {
@@ -303,47 +304,14 @@ __global__ __launch_bounds__(256) void ms_mark(const int32_t* __restrict__ faces
     }
 }
 
-// cc_scan's scheme (mesh_components.hip): workgroup 0 the vertex words, workgroup 1 the face words
-__global__ __launch_bounds__(1024) void ms_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
-                                                uint32_t* __restrict__ vprefix, const unsigned long long* __restrict__ fwords,
-                                                int64_t nfw, uint32_t* __restrict__ fprefix, MsHeader* hdr) {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    const unsigned long long* words = blockIdx.x ? fwords : vwords;
-    uint32_t* prefix = blockIdx.x ? fprefix : vprefix;
-    const int64_t nwords = blockIdx.x ? nfw : nvw;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t start = 0; start < nwords; start += 1024) {
-        const int64_t i = start + threadIdx.x;
-        const uint32_t own = i < nwords ? (uint32_t)__popcll(words[i]) : 0u;
-        uint32_t inc = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += up;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < nwords) prefix[i] = before + inc - own;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = s_carry;
-}
-
-__device__ __forceinline__ bool ms_bit(const unsigned long long* __restrict__ words, int64_t i) {
-    return (words[i >> 6] >> (i & 63)) & 1ull;
-}
-
-// rank of a set bit among the set: numpy's cumsum(keep) - 1
-__device__ __forceinline__ int64_t ms_rank(const unsigned long long* __restrict__ words, const uint32_t* __restrict__ prefix,
-                                           int64_t i) {
-    return (int64_t)prefix[i >> 6] + __popcll(words[i >> 6] & ((1ull << (i & 63)) - 1ull));
+// workgroup 0 the vertex words, workgroup 1 the face words (compact.h)
+__global__ __launch_bounds__(SCAN_THREADS) void ms_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
+                                                        uint32_t* __restrict__ vprefix,
+                                                        const unsigned long long* __restrict__ fwords, int64_t nfw,
+                                                        uint32_t* __restrict__ fprefix, MsHeader* hdr) {
+    const bool f = blockIdx.x != 0;
+    const uint32_t kept = popcount_prefix_sums(f ? fwords : vwords, f ? nfw : nvw, f ? fprefix : vprefix);
+    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = kept;
 }
 
 __global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict__ verts, const float* __restrict__ normals, int nv,
@@ -353,8 +321,8 @@ __global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict_
                                                         const uint32_t* __restrict__ vprefix, int64_t capacity,
                                                         float* __restrict__ out_verts, float* __restrict__ out_normals) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv || !ms_bit(vwords, v)) return;                       // set bits are representatives: good vertices
-    const int64_t dst = ms_rank(vwords, vprefix, v);
+    if (v >= nv || !bit_test(vwords, v)) return;                       // set bits are representatives: good vertices
+    const int64_t dst = bit_rank(vwords, vprefix, v);
     if (dst >= capacity) return;                                     // never past the caller's arrays
     const MsSlot slot = table[slot_of[v]];
     float x[3];
@@ -402,19 +370,15 @@ __global__ __launch_bounds__(256) void ms_emit_faces(const int32_t* __restrict__
                                                      const uint32_t* __restrict__ vprefix, int64_t capacity,
                                                      int32_t* __restrict__ out_faces) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || !ms_bit(fwords, f)) return;
+    if (f >= nf || !bit_test(fwords, f)) return;
     int r[3];
     if (!ms_corners(faces, f, nv, rep, r)) return;                   // such a face never has its bit set
-    const int64_t dst = ms_rank(fwords, fprefix, f);
+    const int64_t dst = bit_rank(fwords, fprefix, f);
     if (dst >= capacity) return;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)ms_rank(vwords, vprefix, r[k]);
+    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)bit_rank(vwords, vprefix, r[k]);
 }
 
-static int64_t ms_align(int64_t b) { return (b + 255) / 256 * 256; }
-static bool ms_sizes_ok(int64_t nv, int64_t nf) {
-    return nv >= 0 && nf >= 0 && nv < (int64_t(1) << 31) - 64 && nf < (int64_t(1) << 31) - 64;
-}
 // the smallest power of two >= 2 n (at least 64)
 static uint64_t ms_capacity(int64_t n) {
     uint64_t cap = 64;
@@ -437,30 +401,27 @@ struct MsWorkspace {
     int64_t nvw, nfw, bytes;
 };
 
-static MsWorkspace ms_carve(void* ws, int64_t nv, int64_t nf) {
-    char* base = static_cast<char*>(ws);
+static MsWorkspace ms_carve(const void* ws, int64_t nv, int64_t nf) {
+    Carver c(ws, 256);
     MsWorkspace w;
     w.cap = ms_capacity(nv);
     w.fcap = ms_capacity(nf);
     w.nvw = (nv + 63) / 64;
     w.nfw = (nf + 63) / 64;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { char* p = base + off; off += ms_align(bytes); return p; };
-    w.hdr = reinterpret_cast<MsHeader*>(take(sizeof(MsHeader)));
-    w.table = reinterpret_cast<MsSlot*>(take((int64_t)w.cap * (int64_t)sizeof(MsSlot)));
-    w.slot_of = reinterpret_cast<uint32_t*>(take(nv * 4));
-    w.rep = reinterpret_cast<int*>(take(nv * 4));
-    w.ftab = reinterpret_cast<int*>(take((int64_t)w.fcap * 4));
-    w.fslot = reinterpret_cast<uint32_t*>(take(nf * 4));
-    w.vwords = reinterpret_cast<unsigned long long*>(take(w.nvw * 8));
-    w.vprefix = reinterpret_cast<uint32_t*>(take(w.nvw * 4));
-    w.fwords = reinterpret_cast<unsigned long long*>(take(w.nfw * 8));
-    w.fprefix = reinterpret_cast<uint32_t*>(take(w.nfw * 4));
-    w.bytes = off;
+    w.hdr = c.take<MsHeader>(1);
+    w.table = c.take<MsSlot>((int64_t)w.cap);
+    w.slot_of = c.take<uint32_t>(nv);
+    w.rep = c.take<int>(nv);
+    w.ftab = c.take<int>((int64_t)w.fcap);
+    w.fslot = c.take<uint32_t>(nf);
+    w.vwords = c.take<unsigned long long>(w.nvw);
+    w.vprefix = c.take<uint32_t>(w.nvw);
+    w.fwords = c.take<unsigned long long>(w.nfw);
+    w.fprefix = c.take<uint32_t>(w.nfw);
+    w.bytes = c.offset;
     return w;
 }
 
-static unsigned ms_grid(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : g); }
 static bool ms_finite(float x) { return x - x == 0.0f; }
 
 }  // namespace nm
@@ -468,7 +429,7 @@ static bool ms_finite(float x) { return x - x == 0.0f; }
 using namespace nm;
 
 #define MS_REQUIRE_MESH(nv, nf)                                                                                          \
-    NM_REQUIRE(ms_sizes_ok(nv, nf), "mesh simplify: vertex and face counts must be in [0, 2^31 - 64)");                  \
+    NM_REQUIRE(mesh_size_ok(nv) && mesh_size_ok(nf), "mesh simplify: vertex and face counts must be in [0, 2^31 - 64)");  \
     NM_REQUIRE(nf == 0 || nv > 0, "mesh simplify: faces without vertices")
 #define MS_REQUIRE_GRID(ox, oy, oz, cell)                                                                                \
     NM_REQUIRE(ms_finite(cell) && cell > 0.0f, "mesh simplify: the cell size must be finite and > 0");                   \
@@ -477,7 +438,7 @@ using namespace nm;
 extern "C" {
 
 int64_t nm_mesh_simplify_workspace_bytes(int64_t num_vertices, int64_t num_faces) {
-    if (!ms_sizes_ok(num_vertices, num_faces)) return 0;
+    if (!mesh_size_ok(num_vertices) || !mesh_size_ok(num_faces)) return 0;
     return ms_carve(nullptr, num_vertices, num_faces).bytes;
 }
 
@@ -492,30 +453,31 @@ int nm_mesh_simplify_cluster(const float* d_verts, int64_t num_vertices, const i
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
     const MsGrid g{{origin_x, origin_y, origin_z}, cell};
+    const unsigned vgrid = launch_grid(num_vertices), fgrid = launch_grid(num_faces);
     const uint64_t most = w.cap > w.fcap ? w.cap : w.fcap;
     hipLaunchKernelGGL(ms_init, dim3((unsigned)(most / 256 > 4096 ? 4096 : most / 256 ? most / 256 : 1)), dim3(256), 0, s, w.table,
                        w.cap, w.ftab, w.fcap, w.vwords, w.nvw, w.hdr);
     NM_HIP_CHECK(hipGetLastError());
     if (nv) {
         if (flags & NM_MESH_SIMPLIFY_AGGREGATE)
-            hipLaunchKernelGGL(ms_insert<true>, dim3(ms_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.cap,
+            hipLaunchKernelGGL(ms_insert<true>, dim3(vgrid), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.cap,
                                w.slot_of, w.rep, w.hdr);
         else
-            hipLaunchKernelGGL(ms_insert<false>, dim3(ms_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.cap,
+            hipLaunchKernelGGL(ms_insert<false>, dim3(vgrid), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.cap,
                                w.slot_of, w.rep, w.hdr);
         NM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(ms_representatives, dim3(ms_grid(num_vertices)), dim3(256), 0, s, w.table, w.slot_of, w.rep, nv, w.hdr);
+        hipLaunchKernelGGL(ms_representatives, dim3(vgrid), dim3(256), 0, s, w.table, w.slot_of, w.rep, nv, w.hdr);
         NM_HIP_CHECK(hipGetLastError());
     }
     if (num_faces) {
-        hipLaunchKernelGGL(ms_insert_faces, dim3(ms_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.ftab, w.fcap,
+        hipLaunchKernelGGL(ms_insert_faces, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.ftab, w.fcap,
                            w.fslot);
         NM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(ms_mark, dim3(ms_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.ftab, w.fslot, w.fwords,
+        hipLaunchKernelGGL(ms_mark, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.ftab, w.fslot, w.fwords,
                            w.vwords, w.hdr);
         NM_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(ms_scan, dim3(2), dim3(1024), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
+    hipLaunchKernelGGL(ms_scan, dim3(2), dim3(SCAN_THREADS), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
     NM_HIP_CHECK(hipGetLastError());
     MsHeader h;
     NM_HIP_CHECK(hipMemcpyAsync(&h, w.hdr, sizeof(MsHeader), hipMemcpyDeviceToHost, s));
@@ -541,17 +503,18 @@ int nm_mesh_simplify_emit(const void* d_workspace, const float* d_verts, int64_t
     NM_REQUIRE(d_workspace && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces), "bad argument");
     NM_REQUIRE(vertices_kept == 0 || (d_out_verts && (!d_normals || d_out_normals)), "mesh simplify: an input array without its output");
     NM_REQUIRE(faces_kept == 0 || d_out_faces, "mesh simplify: null face output");
-    const MsWorkspace w = ms_carve(const_cast<void*>(d_workspace), num_vertices, num_faces);
+    const MsWorkspace w = ms_carve(d_workspace, num_vertices, num_faces);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
     const MsGrid g{{origin_x, origin_y, origin_z}, cell};
+    const unsigned vgrid = launch_grid(num_vertices), fgrid = launch_grid(num_faces);
     if (vertices_kept) {
-        hipLaunchKernelGGL(ms_emit_vertices, dim3(ms_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.slot_of,
+        hipLaunchKernelGGL(ms_emit_vertices, dim3(vgrid), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.slot_of,
                            w.vwords, w.vprefix, vertices_kept, d_out_verts, d_out_normals);
         NM_HIP_CHECK(hipGetLastError());
     }
     if (faces_kept) {
-        hipLaunchKernelGGL(ms_emit_faces, dim3(ms_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.fwords, w.fprefix,
+        hipLaunchKernelGGL(ms_emit_faces, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.fwords, w.fprefix,
                            w.vwords, w.vprefix, faces_kept, d_out_faces);
         NM_HIP_CHECK(hipGetLastError());
     }

@@ -8,14 +8,15 @@
 //                       words of a plane, so no padding is needed), every thread then votes over its window from LDS for its
 //                       4 rows.  The keep bits leave each wave as one __ballot word per (row, 64-column segment): the words in
 //                       memory order are the pixels in row-major order.
-//   2. surface_scan     one workgroup: popcount of every word, exclusive prefix sums, the total -- the compaction order is the
-//                       pixel order by construction, whatever order the tiles ran in (no atomic queue).
-//   3. surface_gather   one thread per pixel: a kept pixel's row is the prefix of its word + the popcount of the lower bits.
+//   2. surface_scan     the ordered compaction of compact.h over those words: one workgroup takes the prefix sums of their
+//                       popcounts and the total, so the output order is the pixel order whatever order the tiles ran in.
+//   3. surface_gather   one thread per pixel: a kept pixel's row is its rank among the set bits.
 // All arithmetic is fp32 with two roundings per multiply-add (-ffp-contract=off) in torch's order of operations, so votes,
 // mask and gathered rows equal the restated reference (tests/surface_filter.py) bit for bit.
 // Memory-bound and small: 28 -- 44 B read and at most 41 B written per pixel, 640 000 pixels per view.
 #include <math.h>
 
+#include "compact.h"
 #include "nm_internal.h"
 
 namespace nm {
@@ -95,37 +96,14 @@ __global__ __launch_bounds__(256) void surface_filter(SfIn in, int step, float t
     }
 }
 
-// exclusive prefix sums of the words' popcounts (uint32 per word) and their total; one workgroup of 1024 threads walks the
-// words 1024 at a time with a running carry (10 400 words for an 800 x 800 view)
-__global__ __launch_bounds__(1024) void surface_scan(const unsigned long long* __restrict__ words, int64_t nwords,
-                                                     uint32_t* __restrict__ prefix, int64_t* __restrict__ total,
-                                                     int64_t* __restrict__ count_out) {
-    __shared__ uint32_t s_wave[16];
-    __shared__ uint32_t s_carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int64_t start = 0; start < nwords; start += 1024) {
-        const int64_t i = start + threadIdx.x;
-        const uint32_t own = i < nwords ? (uint32_t)__popcll(words[i]) : 0u;
-        uint32_t inc = own;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += up;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_carry;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < nwords) prefix[i] = before + inc - own;
-        __syncthreads();
-        if (threadIdx.x == 1023) s_carry = before + inc;
-        __syncthreads();
-    }
+// one workgroup: the prefix sums of the image's words (compact.h) and the number of kept pixels
+__global__ __launch_bounds__(SCAN_THREADS) void surface_scan(const unsigned long long* __restrict__ words, int64_t nwords,
+                                                             uint32_t* __restrict__ prefix, int64_t* __restrict__ total,
+                                                             int64_t* __restrict__ count_out) {
+    const uint32_t kept = popcount_prefix_sums(words, nwords, prefix);
     if (threadIdx.x == 0) {
-        *total = (int64_t)s_carry;
-        if (count_out) *count_out = (int64_t)s_carry;
+        *total = (int64_t)kept;
+        if (count_out) *count_out = (int64_t)kept;
     }
 }
 
@@ -151,9 +129,8 @@ __global__ __launch_bounds__(256) void surface_gather(SfIn in, const float* __re
     if (w >= (int64_t)in.height * words_per_row) return;
     const int row = (int)(w / words_per_row), col = (int)(w - (int64_t)row * words_per_row) * SF_TW + lane;
     if (col >= in.width) return;
-    const unsigned long long word = words[w];
-    if (!((word >> lane) & 1ull)) return;
-    const int64_t dst = row_offset + (int64_t)prefix[w] + __popcll(word & ((1ull << lane) - 1ull));
+    if (!bit_test(words + w, lane)) return;
+    const int64_t dst = row_offset + bit_rank(words + w, prefix + w, lane);
     if (dst < 0 || dst >= capacity) return;                          // never past the caller's arrays
     const int64_t pix = (int64_t)row * in.width + col;
     float p[3];
@@ -171,16 +148,16 @@ __global__ __launch_bounds__(256) void surface_gather(SfIn in, const float* __re
 }
 
 static int64_t sf_words(int64_t h, int64_t w) { return h * ((w + SF_TW - 1) / SF_TW); }
-static int64_t sf_align(int64_t b) { return (b + 15) / 16 * 16; }
 
-struct SfWorkspace { unsigned long long* words; uint32_t* prefix; int64_t* total; };
+struct SfWorkspace { unsigned long long* words; uint32_t* prefix; int64_t* total; int64_t bytes; };
 
-static SfWorkspace sf_carve(void* ws, int64_t nwords) {
-    char* base = static_cast<char*>(ws);
+static SfWorkspace sf_carve(const void* ws, int64_t nwords) {
+    Carver c(ws, 16);
     SfWorkspace s;
-    s.words = reinterpret_cast<unsigned long long*>(base);
-    s.prefix = reinterpret_cast<uint32_t*>(base + sf_align(nwords * 8));
-    s.total = reinterpret_cast<int64_t*>(base + sf_align(nwords * 8) + sf_align(nwords * 4));
+    s.words = c.take<unsigned long long>(nwords);
+    s.prefix = c.take<uint32_t>(nwords);
+    s.total = c.take<int64_t>(2);                                    // the count and 8 spare bytes
+    s.bytes = c.offset;
     return s;
 }
 
@@ -194,8 +171,7 @@ extern "C" {
 
 int64_t nm_surface_filter_workspace_bytes(int32_t height, int32_t width) {
     if (!sf_sizes_ok(height, width)) return 0;
-    const int64_t n = sf_words(height, width);
-    return sf_align(n * 8) + sf_align(n * 4) + 16;
+    return sf_carve(nullptr, sf_words(height, width)).bytes;
 }
 
 int nm_surface_filter(const float* d_origins, int per_ray_o, const float* d_dirs, const float* d_depth,
@@ -215,7 +191,7 @@ int nm_surface_filter(const float* d_origins, int per_ray_o, const float* d_dirs
     hipLaunchKernelGGL(surface_filter, dim3((unsigned)wpr, (unsigned)((height + SF_TH - 1) / SF_TH)), dim3(SF_TW, 4), lds, s, in,
                        (int)step, (float)dist_threshold, (int)min_votes, wpr, d_votes, d_keep, ws.words);
     NM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(surface_scan, dim3(1), dim3(1024), 0, s, ws.words, nwords, ws.prefix, ws.total, d_count);
+    hipLaunchKernelGGL(surface_scan, dim3(1), dim3(SCAN_THREADS), 0, s, ws.words, nwords, ws.prefix, ws.total, d_count);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -232,9 +208,9 @@ int nm_surface_gather(const void* d_workspace, const float* d_origins, int per_r
     const SfIn in{d_origins, d_dirs, d_depth, d_opacity, (float)min_opacity, per_ray_o ? 1 : 0, (int)height, (int)width};
     const int wpr = (width + SF_TW - 1) / SF_TW;
     const int64_t nwords = sf_words(height, width);
-    const SfWorkspace ws = sf_carve(const_cast<void*>(d_workspace), nwords);
+    const SfWorkspace ws = sf_carve(d_workspace, nwords);
     const SfOut out{d_points, d_normals, d_colors, d_colors_u8};
-    hipLaunchKernelGGL(surface_gather, dim3((unsigned)((nwords * 64 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(surface_gather, dim3(launch_grid(nwords * 64)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        in, d_rgb, wpr, ws.words, ws.prefix, row_offset, capacity, out);
     NM_HIP_CHECK(hipGetLastError());
     return 0;

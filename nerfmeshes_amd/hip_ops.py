@@ -670,14 +670,25 @@ def _mesh_faces(faces, num_vertices):
     return faces.detach().contiguous(), nv, nf
 
 
+def _mesh_check(lib, rc, what):
+    """status of a nm_mesh_* entry: 2 (an argument the entry refuses) is the caller's ValueError, in the entry's own words"""
+    if rc == 2:
+        raise ValueError((lib.nm_last_error() or f"{what}: bad argument".encode()).decode())
+    check(rc, what)
+
+
+def _mesh_workspace(nbytes, what, nv, nf, device):
+    """the workspace of a mesh entry; its *_workspace_bytes gives 0 for sizes the entry refuses"""
+    if nbytes == 0:
+        raise ValueError(f"{what}: {nv} vertices / {nf} faces are beyond the supported sizes")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def _mesh_components(lib, faces, nv, nf):
     dev = faces.device
     labels = torch.empty(nv, dtype=torch.int32, device=dev)
     counts = torch.empty(nv, dtype=torch.int32, device=dev)
-    nbytes = int(lib.nm_mesh_components_workspace_bytes(nv, nf))
-    if nbytes == 0:
-        raise ValueError(f"mesh components: {nv} vertices / {nf} faces are beyond the supported sizes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _mesh_workspace(int(lib.nm_mesh_components_workspace_bytes(nv, nf)), "mesh components", nv, nf, dev)
     check(lib.nm_mesh_components(_ptr(faces), nf, nv, _ptr(labels), _ptr(counts), _ptr(ws), _stream()), "nm_mesh_components")
     return labels, counts, ws
 
@@ -725,9 +736,7 @@ def mesh_filter_components(verts, faces, normals, values=None, keys=None, min_fa
     kv, kf, comps, kept = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
     rc = lib.nm_mesh_components_select(_ptr(faces), nf, nv, _ptr(labels), _ptr(counts), min_faces, keep_largest, _ptr(ws),
                                        C.byref(kv), C.byref(kf), C.byref(comps), C.byref(kept), _stream())
-    if rc == 2:
-        raise ValueError((lib.nm_last_error() or b"nm_mesh_components_select: bad argument").decode())
-    check(rc, "nm_mesh_components_select")
+    _mesh_check(lib, rc, "nm_mesh_components_select")
     out_verts = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
     out_normals = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
     out_faces = torch.empty(kf.value, 3, dtype=torch.int32, device=dev)
@@ -775,17 +784,12 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     origin = [float(np.float32(x)) for x in (origin.tolist() if isinstance(origin, (torch.Tensor, np.ndarray)) else origin)]
     if len(origin) != 3 or not all(np.isfinite(x) for x in origin):
         raise ValueError(f"mesh_simplify: the origin must be three finite numbers, got {origin}")
-    nbytes = int(lib.nm_mesh_simplify_workspace_bytes(nv, nf))
-    if nbytes == 0:
-        raise ValueError(f"mesh simplify: {nv} vertices / {nf} faces are beyond the supported sizes")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _mesh_workspace(int(lib.nm_mesh_simplify_workspace_bytes(nv, nf)), "mesh simplify", nv, nf, dev)
     counts = (C.c_int64 * 7)()
     flags = 1 if (SIMPLIFY_AGGREGATE if aggregate is None else aggregate) else 0
     rc = lib.nm_mesh_simplify_cluster(_ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin, cell, flags, _ptr(ws), counts,
                                       _stream())
-    if rc == 2:
-        raise ValueError((lib.nm_last_error() or b"nm_mesh_simplify_cluster: bad argument").decode())
-    check(rc, "nm_mesh_simplify_cluster")
+    _mesh_check(lib, rc, "nm_mesh_simplify_cluster")
     clusters, kv, kf, degenerate, duplicate, bad_v, bad_f = (int(x) for x in counts)
     if bad_v:
         raise ValueError(f"mesh simplify: {bad_v} vertices have a non-finite coordinate or a cell index outside [0, {SIMPLIFY_CELLS})")
@@ -823,9 +827,7 @@ def _mesh_face_weights(lib, verts, faces, nv, nf, what):
     cdf = torch.empty(nf, dtype=torch.int64, device=dev)             # uint64 on the device; every prefix is below 2^63
     hdr = torch.empty(int(lib.nm_mesh_face_weights_workspace_bytes()), dtype=torch.uint8, device=dev)
     rc = lib.nm_mesh_face_weights(_ptr(verts), nv, _ptr(faces), nf, _ptr(areas), _ptr(cdf), _ptr(hdr), _stream())
-    if rc == 2:
-        raise ValueError((lib.nm_last_error() or b"nm_mesh_face_weights: bad argument").decode())
-    check(rc, "nm_mesh_face_weights")
+    _mesh_check(lib, rc, "nm_mesh_face_weights")
     bad, total = (int(v) for v in hdr[:16].view(torch.int64).tolist())
     if bad:
         raise ValueError(f"{what}: {bad} faces have a vertex index outside [0, {nv})")
@@ -867,9 +869,7 @@ def mesh_sample_points(verts, faces, n=None, u=None, generator=None, return_norm
     normals = torch.empty(count, 3, dtype=torch.float32, device=dev) if return_normals else None
     rc = lib.nm_mesh_sample_points(_ptr(u), count, _ptr(verts), nv, _ptr(faces), nf, _ptr(cdf), _ptr(points), _ptr(face_ids),
                                    _ptr(normals), _stream())
-    if rc == 2:
-        raise ValueError((lib.nm_last_error() or b"nm_mesh_sample_points: bad argument").decode())
-    check(rc, "nm_mesh_sample_points")
+    _mesh_check(lib, rc, "nm_mesh_sample_points")
     return (points, face_ids, normals) if return_normals else (points, face_ids)
 
 

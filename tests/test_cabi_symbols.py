@@ -68,6 +68,25 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert lib.nm_export_obj(ok, 1, None, 0, None, 0, None, 0, b"/nonexistent-dir/x.obj") == 6 and "cannot open" in err()
 
 
+def test_workspace_sizes_are_the_recorded_ones():
+    """The byte layout of the mesh / point-cloud workspaces is part of the boundary (hip_ops.py reads their headers): the sizes
+    recorded in tests/golden/workspace_bytes.json before csrc/compact.h's carver replaced the per-unit arithmetic, word and
+    alignment boundaries and the size limit included (0 = refused)."""
+    import json
+    lib = _lib.load()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")))
+    assert sorted(want) == ["nm_mesh_components_workspace_bytes", "nm_mesh_face_weights_workspace_bytes",
+                            "nm_mesh_simplify_workspace_bytes", "nm_points_nearest_workspace_bytes",
+                            "nm_surface_filter_workspace_bytes"]
+    checked = 0
+    for name, rows in want.items():
+        for *args, nbytes in rows:
+            assert int(getattr(lib, name)(*args)) == nbytes, (name, args)
+            checked += 1
+    assert checked == 3 * 66 + 7 + 1
+    assert lib.nm_mesh_components_workspace_bytes(2 ** 31 - 64, 1) == 0 < lib.nm_mesh_components_workspace_bytes(2 ** 31 - 65, 1)
+
+
 def test_ctypes_structs_match_the_header(tmp_path):
     """The ctypes mirrors of the structs that cross the boundary by pointer (nerfmeshes_amd/_lib.py) against what a C compiler makes
     of include/nerfmeshes_hip.h: sizes and the offsets of the members added last (nm_mlp_tape.v_stride and nm_mlp_param_grads, ABI

@@ -142,6 +142,28 @@ def test_many_isolated_triangles(ops):
     assert none[1].shape == (0, 3) and none[0].shape == (0, 3) and none[3].shape == (0,) and none[5]["vertices_kept"] == 0
 
 
+def _triangles_and_strips(nv):
+    """isolated components, alternately one triangle (3 vertices) and a strip of two (4 vertices), ending at the last vertex;
+    the nv % 7 vertices in front are in no face"""
+    base = (nv % 7 + 7 * np.arange(nv // 7))[:, None, None]
+    return (base + np.array([[0, 1, 2], [3, 4, 5], [4, 6, 5]])).astype(np.int32).reshape(-1, 3)
+
+
+@pytest.mark.parametrize("nv", [64, 65_536, 65_537, 131_073])
+def test_compaction_at_the_chunk_boundaries_of_the_scan(ops, nv):
+    """1, 1024, 1025 and 2049 words of vertex keep bits: a single partial wave, one full chunk of the one-workgroup scan
+    (csrc/compact.h), the first word of the second chunk (the carry is handed over) and of the third (it is carried twice).
+    min_faces = 2 keeps the strips alone, so set and clear bits alternate in the vertex and in the face words, and the last
+    vertex -- alone in the last word of the three larger meshes -- is kept: its new index needs that word's prefix."""
+    faces = _triangles_and_strips(nv)
+    assert (nv + 63) // 64 in (1, 1024, 1025, 2049) and faces.max() == nv - 1
+    got, rows = _filter_both(ops, faces, nv, min_faces=2)
+    want = MC.filter_components(rows[0], faces, rows[1], rows[2], rows[3], min_faces=2)
+    _same_filter(got, want, f"{nv} vertices")
+    assert want[5]["vertices_kept"] == 4 * (nv // 7) and want[5]["faces_kept"] == 2 * (nv // 7)
+    assert want[4][-1] == (nv - 1) * 7, "the last row out is the last vertex"
+
+
 def test_unreferenced_vertices_and_k_beyond_the_components(ops):
     faces = np.array([[7, 3, 5], [5, 3, 8], [8, 10, 12], [1, 2, 6]], np.int32)         # 0, 4, 9, 11 are in no triangle
     nv = 13

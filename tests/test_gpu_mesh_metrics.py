@@ -172,6 +172,25 @@ def _check_mesh(ops, verts, faces, n, seed, tag, on_boundary=None):
     return want_areas, want_cdf, want_fid
 
 
+@pytest.mark.parametrize("nf", [1, 1023, 1024, 1025, 2049])
+def test_face_weights_at_the_chunk_boundaries_of_the_scan(ops, nf):
+    """the cumulative table of 1, 1023, 1024, 1025 and 2049 random triangles: a single partial wave, a chunk of the
+    one-workgroup scan (csrc/compact.h) one short of full and exactly full, the first entry of the second chunk (the carry is
+    handed over) and of the third (it is carried twice) -- against numpy's cumsum of the restated integer weights in uint64"""
+    rng = np.random.default_rng(nf)
+    verts = rng.random((3 * nf, 3)).astype(np.float32)
+    faces = rng.permutation(3 * nf).astype(np.int32).reshape(nf, 3)
+    want_areas, want_cdf, bad = MM.face_weights(verts, faces)
+    weights = np.diff(np.concatenate((np.zeros(1, np.uint64), want_cdf)))
+    assert bad == 0 and (weights > 0).all() and weights.max() >= 2 ** 31, "every prefix moves; the largest weight is in [2^31, 2^32)"
+    assert np.array_equal(np.cumsum(weights, dtype=np.uint64), want_cdf)
+    dv, df, nv, _ = ops._mesh_arrays(_dev(verts), _dev(faces), "test")
+    areas, cdf, total = ops._mesh_face_weights(ops._lib.load(), dv, df, nv, nf, "test")
+    _same(areas, want_areas, f"{nf} faces: areas")
+    assert cdf.dtype == torch.int64 and np.array_equal(_np(cdf).view(np.uint64), want_cdf), f"{nf} faces: cdf"
+    assert total == int(want_cdf[-1]) == int(_np(cdf)[-1])
+
+
 def test_sampling_on_the_uv_sphere(ops):
     verts, faces = MM.uv_sphere()
     assert faces.shape == (4096, 3)

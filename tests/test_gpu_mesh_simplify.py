@@ -119,6 +119,39 @@ def test_thin_sheet_keeps_both_sides_and_drops_same_winding_duplicates(ops):
     assert np.array_equal(want[2], np.tile(np.float32([0, 0, -1]), (k * k, 1))), "(-1 + 1 - 1) normalised"
 
 
+def _triangles_and_strips(nv):
+    """test_gpu_mesh_components.py's family with coordinates: component k lives in the cells x in [4 k, 4 k + 2), a cell is 1.
+    A triangle has its corners in three cells.  A strip (p0, p1, p2), (p1, p3, p2) has p0 and p1 in one cell: p1 merges into
+    p0, the first face degenerates, the second stays, and p3 -- the mesh's last vertex -- stays.  The nv % 7 vertices in
+    front are in no face, each in a cell of its own."""
+    k = nv // 7
+    x = 4.0 * np.arange(k)[:, None, None]
+    corners = np.array([[0.5, 0.5, 0.5], [1.5, 0.5, 0.5], [0.5, 1.5, 0.5],                      # the triangle
+                        [0.25, 0.25, 0.5], [0.75, 0.5, 0.5], [1.5, 0.5, 0.5], [0.5, 1.5, 0.5]])  # the strip, 2 cells further
+    corners[3:, 0] += 2.0
+    loose = np.stack((np.arange(nv % 7) + 0.5, np.full(nv % 7, 5.5), np.full(nv % 7, 0.5)), 1)
+    verts = np.concatenate((loose, (corners + x * np.array([1.0, 0.0, 0.0])).reshape(-1, 3))).astype(np.float32)
+    base = (nv % 7 + 7 * np.arange(k))[:, None, None]
+    faces = (base + np.array([[0, 1, 2], [3, 4, 5], [4, 6, 5]])).astype(np.int32).reshape(-1, 3)
+    normals = np.random.default_rng(nv).standard_normal((nv, 3)).astype(np.float32)
+    return verts, faces, normals
+
+
+@pytest.mark.parametrize("nv", [64, 65_536, 65_537, 131_073])
+def test_compaction_at_the_chunk_boundaries_of_the_scan(ops, nv):
+    """1, 1024, 1025 and 2049 words of used bits: a single partial wave, one full chunk of the one-workgroup scan
+    (csrc/compact.h), the first word of the second chunk (the carry is handed over) and of the third (it is carried twice).
+    Set and clear bits alternate in the vertex and in the face words, and the last vertex -- alone in the last word of the
+    three larger meshes -- is kept: its new index needs that word's prefix."""
+    v, f, n = _triangles_and_strips(nv)
+    assert (nv + 63) // 64 in (1, 1024, 1025, 2049) and len(v) == nv and f.max() == nv - 1
+    want = _check(ops, _dev(v), _dev(f), _dev(n), 1.0, (0, 0, 0), f"{nv} vertices")
+    k = nv // 7
+    assert want[3] == dict(vertices=nv, faces=3 * k, clusters=nv - k, vertices_kept=6 * k, faces_kept=2 * k, degenerate_faces=k,
+                           duplicate_faces=0)
+    assert want[0][-1].tobytes() == v[-1].tobytes() and want[1][-1].max() == 6 * k - 1, "the last vertex is the last row out"
+
+
 def test_everything_in_one_cell_leaves_nothing(ops):
     rng = np.random.default_rng(2)
     v = rng.random((5000, 3), dtype=np.float32)

@@ -146,6 +146,15 @@ def test_noise_every_size_and_step(ops, H, W, step):
     _check(ops, _noise(H, W), step, share=H * W >= 1000)
 
 
+@pytest.mark.parametrize("H,W", [(1024, 64), (1025, 64), (41, 1601)])
+def test_noise_at_the_chunk_boundaries_of_the_scan(ops, H, W):
+    """1024, 1025 and 1066 words of keep bits: exactly one full chunk of the one-workgroup scan (csrc/compact.h), the first
+    word of the second chunk, where the carry is handed over, and a second chunk of 42 words that is a single partial wave.
+    (The 800 x 800 image of SIZES has 10 400 words: the carry is carried ten times there.)"""
+    assert H * ((W + 63) // 64) in (1024, 1025, 1066)
+    _check(ops, _noise(H, W), 1, share=True)
+
+
 @pytest.mark.parametrize("H,W", SIZES[2:])
 @pytest.mark.parametrize("shape", ["plane", "sphere"])
 def test_plane_and_sphere_on_real_rays(ops, shape, H, W):
