@@ -114,8 +114,8 @@ enum { NM_KERNEL_GENERIC = 0x100 };
 int nm_mlp_create_ex(const nm_mlp_desc* desc, const nm_mlp_weights* host_weights, int device, int precision, nm_mlp** out);
 int nm_mlp_precision(const nm_mlp* mlp);
 void nm_mlp_destroy(nm_mlp* mlp);
-/* Which tuning variant of the kernel the handle was bound to (0 = production; NM_MLP_VARIANT selects others
- * for A/B measurements) and its waves per workgroup. */
+/* Which kernel family the handle was bound to (0: a tuned kernel; 1000 + width class: the generic-shape family; 2000: the
+ * layer-wise path) and its waves per workgroup. */
 int nm_mlp_kernel_variant(const nm_mlp* mlp, int* waves_per_workgroup);
 /* FLOP of one sample through the net (weights-only count). */
 int64_t nm_mlp_flops_per_sample(const nm_mlp* mlp, int density_only);

@@ -14,7 +14,7 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_NAME = "libnerfmeshes_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
-SOURCES = ["nerf_mlp.hip", "nerf_mlp_generic_a.hip", "nerf_mlp_generic_b.hip", "nerf_mlp_generic_c.hip", "nerf_mlp_generic_d.hip", "nerf_mlp_generic_e.hip", "nerf_mlp_generic_s.hip", "nerf_mlp_generic_a_long.hip", "nerf_mlp_generic_b_long.hip", "nerf_mlp_generic_c_long.hip", "nerf_mlp_generic_d_long.hip", "nerf_mlp_generic_s_long.hip", "nerf_mlp_generic_s_long2.hip", "nerf_train.hip", "nerf_bwd_fused.hip", "nerf_dw.hip", "nerf_dw_g.hip", "nerf_layerwise.hip", "mlp_api.hip", "ray_ops.hip", "marching_cubes.hip", "mc_refine.hip", "surface_filter.hip", "mesh_components.hip", "mesh_simplify.hip", "mesh_metrics.hip", "nerf_input_grad.hip", "buff_tree.hip", "np_reduce.hip", "obj_writer.cpp", "ply_writer.cpp"]
+SOURCES = ["nerf_mlp.hip", "nerf_mlp_generic_a.hip", "nerf_mlp_generic_b.hip", "nerf_mlp_generic_c.hip", "nerf_mlp_generic_d.hip", "nerf_mlp_generic_s.hip", "nerf_mlp_generic_a_long.hip", "nerf_mlp_generic_b_long.hip", "nerf_mlp_generic_c_long.hip", "nerf_mlp_generic_d_long.hip", "nerf_mlp_generic_s_long.hip", "nerf_mlp_generic_s_long2.hip", "nerf_train.hip", "nerf_bwd_fused.hip", "nerf_dw.hip", "nerf_dw_g.hip", "nerf_layerwise.hip", "mlp_api.hip", "ray_ops.hip", "marching_cubes.hip", "mc_refine.hip", "surface_filter.hip", "mesh_components.hip", "mesh_simplify.hip", "mesh_metrics.hip", "nerf_input_grad.hip", "buff_tree.hip", "np_reduce.hip", "obj_writer.cpp", "ply_writer.cpp"]
 # every header next to the sources (mlp_device*.h, nm_internal.h, mc_luts.h, ...) + the public C ABI
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "nerfmeshes_hip.h")]
 # -ffp-contract=off: the reference computes a*b+c with two roundings (torch eager ops); every fused
@@ -42,9 +42,6 @@ def needs_build():
     return any(os.path.getmtime(os.path.join(CSRC, d) if not os.path.isabs(d) else d) > t for d in deps)
 
 
-ABLATION_LIB_PATH = os.path.join(CSRC, "libnerfmeshes_hip_ablations.so")
-
-
 def _includes(path, seen):
     """Quoted includes of `path`, transitively (the headers an object depends on)."""
     try:
@@ -70,14 +67,10 @@ def _stale(src_path, obj):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=True, ablations=False, jobs=None):
-    """Product library by default.  ablations=True builds a SEPARATE library with -DNM_ABLATIONS (the MLP kernel
-    A/B variants, some of which compute wrong results on purpose, selectable there by NM_MLP_VARIANT); nothing in
-    the package loads it -- scripts/bench_mlp.py points nerfmeshes_amd._lib at it explicitly.
-    Per-object incremental: only the translation units whose source or included headers changed are recompiled
+def build(force=False, verbose=True, jobs=None):
+    """Per-object incremental: only the translation units whose source or included headers changed are recompiled
     (`jobs` of them at a time, default = the host's cores)."""
-    lib_path = ABLATION_LIB_PATH if ablations else LIB_PATH
-    bdir = os.path.join(CSRC, "build_ablations" if ablations else "build")
+    bdir = os.path.join(CSRC, "build")
     os.makedirs(bdir, exist_ok=True)
     objs, todo = [], []
     for src in _present(SOURCES):
@@ -85,8 +78,8 @@ def build(force=False, verbose=True, ablations=False, jobs=None):
         objs.append(obj)
         if force or _stale(os.path.join(CSRC, src), obj):
             todo.append((src, obj))
-    if not todo and os.path.exists(lib_path) and all(os.path.getmtime(o) <= os.path.getmtime(lib_path) for o in objs):
-        return lib_path
+    if not todo and os.path.exists(LIB_PATH) and all(os.path.getmtime(o) <= os.path.getmtime(LIB_PATH) for o in objs):
+        return LIB_PATH
     jobs = jobs or int(os.environ.get("NM_BUILD_JOBS", "0")) or os.cpu_count() or 4
     # the largest translation units first, so that they are not what the build waits for at the end
     todo.sort(key=lambda so: -_weight(so[0]))
@@ -94,7 +87,7 @@ def build(force=False, verbose=True, ablations=False, jobs=None):
     while (todo or running) and failed is None:
         while todo and len(running) < jobs:
             src, obj = todo.pop(0)
-            cmd = [hipcc()] + FLAGS + (["-DNM_ABLATIONS"] if ablations else []) + ["-c", os.path.join(CSRC, src), "-o", obj]
+            cmd = [hipcc()] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             running.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -108,11 +101,11 @@ def build(force=False, verbose=True, ablations=False, jobs=None):
         for _, p in running:
             p.kill()
         raise RuntimeError(failed)
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path] + objs
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    return lib_path
+    return LIB_PATH
 
 
 # compile cost of the translation units (CPU seconds on this image, measured in round 6): scheduling order only -- the split
@@ -127,4 +120,4 @@ def _weight(src):
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, ablations="--ablations" in sys.argv))
+    print(build(force="--force" in sys.argv))

@@ -39,7 +39,7 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream
 // ---- layer-wise path (nerf_layerwise.hip): networks beyond the fused families' limits -----------------------------------
 // A plan that launches nothing by itself: launch_mlp_timed / the training entry points route such a handle to the layer-wise
 // evaluator.  nm_mlp_kernel_variant reports 2000.
-static const MlpPlan g_layerwise_plan = {0, 0, 0, 8, 0, 2000, 0, false, nullptr, 0, 0, nullptr, 0, nullptr, nullptr};
+static const MlpPlan g_layerwise_plan = {0, 0, 0, 8, 0, 2000, 0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr};
 
 // the per-argument table of one encoding (GEncArg: band, coordinate)
 static void fill_enc_table(float* tab /* [parts * G_ENC_ARGS][2] */, int parts, int F, const float* bands) {

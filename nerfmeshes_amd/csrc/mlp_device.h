@@ -43,22 +43,11 @@ __device__ __forceinline__ void stream_to_lds(const char* src, char* dst, int by
                                                  u * 1024, 0, 0);
 }
 
-// round-1 form (per-lane 64-bit addresses in VGPRs), kept for the A/B variants of the ablation library
-template <int NW>
-__device__ __forceinline__ void stream_to_lds_vaddr(const char* src, char* dst, int bytes, int wave, int lane) {
-    const int units = (bytes + 1023) >> 10;
-    for (int u = wave; u < units; u += NW) {
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(src + (size_t)u * 1024 + lane * 16),
-            (__attribute__((address_space(3))) void*)(dst + u * 1024), 16, 0, 0);
-    }
-}
-
 // One GEMM "stage": acc[NT tiles] += W_stage * B, B = KS1 registers of b1 followed by KS2 of b2.
 // On entry chunk 0 of the stage is resident in ring slot `par`; on exit the chunk described by
 // (tail_src, tail_bytes) -- the first chunk of whatever runs next -- is resident in slot `par`.
 // Per chunk: start the DMA of the following chunk, run this chunk's MFMAs with the A operands of the NEXT
-// k-step already in flight (PIPE; pinned with sched_barrier -- hipcc otherwise sinks the ds_reads next to
+// k-step already in flight (pinned with sched_barrier -- hipcc otherwise sinks the ds_reads next to
 // their use, and the two waves of a SIMD, released together by the barrier, then expose the LDS latency
 // together every 8 MFMAs), one barrier.  (The cursor is SGPR arithmetic on purpose: a chunk table fetched
 // with s_load costs 3 % -- its s_waitcnt lgkmcnt(0) also drains the in-flight ds_reads.)
@@ -68,8 +57,7 @@ __device__ __forceinline__ void stream_to_lds_vaddr(const char* src, char* dst, 
 // 16-instruction burst before the stage: the bursts of the 8 waves of a workgroup (128 KB) outrun the HBM write
 // bandwidth and the next barrier's s_waitcnt vmcnt(0) -- gfx9 counts stores and loads together -- waits for them
 // (10 % of the delta kernel); spread out, each store has a chunk's worth of MFMAs (1.7 us) to retire.
-template <int NT, int KS1, int KS2, int NW, int LDSBUF, int KCH, bool PIPE, bool SPREAD = false, int ABL = 0,
-          bool STORE = false>
+template <int NT, int KS1, int KS2, int NW, int LDSBUF, int KCH, bool STORE = false>
 __device__ __forceinline__ void gemm_stage(f32x4 (&acc)[NT], const float (&b1)[KS1],
                                            const float (&b2)[(KS2 > 0 ? KS2 : 1)], const char* gw,
                                            const char* tail_src, int tail_bytes, char* lds, int& par,
@@ -93,15 +81,7 @@ __device__ __forceinline__ void gemm_stage(f32x4 (&acc)[NT], const float (&b1)[K
         } else {
             next_src = tail_src; next_bytes = tail_bytes;
         }
-        // DMA of the following chunk: either all of this wave's 1 KiB pieces up front, or (SPREAD) one piece per
-        // k-step inside the MFMA stream -- issued together right after the barrier they keep BOTH waves of a
-        // SIMD away from the matrix pipe for ~100 cycles per piece, 73 times per tile
-        const int next_units = (next_bytes + 1023) >> 10;
-        int next_u = wave;
-        if constexpr (!SPREAD && !(ABL & 4)) {
-            if constexpr (ABL & 8) stream_to_lds_vaddr<NW>(next_src, next_slot, next_bytes, wave, lane);
-            else stream_to_lds<NW>(next_src, next_slot, next_bytes, wave, lane);
-        }
+        stream_to_lds<NW>(next_src, next_slot, next_bytes, wave, lane);   // DMA of the following chunk: all of this wave's 1 KiB pieces up front
         if constexpr (STORE) {
             constexpr int TILES = KS1 / 4, PER_CHUNK = (TILES + NCH - 1) / NCH;
             if (store_row) {
@@ -117,50 +97,28 @@ __device__ __forceinline__ void gemm_stage(f32x4 (&acc)[NT], const float (&b1)[K
         }
         const char* buf = lds + par * LDSBUF + lane * (VW * 4);
         avec a_next[NB];
-        if constexpr (PIPE) {
 #pragma unroll
-            for (int blk = 0; blk < NB; ++blk) a_next[blk] = *reinterpret_cast<const avec*>(buf + blk * (64 * VW * 4));
-        }
+        for (int blk = 0; blk < NB; ++blk) a_next[blk] = *reinterpret_cast<const avec*>(buf + blk * (64 * VW * 4));
 #pragma unroll
         for (int ks = 0; ks < steps; ++ks) {
             const int s = c * KCH + ks;
             const float b = s < KS1 ? b1[s < KS1 ? s : 0] : b2[s >= KS1 ? s - KS1 : 0];
             avec a_cur[NB];
 #pragma unroll
-            for (int blk = 0; blk < NB; ++blk) {
-                if constexpr (PIPE) a_cur[blk] = a_next[blk];
-                else a_cur[blk] = *reinterpret_cast<const avec*>(buf + (ks * NB + blk) * (64 * VW * 4));
-            }
-            if constexpr (PIPE) {
-                if (ks + 1 < steps) {
+            for (int blk = 0; blk < NB; ++blk) a_cur[blk] = a_next[blk];
+            if (ks + 1 < steps) {
 #pragma unroll
-                    for (int blk = 0; blk < NB; ++blk)
-                        a_next[blk] = *reinterpret_cast<const avec*>(buf + ((ks + 1) * NB + blk) * (64 * VW * 4));
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                for (int blk = 0; blk < NB; ++blk)
+                    a_next[blk] = *reinterpret_cast<const avec*>(buf + ((ks + 1) * NB + blk) * (64 * VW * 4));
             }
-            if constexpr (SPREAD) {
-                if (next_u < next_units) {
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) void*)(next_src + (size_t)next_u * 1024 + lane * 16),
-                        (__attribute__((address_space(3))) void*)(next_slot + next_u * 1024), 16, 0, 0);
-                    next_u += NW;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
                 for (int q = 0; q < VW; ++q)
                     acc[blk * VW + q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_cur[blk][q], b, acc[blk * VW + q], 0, 0, 0);
         }
-        if constexpr (SPREAD) {   // pieces beyond the chunk's k-step count (short chunks)
-            for (; next_u < next_units; next_u += NW)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(next_src + (size_t)next_u * 1024 + lane * 16),
-                    (__attribute__((address_space(3))) void*)(next_slot + next_u * 1024), 16, 0, 0);
-        }
-        if constexpr (!(ABL & 2)) __syncthreads();  // drains the DMA (vmcnt(0)) and releases slot `par` for the next fill
+        __syncthreads();  // drains the DMA (vmcnt(0)) and releases slot `par` for the next fill
         par ^= 1;
     }
 }
@@ -187,7 +145,7 @@ __device__ __forceinline__ void acc_to_operand(const f32x4 (&acc)[NT], float (&o
 // step s + 1, each keeps the half it needs and hands the other across with one ds_swizzle -- 11 sincosf per lane for the
 // 8x256 network instead of 21, the same function on the same products, so the results are bit for bit what they were.
 // (Round 3: VALU issue time adds to matrix time -- DESIGN.md 3.1 -- and 58 % of a narrow network's VALU work was this.)
-template <int F, int STEPS, int ABL = 0>
+template <int F, int STEPS>
 __device__ __forceinline__ void encode(float (&enc)[STEPS], const float (&x)[3], const float* bands, int g) {
     const bool hi = (g >> 1) != 0;
     const bool want_cos = (g & 1) != 0;
@@ -202,8 +160,7 @@ __device__ __forceinline__ void encode(float (&enc)[STEPS], const float (&x)[3],
     for (int s = 0; s + 1 < NS; s += 2) {
         const float mine = want_cos ? argument(s + 1) : argument(s);
         float sv, cv;
-        if constexpr (ABL & 1) { sv = mine; cv = mine + 1.0f; }
-        else sincosf(mine, &sv, &cv);
+        sincosf(mine, &sv, &cv);
         const float give = want_cos ? sv : cv;
         const float got = __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(give), 0x401f));   // lane ^ 16
         enc[s] = want_cos ? got : sv;
@@ -212,8 +169,7 @@ __device__ __forceinline__ void encode(float (&enc)[STEPS], const float (&x)[3],
     if constexpr (NS % 2 == 1) {
         float sv, cv;
         const float mine = argument(NS - 1);
-        if constexpr (ABL & 1) { sv = mine; cv = mine + 1.0f; }
-        else sincosf(mine, &sv, &cv);
+        sincosf(mine, &sv, &cv);
         enc[NS - 1] = want_cos ? cv : sv;
     }
     enc[STEPS - 1] = g == 0 ? x[0] : (g == 1 ? x[1] : (g == 2 ? x[2] : 0.0f));
@@ -354,31 +310,26 @@ __device__ __forceinline__ SamplePD fetch_sample(const MlpArgs& args, int64_t si
 // ---- the fused forward kernel (TAPE: also records the activations the backward pass needs) ---------------
 // FLAT: the instantiation that also serves use_viewdirs = 0 networks (`density_only` == 2, see flat_head); a separate
 // instantiation so that the production kernels compile exactly as they did without it
-template <int H, int FX, int FD, int NW, int KCH, bool PIPE, bool KEEP_ENC, bool LBIAS, bool SPREAD, int ABL, bool TAPE, bool FLAT = false>
+template <int H, int FX, int FD, int NW, int KCH, bool TAPE, bool FLAT = false>
 // (occupancy: see mlp_kernel3 -- inference instances up to 128 wide are compiled for four waves per SIMD; the taping ones, whose
 // extra registers would all be spilled for it, measured no gain and stay at two)
 __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kernel(const MlpArgs args, const int num_layers,
                                                       const int density_only) {
     using N = Net<H, FX, FD, KCH>;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    // LBIAS: every bias of the network lives in LDS behind the ring for the whole launch (a bias fetched from
+    // every bias of the network lives in LDS behind the ring for the whole launch (a bias fetched from
     // L2 at the top of a layer is ~1 us of exposed latency in front of that layer's first MFMA)
     float* lds_bias = reinterpret_cast<float*>(lds + 2 * N::LDSBUF);
     const int nbias = H * (1 + num_layers) + H / 2 + 4;   // ... | fc_alpha.bias | fc_rgb.bias[3]
     float* lds_walpha = lds_bias + nbias;          // [4][H/4]
     float* lds_wrgb = lds_walpha + H;              // [3][4][H/8]
-    if constexpr (LBIAS) {
-        for (int i = threadIdx.x; i < nbias; i += NW * 64) lds_bias[i] = args.bias[i];
-        for (int i = threadIdx.x; i < H; i += NW * 64) lds_walpha[i] = args.walpha[i];
-        for (int i = threadIdx.x; i < ((FLAT && density_only == 2) ? 3 * H : 3 * H / 2); i += NW * 64) lds_wrgb[i] = args.wrgb[i];
-    }
-    const float* bias_src = LBIAS ? lds_bias : args.bias;
-    const float* walpha_src = LBIAS ? lds_walpha : args.walpha;
-    const float* wrgb_src = LBIAS ? lds_wrgb : args.wrgb;
+    for (int i = threadIdx.x; i < nbias; i += NW * 64) lds_bias[i] = args.bias[i];
+    for (int i = threadIdx.x; i < H; i += NW * 64) lds_walpha[i] = args.walpha[i];
+    for (int i = threadIdx.x; i < ((FLAT && density_only == 2) ? 3 * H : 3 * H / 2); i += NW * 64) lds_wrgb[i] = args.wrgb[i];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, col = lane & 15;
-    const float* tail_bias = bias_src + nbias - 4;
+    const float* tail_bias = lds_bias + nbias - 4;
 
     const int64_t wg_iters = (args.n + NW * 16 - 1) / (NW * 16);
     int par = 0;
@@ -395,26 +346,17 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
         const SamplePD smp = fetch_sample(args, sidx);
         const float p[3] = {smp.px, smp.py, smp.pz}, d[3] = {smp.dx, smp.dy, smp.dz};
         const float dummy[1] = {0.0f};
-        float encx_keep[KEEP_ENC ? N::EX : 1];
-        if constexpr (KEEP_ENC) encode<FX, N::EX, ABL>(encx_keep, p, args.bands_xyz, g);
-        if constexpr (KEEP_ENC && TAPE) store_encoding_row<FX, N::EX>((valid && args.tape_encx) ? args.tape_encx + sample * 64 : nullptr, encx_keep, g);
+        float encx[N::EX];   // kept in registers for the skip layer
+        encode<FX, N::EX>(encx, p, args.bands_xyz, g);
+        if constexpr (TAPE) store_encoding_row<FX, N::EX>((valid && args.tape_encx) ? args.tape_encx + sample * 64 : nullptr, encx, g);
 
         f32x4 acc[N::NT];
         float in[N::KH];
         __syncthreads();  // first chunk of layer1 resident (its DMA was issued one tile earlier)
 
         // ---- layer1: xyz_enc -> H, no activation (models.py:62)
-        load_bias<N::NT>(acc, bias_src, g);
-        if constexpr (KEEP_ENC) {
-            gemm_stage<N::NT, N::EX, 0, NW, N::LDSBUF, KCH, PIPE, SPREAD, ABL>(acc, encx_keep, dummy, gw, gw + N::EX * N::STEP,
-                                                                   N::LDSBUF, lds, par, wave, lane);
-        } else {   // the encoding registers live only for this stage; the skip layer recomputes them
-            float encx[N::EX];
-            encode<FX, N::EX, ABL>(encx, p, args.bands_xyz, g);
-            if constexpr (TAPE) store_encoding_row<FX, N::EX>((valid && args.tape_encx) ? args.tape_encx + sample * 64 : nullptr, encx, g);
-            gemm_stage<N::NT, N::EX, 0, NW, N::LDSBUF, KCH, PIPE, SPREAD, ABL>(acc, encx, dummy, gw, gw + N::EX * N::STEP, N::LDSBUF,
-                                                                   lds, par, wave, lane);
-        }
+        load_bias<N::NT>(acc, lds_bias, g);
+        gemm_stage<N::NT, N::EX, 0, NW, N::LDSBUF, KCH>(acc, encx, dummy, gw, gw + N::EX * N::STEP, N::LDSBUF, lds, par, wave, lane);
         gw += N::EX * N::STEP;
         acc_to_operand<N::NT, false>(acc, in);
         const int64_t tile = it * NW + wave;
@@ -428,17 +370,17 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
 #pragma unroll 1
         for (int i = 0; i < trunk_iters; ++i) {
             const bool is_feat = i == num_layers - 1;
-            if (is_feat) sigma = alpha_gemv<H>(in, walpha_src, g) + tail_bias[0];   // on the pre-feature activation
+            if (is_feat) sigma = alpha_gemv<H>(in, lds_walpha, g) + tail_bias[0];   // on the pre-feature activation
             const bool skip = !is_feat && ((args.skip_mask >> i) & 1u);
             const bool last_density = density_only && i == num_layers - 2;
-            load_bias<N::NT>(acc, bias_src + H * (1 + i), g);
+            load_bias<N::NT>(acc, lds_bias + H * (1 + i), g);
             {
                 const char* tsrc = gw + N::KH * N::STEP;
                 int tbytes = N::LDSBUF;
                 if (skip) tbytes = N::L1_FIRST;               // the skip layer's encoding columns follow
                 else if (is_feat) tbytes = N::DIR_FIRST;      // view layer follows
                 else if (last_density) { tsrc = args.wstream; tbytes = has_next ? N::L1_FIRST : 0; }
-                gemm_stage<N::NT, N::KH, 0, NW, N::LDSBUF, KCH, PIPE, SPREAD, ABL, TAPE>(
+                gemm_stage<N::NT, N::KH, 0, NW, N::LDSBUF, KCH, TAPE>(
                     acc, in, dummy, gw, tsrc, tbytes, lds, par, wave, lane,
                     (tape_row && !(i == 0 && args.tape_skip_h0)) ? tape_row + (int64_t)i * args.n * H : nullptr);
                 gw += N::KH * N::STEP;
@@ -447,13 +389,7 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
                 const char* tsrc = gw + N::EX * N::STEP;
                 int tbytes = N::LDSBUF;
                 if (last_density) { tsrc = args.wstream; tbytes = has_next ? N::L1_FIRST : 0; }
-                if constexpr (KEEP_ENC) {
-                    gemm_stage<N::NT, N::EX, 0, NW, N::LDSBUF, KCH, PIPE, SPREAD, ABL>(acc, encx_keep, dummy, gw, tsrc, tbytes, lds, par, wave, lane);
-                } else {
-                    float encx[N::EX];
-                    encode<FX, N::EX, ABL>(encx, p, args.bands_xyz, g);
-                    gemm_stage<N::NT, N::EX, 0, NW, N::LDSBUF, KCH, PIPE, SPREAD, ABL>(acc, encx, dummy, gw, tsrc, tbytes, lds, par, wave, lane);
-                }
+                gemm_stage<N::NT, N::EX, 0, NW, N::LDSBUF, KCH>(acc, encx, dummy, gw, tsrc, tbytes, lds, par, wave, lane);
                 gw += N::EX * N::STEP;
             }
             acc_to_operand<N::NT, true>(acc, in);
@@ -463,9 +399,9 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
         }
 
         if (density_only) {
-            sigma = alpha_gemv<H>(in, walpha_src, g) + tail_bias[0];
+            sigma = alpha_gemv<H>(in, lds_walpha, g) + tail_bias[0];
             if (FLAT && density_only == 2) {   // use_viewdirs = 0
-                flat_head<H>(args, in, wrgb_src, tail_bias, sigma, sample, valid, g);
+                flat_head<H>(args, in, lds_wrgb, tail_bias, sigma, sample, valid, g);
                 // TAPE: the trunk's last activation has no stage behind it that would write it while consuming it
                 if constexpr (TAPE) store_rows<N::NT>(args.tape_h + (int64_t)(num_layers - 1) * args.n * H, H, sample, valid, in, g);
             } else if (valid && g == 0) args.out[sample] = sigma;
@@ -476,11 +412,11 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
         // ---- layers_dir[0]: cat(feat, dir_enc) -> H/2, relu (models.py:72-74)
         f32x4 accd[N::NTD];
         float v[N::KD];
-        load_bias<N::NTD>(accd, bias_src + H * (1 + num_layers), g);
+        load_bias<N::NTD>(accd, lds_bias + H * (1 + num_layers), g);
         float encd[N::ED];
-        encode<FD, N::ED, ABL>(encd, d, args.bands_dir, g);
+        encode<FD, N::ED>(encd, d, args.bands_dir, g);
         if constexpr (TAPE) store_encoding_row<FD, N::ED>((valid && args.tape_encd) ? args.tape_encd + sample * 64 : nullptr, encd, g);
-        gemm_stage<N::NTD, N::KH, N::ED, NW, N::LDSBUF, KCH, PIPE, SPREAD, ABL, TAPE>(
+        gemm_stage<N::NTD, N::KH, N::ED, NW, N::LDSBUF, KCH, TAPE>(
             accd, in, encd, gw, args.wstream, has_next ? N::L1_FIRST : 0, lds, par, wave, lane,
             (TAPE && valid) ? args.tape_feat + sample * H + 4 * g : nullptr);
         gw = args.wstream;
@@ -495,7 +431,7 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             float part = 0.0f;
-            const float* wr = wrgb_src + (ch * 4 + g) * N::KD;
+            const float* wr = lds_wrgb + (ch * 4 + g) * N::KD;
 #pragma unroll
             for (int s = 0; s < N::KD; s += 4) {
                 const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + s);

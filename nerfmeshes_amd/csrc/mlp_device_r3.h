@@ -27,15 +27,12 @@ struct NextChunks {          // the first two chunks of whatever stage runs next
 // operands of block j + 2 are fetched while block j runs (8 MFMAs = 256 matrix-pipe cycles of cover, 3 live operand
 // quads instead of round 1's 8), and the stream simply continues into the next chunk / the next stage: `carry` holds
 // blocks 0 and 1 of whatever comes next.
-// STAG: 0 every wave issues its DMA pieces at block 0 of a chunk | 1 waves 0..NW/2-1 at block 0, the others half a chunk
-// later.  ABL (timing-only ablations, ablation library): 1 barriers do not wait for the DMA | 2 no DMA | 4 one lane per
-// DMA instruction | 8 round-1 DMA form (global_load_lds with per-lane address VGPRs).
-// STORE (training): b1 is written to `store_row` a few tiles per chunk while the stage consumes it (see gemm_stage).
-template <int NT, int KS1, int KS2, int NW, int LDSBUF, int KCH, int STAG, int ABL = 0, bool STORE = false>
+// Waves 0..NW/2-1 issue their DMA pieces at block 0 of a chunk, the others half a chunk later.
+template <int NT, int KS1, int KS2, int NW, int LDSBUF, int KCH>
 __device__ __forceinline__ void gemm_stage3(f32x4 (&acc)[NT], const float (&b1)[KS1],
                                             const float (&b2)[(KS2 > 0 ? KS2 : 1)], const char* gw,
                                             const NextChunks nx, char* lds, int& slot, f32x4 (&carry)[2],
-                                            int wave, int lane, float* store_row = nullptr) {
+                                            int wave, int lane) {
     constexpr int KS = KS1 + KS2;
     constexpr int NCH = (KS + KCH - 1) / KCH;
     constexpr int NB = NT / 4;
@@ -61,37 +58,10 @@ __device__ __forceinline__ void gemm_stage3(f32x4 (&acc)[NT], const float (&b1)[
         char* dst = lds + slot2 * LDSBUF;
         const char* buf = lds + slot * LDSBUF + lane * 16;
         const char* nbuf = lds + slot1 * LDSBUF + lane * 16;
-        if constexpr (STORE) {
-            constexpr int TILES = KS1 / 4, PER_CHUNK = (TILES + NCH - 1) / NCH;
-            if (store_row) {
-#pragma unroll
-                for (int q = 0; q < PER_CHUNK; ++q) {
-                    const int nt = c * PER_CHUNK + q;
-                    if (nt < TILES) {
-                        const f32x4 v4 = {b1[4 * nt], b1[4 * nt + 1], b1[4 * nt + 2], b1[4 * nt + 3]};
-                        *reinterpret_cast<f32x4*>(store_row + 16 * nt) = v4;
-                    }
-                }
-            }
-        }
 #pragma unroll
         for (int j = 0; j < nblk; ++j) {
-            auto dma = [&]() {
-                if constexpr (ABL & 8) stream_to_lds_vaddr<NW>(src, dst, bytes, wave, lane);
-                else stream_to_lds<NW>(src, dst, bytes, wave, lane);
-            };
-            if constexpr (ABL & 2) {
-            } else if constexpr (ABL & 4) {   // timing only: the same instruction sequence moving 16 B instead of 1 KiB per piece
-                if (lane == 0) {
-                    if (j == 0 && wave < NW / 2) stream_to_lds_vaddr<NW>(src, dst, bytes, wave, lane);
-                    if (j == nblk / 2 && wave >= NW / 2) stream_to_lds_vaddr<NW>(src, dst, bytes, wave, lane);
-                }
-            } else if constexpr (STAG == 1) {
-                if (j == 0 && wave < NW / 2) dma();
-                if (j == nblk / 2 && wave >= NW / 2) dma();
-            } else {
-                if (j == 0) dma();
-            }
+            if (j == 0 && wave < NW / 2) stream_to_lds<NW>(src, dst, bytes, wave, lane);
+            if (j == nblk / 2 && wave >= NW / 2) stream_to_lds<NW>(src, dst, bytes, wave, lane);
             const int ks = j / NB, blk = j % NB;
             const int s = c * KCH + ks;
             const float b = s < KS1 ? b1[s < KS1 ? s : 0] : b2[s >= KS1 ? s - KS1 : 0];
@@ -104,8 +74,7 @@ __device__ __forceinline__ void gemm_stage3(f32x4 (&acc)[NT], const float (&b1)[
             for (int q = 0; q < 4; ++q)
                 acc[blk * 4 + q] = __builtin_amdgcn_mfma_f32_16x16x4f32(ab[r0][q], b, acc[blk * 4 + q], 0, 0, 0);
         }
-        if constexpr (ABL & 1) __builtin_amdgcn_s_barrier();   // timing-only: no wait for the DMA (results WRONG)
-        else __syncthreads();   // this wave's DMA pieces have landed (vmcnt(0)); after it the chunk after next is visible to all
+        __syncthreads();   // this wave's DMA pieces have landed (vmcnt(0)); after it the chunk after next is visible to all
         slot = slot1;
     }
     constexpr int TOTAL = KS * NB;                           // blocks consumed: the two in flight sit at TOTAL, TOTAL + 1
@@ -113,15 +82,14 @@ __device__ __forceinline__ void gemm_stage3(f32x4 (&acc)[NT], const float (&b1)[
     carry[1] = ab[(TOTAL + 1) % 3];
 }
 
-// TAPE (EXPERIMENT, instantiated in the ablation library only -- nerf_train.hip, NM_MLP_VARIANT=3): the taping forward on this
-// dataflow, writing the same tape as mlp_kernel<..., TAPE> (activation rows while the next stage consumes them, ReLU bit masks
-// per tile), the same bits.  Measured 4.7 % SLOWER than the 2-slot taping kernel (3.54 vs 3.38 ms per 393 216 samples of the
-// 8x256 network, profiles/r04_train_three_slot.json): the training kernels stay on mlp_device.h's dataflow.
-template <int H, int FX, int FD, int NW, int KCH, int STAG, int ABL = 0, bool FLAT = false, bool TAPE = false>   // FLAT: see mlp_kernel
+// Inference only.  The taping forward on this dataflow was built, wrote the same tape bit for bit and measured 4.7 % SLOWER than
+// the 2-slot taping kernel (3.54 vs 3.38 ms per 393 216 samples of the 8x256 network, profiles/r04_train_three_slot.json; source
+// last present in 94bb324): the training kernels stay on mlp_device.h's dataflow.
+template <int H, int FX, int FD, int NW, int KCH, bool FLAT = false>   // FLAT: see mlp_kernel
 // Occupancy: networks up to 128 wide are compiled for FOUR waves per SIMD (128 registers: two 8-wave workgroups per CU; the
 // 128-wide instances spill 9 -- 17 registers outside the k-step loops for it).  With VALU issue time adding to matrix time on
 // narrow networks two more waves per SIMD are worth +2.7 points at 8x128 (0.875 -> 0.902, same bits).
-__global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kernel3(const MlpArgs args, const int num_layers,
+__global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const MlpArgs args, const int num_layers,
                                                           const int density_only) {
     using N = Net<H, FX, FD, KCH>;
     static_assert(N::EX > KCH && N::KH >= 2 * KCH, "stages must span two chunks");
@@ -168,7 +136,7 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
         const float p[3] = {smp.px, smp.py, smp.pz}, d[3] = {smp.dx, smp.dy, smp.dz};
         const float dummy[1] = {0.0f};
         float encx[N::EX];
-        encode<FX, N::EX, 0>(encx, p, args.bands_xyz, g);
+        encode<FX, N::EX>(encx, p, args.bands_xyz, g);
         const NextChunks wrap = enc_next(args.wstream, has_next);
 
         f32x4 acc[N::NT];
@@ -176,12 +144,9 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
         const char* gw = args.wstream;
         // ---- layer1: xyz_enc -> H, no activation (models.py:62)
         load_bias<N::NT>(acc, lds_bias, g);
-        gemm_stage3<N::NT, N::EX, 0, NW, N::LDSBUF, KCH, STAG, ABL>(acc, encx, dummy, gw, hidden_next(gw + N::EX * N::STEP), lds,
-                                                              slot, carry, wave, lane);
+        gemm_stage3<N::NT, N::EX, 0, NW, N::LDSBUF, KCH>(acc, encx, dummy, gw, hidden_next(gw + N::EX * N::STEP), lds, slot, carry, wave, lane);
         gw += N::EX * N::STEP;
         acc_to_operand<N::NT, false>(acc, in);
-        const int64_t tile = it * NW + wave;
-        float* tape_row = (TAPE && valid) ? args.tape_h + sample * H + 4 * g : nullptr;
 
         // ---- layers_xyz[0 .. L-2], then (full evaluation only) fc_feat as iteration L-1 (models.py:63-70)
         float sigma = 0.0f;
@@ -199,29 +164,22 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
                 if (skip) nx = enc_next(after, true);
                 else if (is_feat) nx = dir_next(after);
                 else if (last_density) nx = wrap;
-                gemm_stage3<N::NT, N::KH, 0, NW, N::LDSBUF, KCH, STAG, ABL, TAPE>(acc, in, dummy, gw, nx, lds, slot, carry, wave, lane,
-                                                                                 tape_row ? tape_row + (int64_t)i * args.n * H : nullptr);
+                gemm_stage3<N::NT, N::KH, 0, NW, N::LDSBUF, KCH>(acc, in, dummy, gw, nx, lds, slot, carry, wave, lane);
                 gw = after;
             }
             if (skip) {  // cat(hidden, xyz_enc): the encoding columns of layers_xyz[i] (models.py:64-65)
                 const char* after = gw + N::EX * N::STEP;
                 const NextChunks nx = last_density ? wrap : hidden_next(after);
-                gemm_stage3<N::NT, N::EX, 0, NW, N::LDSBUF, KCH, STAG, ABL>(acc, encx, dummy, gw, nx, lds, slot, carry, wave, lane);
+                gemm_stage3<N::NT, N::EX, 0, NW, N::LDSBUF, KCH>(acc, encx, dummy, gw, nx, lds, slot, carry, wave, lane);
                 gw = after;
             }
             acc_to_operand<N::NT, true>(acc, in);
-            if constexpr (TAPE) {
-                if (tile < args.tiles) args.mask_h[((int64_t)i * args.tiles + tile) * 64 + lane] = positive_mask(in);
-            }
         }
 
         if (density_only) {
             sigma = alpha_gemv<H>(in, lds_walpha, g) + tail_bias[0];
-            if (FLAT && density_only == 2) {   // use_viewdirs = 0
-                flat_head<H>(args, in, lds_wrgb, tail_bias, sigma, sample, valid, g);
-                // TAPE: the trunk's last activation has no stage behind it that would write it while consuming it
-                if constexpr (TAPE) store_rows<N::NT>(args.tape_h + (int64_t)(num_layers - 1) * args.n * H, H, sample, valid, in, g);
-            } else if (valid && g == 0) args.out[sample] = sigma;
+            if (FLAT && density_only == 2) flat_head<H>(args, in, lds_wrgb, tail_bias, sigma, sample, valid, g);   // use_viewdirs = 0
+            else if (valid && g == 0) args.out[sample] = sigma;
             continue;
         }
 
@@ -230,14 +188,9 @@ __global__ __launch_bounds__(NW * 64, (H <= 128 && !TAPE) ? 4 : 2) void mlp_kern
         float v[N::KD];
         load_bias<N::NTD>(accd, lds_bias + H * (1 + num_layers), g);
         float encd[N::ED];
-        encode<FD, N::ED, 0>(encd, d, args.bands_dir, g);
-        gemm_stage3<N::NTD, N::KH, N::ED, NW, N::LDSBUF, KCH, STAG, ABL, TAPE>(accd, in, encd, gw, wrap, lds, slot, carry, wave, lane,
-                                                                             (TAPE && valid) ? args.tape_feat + sample * H + 4 * g : nullptr);
+        encode<FD, N::ED>(encd, d, args.bands_dir, g);
+        gemm_stage3<N::NTD, N::KH, N::ED, NW, N::LDSBUF, KCH>(accd, in, encd, gw, wrap, lds, slot, carry, wave, lane);
         acc_to_operand<N::NTD, true>(accd, v);
-        if constexpr (TAPE) {
-            store_rows<N::NTD>(args.tape_v, args.tape_v_ld, sample, valid, v, g);
-            if (tile < args.tiles) args.mask_v[tile * 64 + lane] = positive_mask(v);
-        }
 
         // ---- fc_rgb + sigmoid (models.py:75), 3-row GEMV on the VALU
         float rgb[3];

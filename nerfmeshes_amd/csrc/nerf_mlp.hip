@@ -26,8 +26,6 @@
 //
 // Roofline: MFMA (fp32 matrix peak 157.3 TFLOP/s).  593 408 MAC per sample for the 8x256 net; the
 // kernel issues 9 280 MFMAs (1 024 MAC each) per 16-sample tile = 99.9 % useful work.
-#include <stdlib.h>
-
 #include <iterator>
 #include <vector>
 
@@ -36,73 +34,40 @@
 #include "mlp_device_r3.h"
 #include "mlp_device_b3.h"
 #include "mlp_device_g.h"
-#ifdef NM_ABLATIONS
-#include "mlp_device_g2.h"
-#include "mlp_device_b3w.h"
-#endif
 
 namespace nm {
 
-
 // ---- host side: plan table + launcher ------------------------------------------------------
-template <int H, int FX, int FD, int NW, int KCH, bool PIPE, bool KEEP_ENC, bool LBIAS, bool SPREAD = false, int ABL = 0>
-static MlpPlan make_plan(int variant) {
-    return MlpPlan{H, FX, FD, NW, KCH, variant, 2 * Net<H, FX, FD, KCH>::LDSBUF, LBIAS,
-                   &mlp_kernel<H, FX, FD, NW, KCH, PIPE, KEEP_ENC, LBIAS, SPREAD, ABL, false>, NW * 16, 8 / NW,
-                   (ABL == 0 && LBIAS) ? &mlp_kernel<H, FX, FD, NW, KCH, PIPE, KEEP_ENC, LBIAS, SPREAD, ABL, false, true> : nullptr, 0,
-                   nullptr, nullptr};
+template <int H, int FX, int FD, int NW, int KCH>
+static MlpPlan make_plan() {
+    return MlpPlan{H, FX, FD, NW, KCH, 0, 2 * Net<H, FX, FD, KCH>::LDSBUF, &mlp_kernel<H, FX, FD, NW, KCH, false>,
+                   NW * 16, 8 / NW, &mlp_kernel<H, FX, FD, NW, KCH, false, true>, 0, nullptr, nullptr};
 }
 
-template <int H, int FX, int FD, int NW, int KCH, int STAG, int ABL = 0>
-static MlpPlan make_plan3(int variant) {
-    return MlpPlan{H, FX, FD, NW, KCH, variant, 3 * Net<H, FX, FD, KCH>::LDSBUF, true, &mlp_kernel3<H, FX, FD, NW, KCH, STAG, ABL>,
-                   NW * 16, 8 / NW, ABL == 0 ? &mlp_kernel3<H, FX, FD, NW, KCH, STAG, ABL, true> : nullptr, 0, nullptr, nullptr};
+template <int H, int FX, int FD, int NW, int KCH>
+static MlpPlan make_plan3() {
+    return MlpPlan{H, FX, FD, NW, KCH, 0, 3 * Net<H, FX, FD, KCH>::LDSBUF, &mlp_kernel3<H, FX, FD, NW, KCH>,
+                   NW * 16, 8 / NW, &mlp_kernel3<H, FX, FD, NW, KCH, true>, 0, nullptr, nullptr};
 }
 
-// variant 0 is the production choice and the ONLY one in libnerfmeshes_hip.so.  The others exist for within-process
-// A/B runs (scripts/bench_mlp.py) and are compiled only with -DNM_ABLATIONS into a separate library
-// (libnerfmeshes_hip_ablations.so, `python -m nerfmeshes_amd.build --ablations`), where NM_MLP_VARIANT=<n> selects
-// them; the product library never reads that variable, so an inherited environment cannot change its results.
+// One plan per tuned shape.  The A/B variants of rounds 1 -- 5 that used to sit next to them (profiles/r0*_mlp_variants.json,
+// DESIGN.md 3.1) were measured and retired: source last present in 94bb324.
 static const MlpPlan g_tuned_plans[] = {
     // production: the round-2 kernel (3-slot ring, operand stream across boundaries, staggered scalar-addressed DMA)
     // for the 256- and 128-wide networks; 64-wide networks (2-tile view layer) keep the round-1 dataflow
-    make_plan3<256, 10, 4, 8, 8, 1>(0),
-    make_plan3<128, 10, 4, 8, 8, 1>(0),
-    make_plan<64, 10, 4, 8, 8, true, true, true>(0),
-    make_plan3<256, 6, 4, 8, 8, 1>(0),
-    make_plan3<128, 6, 4, 8, 8, 1>(0),
-    make_plan<64, 6, 4, 8, 8, true, true, true>(0),
-#ifdef NM_ABLATIONS
-    // round 1 (profiles/r01_mlp_variants.json; all with the round-1 DMA form, ABL bit 8): v10 = round-1 production 141.1
-    make_plan<256, 10, 4, 8, 8, true, true, true, false, 8>(10),
-    make_plan<256, 10, 4, 8, 16, true, true, true, false, 8>(1),     // 16-k-step chunks: 137.6
-    make_plan<256, 10, 4, 8, 8, false, true, false, false, 8>(2),    // round-1 first version (no prefetch, L2 biases): 133.7
-    make_plan<256, 10, 4, 8, 8, true, false, true, false, 8>(3),     // encodings recomputed at the skip layer: ~135
-    make_plan<256, 10, 4, 8, 8, true, true, false, false, 8>(4),     // prefetch only, biases from L2: 138.3
-    make_plan<256, 10, 4, 4, 8, true, true, true, false, 8>(5),      // 4-wave workgroups, two per CU (decoupled barriers): 132.3
-    make_plan<256, 10, 4, 4, 8, true, true, true>(6),                // ... with the scalar-addressed DMA: 143.4 (= variant 9: decoupling buys nothing)
-    // timing-only ablations (WRONG results): 1 = no sincos, 2 = no barrier, 4 = no weight DMA
-    make_plan<256, 10, 4, 8, 8, true, true, true, false, 1>(11),
-    make_plan<256, 10, 4, 8, 8, true, true, true, false, 2>(12),
-    make_plan<256, 10, 4, 8, 8, true, true, true, false, 4>(14),
-    make_plan<256, 10, 4, 8, 8, true, true, true, false, 6>(16),
-    make_plan<256, 10, 4, 8, 8, true, true, true, false, 7>(17),
-    // round 2 (profiles/r02_mlp_variants.json): 3-slot ring, DMA two chunks ahead, operand stream across boundaries
-    make_plan<256, 10, 4, 8, 8, true, true, true>(9),  // round-1 dataflow (2-slot ring) with the scalar-addressed DMA
-    make_plan3<256, 10, 4, 8, 8, 0>(21),        // all waves at block 0
-    make_plan3<256, 10, 4, 8, 8, 1, 8>(31),     // v20 with the round-1 DMA form (address VGPRs)
-    make_plan3<256, 10, 4, 8, 8, 1, 8 | 1>(22), // timing only (WRONG results): ... barriers do not wait for the DMA
-    make_plan3<256, 10, 4, 8, 8, 1, 2>(23),     // timing only (WRONG results): no weight DMA at all
-    make_plan3<256, 10, 4, 8, 8, 1, 4>(42),     // timing only (WRONG results): round-1 DMA form issued for one lane
-#endif
+    make_plan3<256, 10, 4, 8, 8>(),
+    make_plan3<128, 10, 4, 8, 8>(),
+    make_plan<64, 10, 4, 8, 8>(),
+    make_plan3<256, 6, 4, 8, 8>(),
+    make_plan3<128, 6, 4, 8, 8>(),
+    make_plan<64, 6, 4, 8, 8>(),
 };
 
-// the generic-shape family (mlp_device_g.h), instantiated in nerf_mlp_generic_{a..e}.hip, in ascending width
+// the generic-shape family (mlp_device_g.h), instantiated in nerf_mlp_generic_{a..d,s}.hip, in ascending width
 void generic_plans_a(std::vector<MlpPlan>&);
 void generic_plans_b(std::vector<MlpPlan>&);
 void generic_plans_c(std::vector<MlpPlan>&);
 void generic_plans_d(std::vector<MlpPlan>&);
-void generic_plans_e(std::vector<MlpPlan>&);
 void generic_plans_s(std::vector<MlpPlan>&);
 void generic_plans_a_long(std::vector<MlpPlan>&);      // the same classes with two-part encoding stages (variant G_LONG_VARIANT)
 void generic_plans_b_long(std::vector<MlpPlan>&);
@@ -114,18 +79,8 @@ void generic_plans_s_long_upper(std::vector<MlpPlan>&);
 static const std::vector<MlpPlan>& all_plans() {
     static const std::vector<MlpPlan> plans = [] {
         std::vector<MlpPlan> v(std::begin(g_tuned_plans), std::end(g_tuned_plans));
-        generic_plans_a(v); generic_plans_b(v); generic_plans_c(v); generic_plans_d(v); generic_plans_s(v); generic_plans_e(v);
+        generic_plans_a(v); generic_plans_b(v); generic_plans_c(v); generic_plans_d(v); generic_plans_s(v);
         generic_plans_a_long(v); generic_plans_b_long(v); generic_plans_c_long(v); generic_plans_d_long(v); generic_plans_s_long(v); generic_plans_s_long_upper(v);
-#ifdef NM_ABLATIONS
-        // experiment (NM_MLP_VARIANT=200 + NM_KERNEL_GENERIC): two 16-sample column tiles per wave (mlp_device_g2.h)
-        // (round 5: also the classes of 2 and 3 tiles -- VERDICT r4 item 7 -- compiled for four waves per SIMD (200) and two (201))
-        v.push_back(MlpPlan{32, -1, -1, 8, 8, 200, 2 * 8 * 1024, true, &mlp_kernel_g2<2, 8, 8, 4>, 8 * 32, 1, nullptr, 2, nullptr, nullptr});
-        v.push_back(MlpPlan{48, -1, -1, 8, 8, 200, 2 * 8 * 1024, true, &mlp_kernel_g2<3, 8, 8, 4>, 8 * 32, 1, nullptr, 3, nullptr, nullptr});
-        v.push_back(MlpPlan{32, -1, -1, 8, 8, 201, 2 * 8 * 1024, true, &mlp_kernel_g2<2, 8, 8, 2>, 8 * 32, 1, nullptr, 2, nullptr, nullptr});
-        v.push_back(MlpPlan{48, -1, -1, 8, 8, 201, 2 * 8 * 1024, true, &mlp_kernel_g2<3, 8, 8, 2>, 8 * 32, 1, nullptr, 3, nullptr, nullptr});
-        v.push_back(MlpPlan{64, -1, -1, 8, 8, 200, 2 * 8 * 1024, true, &mlp_kernel_g2<4, 8, 8>, 8 * 32, 1, nullptr, 4, nullptr, nullptr});
-        v.push_back(MlpPlan{128, -1, -1, 8, 8, 200, 2 * 8 * 2 * 1024, true, &mlp_kernel_g2<8, 8, 8>, 8 * 32, 1, nullptr, 8, nullptr, nullptr});
-#endif
         return v;
     }();
     return plans;
@@ -135,23 +90,17 @@ static const std::vector<MlpPlan>& all_plans() {
 struct B3Plan {
     int H, FX, FD;
     void (*kernel)(const MlpArgs, const int, const int);
-    void (*kernel_w)(const MlpArgs, const int, const int);      // ablation library: two column tiles per wave (mlp_device_b3w.h)
     int chunk_units;                                            // units per ring slot (a stage must span two chunks)
 };
 static const B3Plan g_b3_plans[] = {
-#ifdef NM_ABLATIONS
-    {256, 10, 4, &mlp_kernel_b3<256, 10, 4, 8>, &mlp_kernel_b3w<256, 10, 4, 4>, B3_CHUNK_UNITS},
-    {256, 6, 4, &mlp_kernel_b3<256, 6, 4, 8>, &mlp_kernel_b3w<256, 6, 4, 4>, B3_CHUNK_UNITS},
-#else
-    {256, 10, 4, &mlp_kernel_b3<256, 10, 4, 8>, nullptr, B3_CHUNK_UNITS},
-    {256, 6, 4, &mlp_kernel_b3<256, 6, 4, 8>, nullptr, B3_CHUNK_UNITS},
-#endif
+    {256, 10, 4, &mlp_kernel_b3<256, 10, 4, 8>, B3_CHUNK_UNITS},
+    {256, 6, 4, &mlp_kernel_b3<256, 6, 4, 8>, B3_CHUNK_UNITS},
     // round 5: the narrower shipped shapes (the fern configs' 8x128, config 1's 4x64): smaller chunks so that every stage still
     // spans two of them; the same kernel otherwise
-    {128, 10, 4, &mlp_kernel_b3<128, 10, 4, 8, 8>, nullptr, 8},
-    {128, 6, 4, &mlp_kernel_b3<128, 6, 4, 8, 8>, nullptr, 8},
-    {64, 10, 4, &mlp_kernel_b3<64, 10, 4, 8, 3>, nullptr, 3},
-    {64, 6, 4, &mlp_kernel_b3<64, 6, 4, 8, 3>, nullptr, 3},
+    {128, 10, 4, &mlp_kernel_b3<128, 10, 4, 8, 8>, 8},
+    {128, 6, 4, &mlp_kernel_b3<128, 6, 4, 8, 8>, 8},
+    {64, 10, 4, &mlp_kernel_b3<64, 10, 4, 8, 3>, 3},
+    {64, 6, 4, &mlp_kernel_b3<64, 6, 4, 8, 3>, 3},
 };
 static const B3Plan* find_b3_plan(int H, int FX, int FD) {
     for (const B3Plan& p : g_b3_plans)
@@ -164,28 +113,16 @@ bool has_b3_kernel(int H, int FX, int FD) { return find_b3_plan(H, FX, FD) != nu
 // tuned kernels' identity k-step assumes is laid out -- its weights may still be zero); otherwise the narrowest class of
 // the generic family that holds the network; null only beyond the family's limits (mlp_api.hip says which).
 const MlpPlan* find_mlp_plan(int H, int FX, int FD) {
-    int want = 0;
-#ifdef NM_ABLATIONS
-    if (const char* v = getenv("NM_MLP_VARIANT")) want = atoi(v);
-#endif
-    const MlpPlan* fallback = nullptr;
     for (const MlpPlan& p : all_plans())
-        if (!p.generic_nt && p.H == H && p.FX == FX && p.FD == FD) {
-            if (p.variant == want) return &p;
-            if (p.variant == 0) fallback = &p;
-        }
-    return fallback;
+        if (!p.generic_nt && p.H == H && p.FX == FX && p.FD == FD) return &p;
+    return nullptr;
 }
 
 // the narrowest class of the generic family that holds hidden_size H and whose LDS image (weight ring + every bias of an L-layer
 // network + heads + tables) fits a CU; `long_encoding`: an encoding of more than G_ENC_STEPS k-steps (16 -- 31 functions) -- the
 // instantiations with two-part encoding stages.  Null if there is none (the caller then takes the layer-wise path).
 const MlpPlan* find_generic_plan(int H, int L, bool long_encoding) {
-    int want = long_encoding ? G_LONG_VARIANT : 0;
-#ifdef NM_ABLATIONS
-    if (const char* v = getenv("NM_MLP_VARIANT"))
-        if (!long_encoding) want = (atoi(v) == 200 || atoi(v) == 201 || atoi(v) == 310) ? atoi(v) : 0;
-#endif
+    const int want = long_encoding ? G_LONG_VARIANT : 0;
     for (const MlpPlan& p : all_plans())
         if (p.generic_nt && p.variant == want && p.H >= H && forward_lds_bytes(p, H, L, 0) <= 160 * 1024) return &p;
     return nullptr;
@@ -199,7 +136,7 @@ int mlp_plan_info(const MlpPlan* p, int* nw) {
 int forward_lds_bytes(const MlpPlan& p, int H, int L, int head_floats) {
     if (p.generic_nt)      // padded widths, both head layouts, the two argument tables (mlp_device_g.h)
         return g_lds_bytes(p.ring_bytes, p.generic_nt, L, p.variant == G_LONG_VARIANT ? G_ENC_PARTS : 1);
-    return p.ring_bytes + (p.lds_bias ? tuned_cache_bytes(H, L, head_floats) : 0);
+    return p.ring_bytes + tuned_cache_bytes(H, L, head_floats);
 }
 
 int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream_t stream) {
@@ -216,10 +153,6 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream
         NM_REQUIRE(lds_bytes <= 160 * 1024, "LDS budget exceeded (bf16x3 ring + bias cache): too many layers");
         auto b3_kernel = b->kernel;
         unsigned b3_threads = 512;
-#ifdef NM_ABLATIONS
-        if (const char* v = getenv("NM_MLP_VARIANT"))       // experiment: 4 waves x 32 samples, the same 128-sample workgroup
-            if (atoi(v) == 300) { b3_kernel = b->kernel_w; b3_threads = 256; }
-#endif
         if (int rc = ensure_dynamic_lds((const void*)b3_kernel, lds_bytes)) return rc;
         MlpArgs a = args;
         a.wstream = static_cast<const char*>(m->d_stream_b3);

@@ -26,7 +26,7 @@ static MlpPlan generic_plan() {
     static_assert(NT <= 24, "wider classes: nerf_mlp_generic_s.hip");
     constexpr int NW = 8, KCH = 8;            // two waves per SIMD; ring slots of at most 48 KiB
     constexpr int SLOT = KCH * ((NT + 3) / 4) * 1024;
-    return MlpPlan{16 * NT, -1, -1, NW, KCH, kLong ? G_LONG_VARIANT : 0, 2 * SLOT, true, &mlp_kernel_g<NT, NW, KCH, false, kLong>, NW * 16, 1,
+    return MlpPlan{16 * NT, -1, -1, NW, KCH, kLong ? G_LONG_VARIANT : 0, 2 * SLOT, &mlp_kernel_g<NT, NW, KCH, false, kLong>, NW * 16, 1,
                    &mlp_kernel_g<NT, NW, KCH, false, kLong>, NT, &mlp_kernel_g<NT, NW, KCH, true, kLong>, &mlp_backward_kernel_g<NT, NW, KCH>};
 }
 

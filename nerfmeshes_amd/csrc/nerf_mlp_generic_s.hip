@@ -24,7 +24,7 @@ template <int NT>
 static MlpPlan split_plan() {
     constexpr int KCH = 4;                    // one input tile per chunk (the exchange schedule of mlp_device_gs.h)
     constexpr int SLOT = KCH * ((NT + 3) / 4) * 1024;
-    return MlpPlan{16 * NT, -1, -1, 2 * GS_PAIRS, KCH, kLong ? G_LONG_VARIANT : 0, 2 * SLOT + GS_EXTRA_BYTES, true, &mlp_kernel_gs<NT, KCH, false, kLong>, GS_PAIRS * 16, 1,
+    return MlpPlan{16 * NT, -1, -1, 2 * GS_PAIRS, KCH, kLong ? G_LONG_VARIANT : 0, 2 * SLOT + GS_EXTRA_BYTES, &mlp_kernel_gs<NT, KCH, false, kLong>, GS_PAIRS * 16, 1,
                    &mlp_kernel_gs<NT, KCH, false, kLong>, NT, &mlp_kernel_gs<NT, KCH, true, kLong>, &mlp_backward_kernel_gs<NT, KCH>};
 }
 

@@ -17,10 +17,6 @@
 
 #include "nm_internal.h"
 #include "mlp_device.h"
-#ifdef NM_ABLATIONS
-#include <cstdlib>
-#include "mlp_device_r3.h"
-#endif
 #include "mlp_device_g.h"
 #include "nerf_layerwise.h"
 
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_backward_kernel
 #pragma unroll
             for (int nt = 0; nt < N::NT; ++nt) acc[nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             const uint64_t m = tile_ok ? mrow[(int64_t)(L - 1) * mstride] : 0;
-            gemm_stage<N::NT, N::KD, 0, NW, N::LDSBUF, KCH, true, false, 0, true>(
+            gemm_stage<N::NT, N::KD, 0, NW, N::LDSBUF, KCH, true>(
                 acc, dv, dummy, gw, gw + N::KD * N::STEP, N::LDSBUF, lds, par, wave, lane,
                 valid ? args.d_v + sample * (H / 2) + 4 * g : nullptr);
             gw += N::KD * N::STEP;
@@ -132,7 +128,7 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_backward_kernel
                 acc[nt] = f32x4{w4[0] * dsigma, w4[1] * dsigma, w4[2] * dsigma, w4[3] * dsigma};
             }
             const uint64_t m = tile_ok ? mrow[(int64_t)(L - 2) * mstride] : 0;
-            gemm_stage<N::NT, N::KH, 0, NW, N::LDSBUF, KCH, true, false, 0, true>(
+            gemm_stage<N::NT, N::KH, 0, NW, N::LDSBUF, KCH, true>(
                 acc, in, dummy, gw, gw + N::KH * N::STEP, N::LDSBUF, lds, par, wave, lane,
                 valid ? args.d_feat + sample * H + 4 * g : nullptr);
             gw += N::KH * N::STEP;
@@ -153,7 +149,7 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_backward_kernel
             const char* tsrc = gw + N::KH * N::STEP;
             int tbytes = N::LDSBUF;
             if (i == last_i) { tsrc = args.wstream; tbytes = has_next ? FIRST : 0; }
-            gemm_stage<N::NT, N::KH, 0, NW, N::LDSBUF, KCH, true, false, 0, true>(
+            gemm_stage<N::NT, N::KH, 0, NW, N::LDSBUF, KCH, true>(
                 acc, in, dummy, gw, tsrc, tbytes, lds, par, wave, lane,
                 d_row ? d_row + (int64_t)(i + 1) * args.n * H : nullptr);   // the delta this stage consumes
             gw += N::KH * N::STEP;
@@ -235,31 +231,18 @@ __global__ __launch_bounds__(256) void encode_samples_rows_kernel(const EncodeAr
 // ---- plan tables -------------------------------------------------------------------------------------------
 struct TrainPlan {
     int H, FX, FD;
-    int ring_slots;                                                // LDS ring: 3 (mlp_kernel3 dataflow) or 2
+    int ring_slots;                                                // LDS ring of mlp_kernel (mlp_device.h)
     void (*forward)(const MlpArgs, const int, const int);
     void (*forward_flat)(const MlpArgs, const int, const int);     // the taping kernel that also serves use_viewdirs = 0 networks
 };
 template <int H, int FX, int FD>
 static TrainPlan make_train_plan() {
-    return TrainPlan{H, FX, FD, 2, &mlp_kernel<H, FX, FD, 8, KC, true, true, true, false, 0, true>,
-                     &mlp_kernel<H, FX, FD, 8, KC, true, true, true, false, 0, true, true>};
+    return TrainPlan{H, FX, FD, 2, &mlp_kernel<H, FX, FD, 8, KC, true>, &mlp_kernel<H, FX, FD, 8, KC, true, true>};
 }
 static const TrainPlan g_train_plans[] = {
     make_train_plan<256, 10, 4>(), make_train_plan<128, 10, 4>(), make_train_plan<64, 10, 4>(),
     make_train_plan<256, 6, 4>(),  make_train_plan<128, 6, 4>(),  make_train_plan<64, 6, 4>(),
 };
-#ifdef NM_ABLATIONS
-// experiment (ablation library, NM_MLP_VARIANT=3): the 256- and 128-wide networks tape on the inference kernel's dataflow
-// (3-slot ring, operand stream across chunk and stage boundaries, staggered DMA: mlp_device_r3.h) -- same tape, same bits,
-// measured slower (see mlp_kernel3)
-template <int H, int FX, int FD>
-static TrainPlan make_train_plan3() {
-    return TrainPlan{H, FX, FD, 3, &mlp_kernel3<H, FX, FD, 8, KC, 1, 0, false, true>, &mlp_kernel3<H, FX, FD, 8, KC, 1, 0, true, true>};
-}
-static const TrainPlan g_train_plans3[] = {
-    make_train_plan3<256, 10, 4>(), make_train_plan3<128, 10, 4>(), make_train_plan3<256, 6, 4>(), make_train_plan3<128, 6, 4>(),
-};
-#endif
 
 struct BwdPlan {
     int H;
@@ -321,12 +304,6 @@ int nm_mlp_forward_train(nm_mlp* m, const float* d_origins, int origins_per_ray,
     for (const TrainPlan& p : g_train_plans)
         if (p.H == d.hidden_size && p.FX == d.num_encoding_fn_xyz && p.FD == (flat ? 4 : d.num_encoding_fn_dir)) plan = &p;
     NM_REQUIRE(plan, "no training kernel instantiated for this network shape");
-#ifdef NM_ABLATIONS
-    if (const char* v = getenv("NM_MLP_VARIANT"))
-        if (atoi(v) == 3)
-            for (const TrainPlan& p : g_train_plans3)
-                if (p.H == plan->H && p.FX == plan->FX && p.FD == plan->FD) { plan = &p; break; }
-#endif
     if (a.n == 0) return 0;
     a.tape_h = tape->d_h; a.tape_feat = tape->d_feat; a.tape_v = tape->d_v;
     a.tape_v_ld = tape->v_stride > 0 ? tape->v_stride : d.hidden_size / 2;

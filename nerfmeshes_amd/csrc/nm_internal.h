@@ -159,7 +159,6 @@ struct WeightPtrs { const float* p[T_COUNT]; };
 struct MlpPlan {
     int H, FX, FD, NW, KCH, variant;
     int ring_bytes;
-    bool lds_bias;
     void (*kernel)(const MlpArgs, const int, const int);
     int wg_samples;      // samples one workgroup evaluates per iteration
     int wg_per_cu;       // workgroups co-resident on a CU

@@ -1,8 +1,9 @@
 """CPU: a model of the activation hand-over of the split kernels (nerfmeshes_amd/csrc/mlp_device_gs.h, gs_publish_first /
 gs_stage_hidden): for every width class they serve, replay the schedule chunk by chunk and check the protocol's three claims --
 a tile is visible (written before a barrier) before its reader fetches it, it is fetched before the chunk that multiplies with it,
-and a slot is never rewritten before a barrier behind the last fetch of the tile it held.  The kernels themselves are pinned bit
-for bit to the one-wave kernels on the GPU (tests/tools/bench_split.py, tests/test_gpu_generic.py); this pins the reasoning."""
+and a slot is never rewritten before a barrier behind the last fetch of the tile it held.  The kernels themselves are checked
+against the oracle on the GPU (tests/test_gpu_generic.py), and round 5 pinned them bit for bit to the one-wave kernels they replaced
+(profiles/r05_split_wide_classes.json; those kernels and their A/B tool: source last present in 94bb324); this pins the reasoning."""
 import pytest
 
 SLOTS = 4          # 1 KiB exchange slots per pair of waves

@@ -1,20 +1,13 @@
 """SHA-256 of the taping forward's outputs (radiance + every tape tensor) and of the delta kernel's outputs on seeded inputs,
 plus their best-of-N times: run before and after a change of the training kernels that must not change a bit.
 
-    python tests/tools/train_checksum.py                 # product library
-    python tests/tools/train_checksum.py --variant 3     # ablation library, NM_MLP_VARIANT=3: taping forward on the 3-slot dataflow
+    python tests/tools/train_checksum.py
 """
 import ctypes as C, hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import torch
 from nerfmeshes_amd import _lib
-if "--variant" in sys.argv:
-    from nerfmeshes_amd import build as hip_build
-    if not os.path.exists(hip_build.ABLATION_LIB_PATH):
-        hip_build.build(ablations=True, verbose=False)
-    _lib.LIB_PATH = hip_build.ABLATION_LIB_PATH            # explicit: nothing else in the package loads this library
-    os.environ["NM_MLP_VARIANT"] = sys.argv[sys.argv.index("--variant") + 1]
 from nerfmeshes_amd import hip_ops, synthetic as S, train_ops as T
 from nerfmeshes_amd._lib import MlpDeltas
 
