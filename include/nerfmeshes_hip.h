@@ -122,7 +122,12 @@ int64_t nm_mlp_flops_per_sample(const nm_mlp* mlp, int density_only);
 
 /* Measurement hook (no reference counterpart): while enabled, every launch of the fused MLP kernel is
  * bracketed by hipEvents on its own stream.  nm_mlp_profile_read synchronises those events, returns
- * the number of launches, their summed duration and summed ALGORITHMIC flops, and clears the list. */
+ * the number of launches, their summed duration and summed EXECUTED flops, and clears the list: total_flops is
+ * the algorithmic count (samples x nm_mlp_flops_per_sample) minus, for the render calls' launches, what their
+ * skipped tiles did not run -- skipped tiles x tile samples x (flops_per_sample(0) - flops_per_sample(1)); the tiles
+ * are counted on the device (one counter per launch, allocated on every device by nm_mlp_profile_enable(1)) while
+ * profiling is on.  A device has 2^20 counters: a skipping launch beyond that many since the last read evaluates
+ * every tile (slower, and counted as such), so read at least that often. */
 int nm_mlp_profile_enable(int on);
 int nm_mlp_profile_read(int64_t* launches, double* total_ms, double* total_flops);
 
@@ -228,7 +233,11 @@ int nm_sample_pdf(const float* d_t, const float* d_weights, const float* d_u, in
 
 /* NeRFModel.forward  (src/models/model_nerf.py:37-78): the whole coarse -> resample -> fine chain in
  * one call, all intermediates in caller-provided workspace (nm_render_workspace_bytes).  `fine`
- * (and fine_out) may be NULL (models.use_fine False). */
+ * (and fine_out) may be NULL (models.use_fine False).
+ * The radiance held in the workspace is internal: where no sample of a workgroup tile (128 samples: 8 adjacent rays x
+ * 16 consecutive samples when the sample count is a multiple of 16, else 128 consecutive samples) has raw sigma > 0,
+ * the fused 256-wide and 128-wide (10 xyz frequencies) fp32 kernels store {0, 0, 0, sigma} for the tile and do not evaluate its colour -- alpha
+ * and weight of such samples are exactly 0, so every output map has the bits it has with the colours computed. */
 typedef struct nm_render_cfg {
     int32_t num_coarse, num_fine;      /* cfg.nerf.train.num_coarse / num_fine (model_nerf.py:30-31) */
     int32_t lindisp;                   /* cfg.nerf.{train,validation}.lindisp */

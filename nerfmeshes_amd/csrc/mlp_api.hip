@@ -167,9 +167,14 @@ MlpArgs ray_mode_args(const nm_mlp* m, const float* d_origins, int origins_per_r
 }
 
 // ---- optional per-launch timing of the dominant kernel (bench.py's roofline leg) ---------------
-struct ProfRec { hipEvent_t start, stop; double flops; };
+// A launch that may skip the colour branch of tiles without density (MlpArgs::skip_empty) counts them in a device word of its own:
+// `slot` indexes g_prof_skips (-1: the launch cannot skip), `skip_flops` is what one skipped tile did not execute.
+struct ProfRec { hipEvent_t start, stop; double flops; int slot, device; double skip_flops; };
 static bool g_prof_on = false;
 static std::vector<ProfRec> g_prof;
+constexpr int PROF_SKIP_SLOTS = 1 << 20;          // skipping launches per device between two reads (4 MB of counters per device)
+struct ProfSkips { uint32_t* d = nullptr; int used = 0; };
+static std::vector<ProfSkips> g_prof_skips;       // one array per device, allocated (zeroed) by nm_mlp_profile_enable(1), never in a launch
 
 // density_only: 0 full evaluation | 1 sigma only.  For a use_viewdirs = 0 handle the full evaluation is the kernels' mode 2:
 // the trunk as in mode 1, then all four rows of fc_out (models.py:77-79).
@@ -181,8 +186,22 @@ static int launch_mlp_timed(const nm_mlp* m, const MlpArgs& a, int density_only,
     NM_HIP_CHECK(hipEventCreate(&r.start));
     NM_HIP_CHECK(hipEventCreate(&r.stop));
     r.flops = (double)a.n * (double)(density_only == 1 ? m->flops_density : m->flops_full);
+    r.slot = -1; r.device = -1; r.skip_flops = 0;
+    MlpArgs counted = a;
+    if (a.skip_empty && !density_only && !m->lw) {
+        ProfSkips* ps = m->device >= 0 && m->device < (int)g_prof_skips.size() ? &g_prof_skips[m->device] : nullptr;
+        if (ps && ps->d && ps->used < PROF_SKIP_SLOTS) {
+            r.slot = ps->used++; r.device = m->device;
+            r.skip_flops = (double)m->plan->wg_samples * (double)(m->flops_full - m->flops_density);
+            counted.skip_count = ps->d + r.slot;
+        } else {
+            // more than PROF_SKIP_SLOTS skipping launches since the last read (documented in the public header): without a
+            // counter the launch evaluates every tile, so that it executes every FLOP it is credited with
+            counted.skip_empty = 0;
+        }
+    }
     NM_HIP_CHECK(hipEventRecord(r.start, stream));
-    const int rc = launch();
+    const int rc = m->lw ? launch() : launch_mlp(m, counted, density_only, stream);
     NM_HIP_CHECK(hipEventRecord(r.stop, stream));
     g_prof.push_back(r);
     return rc;
@@ -357,18 +376,41 @@ int nm_device_count(void) {
 }
 
 int nm_mlp_profile_enable(int on) {
+    if (on && g_prof_skips.empty()) {             // a handle may live on any device: counters on each of them
+        int count = 0;
+        NM_HIP_CHECK(hipGetDeviceCount(&count));
+        std::vector<ProfSkips> slots(count);
+        for (int dev = 0; dev < count; ++dev) {
+            DeviceGuard guard(dev);
+            NM_HIP_CHECK(hipMalloc(&slots[dev].d, PROF_SKIP_SLOTS * sizeof(uint32_t)));
+            NM_HIP_CHECK(hipMemset(slots[dev].d, 0, PROF_SKIP_SLOTS * sizeof(uint32_t)));
+        }
+        g_prof_skips.swap(slots);
+    }
     g_prof_on = on != 0;
     return 0;
 }
 
 int nm_mlp_profile_read(int64_t* launches, double* total_ms, double* total_flops) {
     double ms = 0, fl = 0;
+    std::vector<uint32_t> skips;
     for (ProfRec& r : g_prof) {
         NM_HIP_CHECK(hipEventSynchronize(r.stop));
         float t = 0;
         NM_HIP_CHECK(hipEventElapsedTime(&t, r.start, r.stop));
         ms += t; fl += r.flops;
         (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop);
+    }
+    for (int dev = 0; dev < (int)g_prof_skips.size(); ++dev) {   // every counted launch has finished: its stop event was waited for above
+        ProfSkips& ps = g_prof_skips[dev];
+        if (ps.used == 0) continue;
+        DeviceGuard guard(dev);
+        skips.resize(ps.used);
+        NM_HIP_CHECK(hipMemcpy(skips.data(), ps.d, skips.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        NM_HIP_CHECK(hipMemset(ps.d, 0, skips.size() * sizeof(uint32_t)));
+        for (const ProfRec& r : g_prof)
+            if (r.slot >= 0 && r.device == dev) fl -= (double)skips[r.slot] * r.skip_flops;
+        ps.used = 0;
     }
     if (launches) *launches = (int64_t)g_prof.size();
     if (total_ms) *total_ms = ms;
@@ -582,14 +624,16 @@ int nm_mlp_eval_rays(nm_mlp* m, const float* d_origins, int origins_per_ray, con
 }  // extern "C"
 
 namespace nm {
-int nm_mlp_eval_view_internal(nm_mlp* m, const RayGen* gen, const float* d_t, int64_t rays, int32_t samples,
-                              float* d_radiance, hipStream_t stream) {
-    NM_REQUIRE(m && gen && d_t && d_radiance && rays >= 0 && samples > 0, "bad argument");
-    MlpArgs a = m->base;
-    a.mode = MODE_VIEW;
-    a.a = nullptr; a.b = nullptr; a.c = d_t;
-    a.samples = samples; a.gen = *gen;
-    a.n = rays * samples; a.out = d_radiance;
+int nm_mlp_eval_render_internal(nm_mlp* m, const RayGen* gen, const float* d_origins, int origins_per_ray, const float* d_dirs,
+                                const float* d_t, int64_t rays, int32_t samples, float* d_radiance, hipStream_t stream) {
+    NM_REQUIRE(m && (gen || (d_origins && d_dirs)) && d_t && d_radiance && rays >= 0 && samples > 0, "bad argument");
+    MlpArgs a = ray_mode_args(m, d_origins, origins_per_ray, d_dirs, d_t, rays, samples, d_radiance);
+    if (gen) {
+        a.mode = MODE_VIEW;
+        a.a = nullptr; a.b = nullptr;
+        a.gen = *gen;
+    }
+    a.skip_empty = 1;
     return launch_mlp_timed(m, a, 0, stream);
 }
 }  // namespace nm

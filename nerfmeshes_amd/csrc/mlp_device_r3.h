@@ -85,19 +85,27 @@ __device__ __forceinline__ void gemm_stage3(f32x4 (&acc)[NT], const float (&b1)[
 // Inference only.  The taping forward on this dataflow was built, wrote the same tape bit for bit and measured 4.7 % SLOWER than
 // the 2-slot taping kernel (3.54 vs 3.38 ms per 393 216 samples of the 8x256 network, profiles/r04_train_three_slot.json; source
 // last present in 94bb324): the training kernels stay on mlp_device.h's dataflow.
-template <int H, int FX, int FD, int NW, int KCH, bool FLAT = false>   // FLAT: see mlp_kernel
+// SKIP: the render path's instantiation (MlpArgs::skip_empty): a tile on which no sample has density writes
+// {0, 0, 0, sigma} and skips fc_feat, the view layer and fc_rgb; in ray modes with samples % 16 == 0 a tile is NW adjacent rays x
+// 16 consecutive samples (MlpArgs::ray_tiles).  A separate instantiation so that every other entry point runs the kernel it ran.
+template <int H, int FX, int FD, int NW, int KCH, bool FLAT = false, bool SKIP = false>   // FLAT: see mlp_kernel
 // Occupancy: networks up to 128 wide are compiled for FOUR waves per SIMD (128 registers: two 8-wave workgroups per CU; the
 // 128-wide instances spill 9 -- 17 registers outside the k-step loops for it).  With VALU issue time adding to matrix time on
 // narrow networks two more waves per SIMD are worth +2.7 points at 8x128 (0.875 -> 0.902, same bits).
 __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const MlpArgs args, const int num_layers,
                                                           const int density_only) {
     using N = Net<H, FX, FD, KCH>;
+    static_assert(!(FLAT && SKIP), "the use_viewdirs = 0 heads have no colour branch to skip");
     static_assert(N::EX > KCH && N::KH >= 2 * KCH, "stages must span two chunks");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* lds_bias = reinterpret_cast<float*>(lds + 3 * N::LDSBUF);
     const int nbias = H * (1 + num_layers) + H / 2 + 4;
     float* lds_walpha = lds_bias + nbias;
     float* lds_wrgb = lds_walpha + H;
+    // SKIP's vote word, behind fc_rgb's rows (the cache is 4 H (L + 4) + 16 bytes rounded up to 256: 240 bytes are spare; the
+    // FLAT heads' wider rows never meet SKIP).  It holds the stamp of the last iteration on which some wave saw density.
+    int* lds_vote = reinterpret_cast<int*>(lds_wrgb + 3 * H / 2);
+    if (SKIP && threadIdx.x == 0) *lds_vote = 0;
     for (int i = threadIdx.x; i < nbias; i += NW * 64) lds_bias[i] = args.bias[i];
     for (int i = threadIdx.x; i < H; i += NW * 64) lds_walpha[i] = args.walpha[i];
     for (int i = threadIdx.x; i < ((FLAT && density_only == 2) ? 3 * H : 3 * H / 2); i += NW * 64) lds_wrgb[i] = args.wrgb[i];
@@ -106,7 +114,7 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
     const int g = lane >> 4, col = lane & 15;
     const float* tail_bias = lds_bias + nbias - 4;
 
-    const int64_t wg_iters = (args.n + NW * 16 - 1) / (NW * 16);
+    const int64_t wg_iters = mlp_wg_iters(args, NW * 16);
     auto hidden_next = [](const char* p) {
         return NextChunks{p, KCH * N::STEP, p + KCH * N::STEP, (N::KH - KCH < KCH ? N::KH - KCH : KCH) * N::STEP};
     };
@@ -129,8 +137,16 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
 
     for (int64_t it = blockIdx.x; it < wg_iters; it += gridDim.x) {
         const bool has_next = it + gridDim.x < wg_iters;
-        const int64_t sample = (it * NW + wave) * 16 + col;
-        const bool valid = sample < args.n;
+        // linear order: wave w of iteration `it` owns 16 consecutive samples; ray_tiles: ray NW * block + w, depth slot k
+        int64_t sample = (it * NW + wave) * 16 + col;
+        bool valid = sample < args.n;
+        if (SKIP && args.ray_tiles) {   // (32-bit split: launch_mlp keeps wg_iters below 2^31 in this mode; the 64-bit division costs registers)
+            const uint32_t depth_slots = (uint32_t)args.samples >> 4;
+            const uint32_t block = (uint32_t)it / depth_slots;
+            const int64_t ray_first = ((int64_t)block * NW + wave) * args.samples;
+            sample = ray_first + (((uint32_t)it - block * depth_slots) << 4) + col;
+            valid = ray_first < args.n;
+        }
         const int64_t sidx = valid ? sample : args.n - 1;
         const SamplePD smp = fetch_sample(args, sidx);
         const float p[3] = {smp.px, smp.py, smp.pz}, d[3] = {smp.dx, smp.dy, smp.dz};
@@ -150,11 +166,22 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
 
         // ---- layers_xyz[0 .. L-2], then (full evaluation only) fc_feat as iteration L-1 (models.py:63-70)
         float sigma = 0.0f;
+        bool empty_tile = false;
         const int trunk_iters = density_only ? num_layers - 1 : num_layers;
 #pragma unroll 1
         for (int i = 0; i < trunk_iters; ++i) {
             const bool is_feat = i == num_layers - 1;
             if (is_feat) sigma = alpha_gemv<H>(in, lds_walpha, g) + tail_bias[0];
+            if (SKIP && is_feat) {
+                // Workgroup-uniform vote (the stages below hold barriers: every wave must take the same branch): a wave on which some
+                // valid sample has density -- or a NaN sigma, which must keep propagating -- stamps this iteration's number.
+                const int epoch = (int)it + 1;      // never 0, and different on consecutive iterations of a workgroup
+                const bool dense = valid && !(sigma <= 0.0f);
+                if (dense) *lds_vote = epoch;
+                __syncthreads();
+                empty_tile = __builtin_amdgcn_readfirstlane(*lds_vote) != epoch;
+                if (empty_tile) break;
+            }
             const bool skip = !is_feat && ((args.skip_mask >> i) & 1u);
             const bool last_density = density_only && i == num_layers - 2;
             load_bias<N::NT>(acc, lds_bias + H * (1 + i), g);
@@ -174,6 +201,30 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
                 gw = after;
             }
             acc_to_operand<N::NT, true>(acc, in);
+        }
+
+        if (empty_tile) {
+            // No sample of the tile has density: alpha and weight are exactly 0 for all of them, so their colour never reaches a map.
+            // It is written as zeros (finite: 0 * rgb must stay 0 in the compositor); fc_feat, the view layer and fc_rgb are skipped.
+            if (valid && g == 0) {
+                f32x4 o4 = {0.0f, 0.0f, 0.0f, sigma};
+                *reinterpret_cast<f32x4*>(args.out + 4 * sample) = o4;
+            }
+            if (args.skip_count && threadIdx.x == 0) atomicAdd(args.skip_count, 1u);
+            // The ring holds fc_feat's first two chunks and `carry` its first two blocks.  Restart the stream as the prologue does:
+            // layer1's chunks 0 and 1 into the two slots after `slot` (every read of the ring completed before the vote's barrier),
+            // one barrier, `carry` from the first of them, which becomes `slot`.
+            if (has_next) {
+                const int slot1 = slot == 2 ? 0 : slot + 1;
+                const int slot2 = slot1 == 2 ? 0 : slot1 + 1;
+                stream_to_lds<NW>(wrap.s0, lds + slot1 * N::LDSBUF, wrap.b0, wave, lane);
+                stream_to_lds<NW>(wrap.s1, lds + slot2 * N::LDSBUF, wrap.b1, wave, lane);
+                __syncthreads();
+                slot = slot1;
+                carry[0] = *reinterpret_cast<const f32x4*>(lds + slot * N::LDSBUF + lane * 16);
+                carry[1] = *reinterpret_cast<const f32x4*>(lds + slot * N::LDSBUF + lane * 16 + 1024);
+            }
+            continue;
         }
 
         if (density_only) {

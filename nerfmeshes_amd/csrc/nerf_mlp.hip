@@ -44,10 +44,12 @@ static MlpPlan make_plan() {
                    NW * 16, 8 / NW, &mlp_kernel<H, FX, FD, NW, KCH, false, true>, 0, nullptr, nullptr};
 }
 
-template <int H, int FX, int FD, int NW, int KCH>
+// SKIP: install the render path's instantiation (mlp_device_r3.h) -- where it stays within its sibling's register budget
+template <int H, int FX, int FD, int NW, int KCH, bool SKIP = true>
 static MlpPlan make_plan3() {
     return MlpPlan{H, FX, FD, NW, KCH, 0, 3 * Net<H, FX, FD, KCH>::LDSBUF, &mlp_kernel3<H, FX, FD, NW, KCH>,
-                   NW * 16, 8 / NW, &mlp_kernel3<H, FX, FD, NW, KCH, true>, 0, nullptr, nullptr};
+                   NW * 16, 8 / NW, &mlp_kernel3<H, FX, FD, NW, KCH, true>, 0, nullptr, nullptr,
+                   SKIP ? &mlp_kernel3<H, FX, FD, NW, KCH, false, SKIP> : nullptr};
 }
 
 // One plan per tuned shape.  The A/B variants of rounds 1 -- 5 that used to sit next to them (profiles/r0*_mlp_variants.json,
@@ -59,7 +61,8 @@ static const MlpPlan g_tuned_plans[] = {
     make_plan3<128, 10, 4, 8, 8>(),
     make_plan<64, 10, 4, 8, 8>(),
     make_plan3<256, 6, 4, 8, 8>(),
-    make_plan3<128, 6, 4, 8, 8>(),
+    // no SKIP instance for 128 / 6: it spills 12 VGPRs where this kernel spills 9, so that shape's render keeps this kernel
+    make_plan3<128, 6, 4, 8, 8, false>(),
     make_plan<64, 6, 4, 8, 8>(),
 };
 
@@ -139,13 +142,20 @@ int forward_lds_bytes(const MlpPlan& p, int H, int L, int head_floats) {
     return p.ring_bytes + tuned_cache_bytes(H, L, head_floats);
 }
 
-int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream_t stream) {
+int launch_mlp(const nm_mlp* m, const MlpArgs& args_in, int density_only, hipStream_t stream) {
     const MlpPlan* p = m->plan;
-    if (args.n <= 0) return 0;
+    if (args_in.n <= 0) return 0;
+    // The render path's skip of tiles without density (MlpArgs::skip_empty) exists as mlp_kernel3's SKIP instantiation only: every other
+    // family -- mlp_kernel<64, ...>, the generic kernels, bf16x3, the use_viewdirs = 0 heads -- evaluates every sample in linear order.
+    MlpArgs args = args_in;
+    if (!(args.skip_empty && p->kernel_skip && density_only == 0 && m->precision == NM_PREC_F32)) args.skip_empty = 0;
+    args.ray_tiles = args.skip_empty && (args.mode == MODE_RAYS || args.mode == MODE_VIEW) && args.samples % 16 == 0;
+    if (args.ray_tiles && mlp_wg_iters(args, p->wg_samples) > INT32_MAX) args.ray_tiles = 0;   // the kernel splits `it` in 32 bits
+    if (!args.skip_empty) args.skip_count = nullptr;
     DeviceGuard guard(m->device);
     const int L = m->desc.num_layers, H = m->desc.hidden_size;
     NM_REQUIRE(density_only != 2 || (m->precision == NM_PREC_F32 && p->kernel_flat), "no kernel for use_viewdirs=0 networks in this plan");
-    auto kernel = density_only == 2 ? p->kernel_flat : p->kernel;
+    auto kernel = density_only == 2 ? p->kernel_flat : (args.skip_empty ? p->kernel_skip : p->kernel);
     if (m->precision == NM_PREC_BF16X3) {
         const B3Plan* b = find_b3_plan(H, m->desc.num_encoding_fn_xyz, m->desc.num_encoding_fn_dir);
         NM_REQUIRE(b && m->d_stream_b3, "no bf16x3 kernel for this network");
@@ -165,7 +175,7 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args, int density_only, hipStream
     const int lds_bytes = forward_lds_bytes(*p, H, L, density_only == 2 ? 3 * H : 3 * H / 2);
     NM_REQUIRE(lds_bytes <= 160 * 1024, "LDS budget exceeded (ring + bias cache)");
     if (int rc = ensure_dynamic_lds((const void*)kernel, lds_bytes)) return rc;
-    const int64_t wg_iters = (args.n + p->wg_samples - 1) / p->wg_samples;
+    const int64_t wg_iters = mlp_wg_iters(args, p->wg_samples);
     const unsigned grid = persistent_grid(wg_iters, (int64_t)m->num_cus * p->wg_per_cu);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(p->NW * 64), lds_bytes, stream, args, (int)m->desc.num_layers, density_only);
     NM_HIP_CHECK(hipGetLastError());

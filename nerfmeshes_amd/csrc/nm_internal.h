@@ -128,7 +128,21 @@ struct MlpArgs {
     int32_t g_nsx, g_idx, g_chx;   // xyz: k-steps that carry arguments, 1 = an identity step follows, whole chunks in the stream
     int32_t g_nsd, g_idd, g_chd;   // direction encoding likewise (g_chd = 0: no encoded direction columns at all)
     int32_t g_h, g_hd;             // the REAL widths hidden_size and hidden_size // 2: row strides of the generic training tape
+    // render-internal evaluation (render_impl in ray_ops.hip only; launch_mlp clears all three where the plan has no kernel_skip)
+    int32_t skip_empty;      // a workgroup tile on which no sample has raw sigma > 0 gets {0, 0, 0, sigma} and skips the colour branch
+    int32_t ray_tiles;       // RAYS / VIEW with samples % 16 == 0: a tile is wg_samples / 16 adjacent rays x 16 consecutive samples
+    uint32_t* skip_count;    // null, or the launch's counter of skipped tiles (profiling: mlp_api.hip)
 };
+
+// Workgroup iterations of a tuned forward launch: THE expression, shared by launch_mlp (grid size) and the kernels (loop bound).
+// Linear order: wg_samples consecutive samples per tile.  ray_tiles: ceil(rays / (wg_samples / 16)) ray blocks x samples / 16 depth slots.
+__host__ __device__ inline int64_t mlp_wg_iters(const MlpArgs& a, int wg_samples) {
+    if (a.ray_tiles) {
+        const int rays_per_tile = wg_samples / 16;
+        return (a.n / a.samples + rays_per_tile - 1) / rays_per_tile * (a.samples / 16);
+    }
+    return (a.n + wg_samples - 1) / wg_samples;
+}
 
 // Kernel arguments of the backward (delta propagation) kernel.
 struct MlpBwdArgs {
@@ -166,6 +180,8 @@ struct MlpPlan {
     int generic_nt;      // 0: a tuned plan for exactly (H, FX, FD) | NT: the generic family's width class (mlp_device_g.h), H = 16 NT
     void (*kernel_tape)(const MlpArgs, const int, const int);        // generic family: the taping forward ...
     void (*kernel_bwd)(const MlpBwdArgs, const int, const int);      // ... and the delta kernel (null for tuned plans: nerf_train.hip)
+    void (*kernel_skip)(const MlpArgs, const int, const int);        // the instantiation that implements MlpArgs::skip_empty / ray_tiles
+                                                                     // (mlp_kernel3<..., SKIP>), or null
 };
 
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, raised once per (device, kernel) and whenever a launch needs more --
@@ -215,9 +231,11 @@ struct DwgEpilogue { float* out; const float* bias; const float* mask; int64_t l
 int dwg_gemm(const float* A, int out, int lda, const float* B, int64_t in, int64_t ldb, int rows, float* partial, hipStream_t stream,
              const DwgEpilogue* epilogue = nullptr);
 
-// fused MLP over rays generated from a camera pose (mlp_api.hip; used by the render path in ray_ops.hip)
-int nm_mlp_eval_view_internal(nm_mlp* m, const RayGen* gen, const float* d_t, int64_t rays, int32_t samples,
-                              float* d_radiance, hipStream_t stream);
+// The render path's two network calls (ray_ops.hip: render_impl): rays from buffers (`gen` null) or from the pose, into WORKSPACE
+// radiance that only the compositor reads, with MlpArgs::skip_empty set -- a sample with raw sigma <= 0 has alpha == weight == 0
+// exactly (no noise is added on this path), so the rgb of a tile without density is written as zeros instead of being computed.
+int nm_mlp_eval_render_internal(nm_mlp* m, const RayGen* gen, const float* d_origins, int origins_per_ray, const float* d_dirs,
+                                const float* d_t, int64_t rays, int32_t samples, float* d_radiance, hipStream_t stream);
 
 }  // namespace nm
 

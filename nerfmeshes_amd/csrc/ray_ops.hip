@@ -700,8 +700,8 @@ static int render_impl(nm_mlp* coarse, nm_mlp* fine, const nm_render_cfg* cfg, c
     float* w_c = reinterpret_cast<float*>(ws); ws += align256(rays * (size_t)sc * 4);
     int rc;
     auto mlp = [&](nm_mlp* m, const float* t, int samples, float* rad) -> int {
-        if (!gen) return nm_mlp_eval_rays(m, d_origins, origins_per_ray, d_dirs, t, rays, samples, rad, stream);
-        return nm_mlp_eval_view_internal(m, gen, t, rays, samples, rad, stream);
+        // `rad` is workspace only the compositor below reads, and no noise is added to sigma: tiles without density skip the colour branch
+        return nm_mlp_eval_render_internal(m, gen, d_origins, origins_per_ray, d_dirs, t, rays, samples, rad, stream);
     };
     // RaySampleInterval -> intervals_to_ray_points -> model_coarse -> volume_renderer (model_nerf.py:52-62)
     if ((rc = launch_coarse_intervals(d_u_coarse, d_near, d_far, bounds_per_ray, cfg->lindisp, rays, sc, t_c, stream))) return rc;

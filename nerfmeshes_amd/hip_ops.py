@@ -362,10 +362,26 @@ def mlp_profile_enable(on=True):
 
 
 def mlp_profile_read():
-    """(launches, total kernel ms, total algorithmic flops) of the fused-MLP launches since the last read."""
+    """(launches, total kernel ms, total EXECUTED flops) of the fused-MLP launches since the last read: the algorithmic count
+    minus what the render path's skipped tiles (workgroup tiles without density: no fc_feat, view layer, fc_rgb) did not run."""
     n, ms, fl = C.c_int64(), C.c_double(), C.c_double()
     check(_lib.load().nm_mlp_profile_read(C.byref(n), C.byref(ms), C.byref(fl)), "nm_mlp_profile_read")
     return n.value, ms.value, fl.value
+
+
+def mlp_profile_read_skipped(model, samples):
+    """mlp_profile_read() for a profiled stretch in which networks of `model`'s shape evaluated `samples` samples in full:
+    (launches, kernel ms, executed flops, skipped tiles).  The library counts skipped tiles per launch and reports them as the
+    flops they did not execute; a tile is `waves * 16` samples, and both counts are integers far below 2**53, so the division
+    is exact.  The stretch must bracket exactly those evaluations (render calls of one network shape, say): any other
+    profiled fused-MLP launch in it -- a density-only query, another shape -- makes the counts disagree, which raises."""
+    n, ms, fl = mlp_profile_read()
+    full, density = model.flops_per_sample(), model.flops_per_sample(True)
+    per_tile = model.kernel_variant()[1] * 16 * (full - density)
+    missing = int(samples) * full - int(round(fl))
+    if missing < 0 or missing % per_tile:
+        raise _lib.HipLibraryError(f"profiled flops {fl!r} do not match {samples} full evaluations minus whole skipped tiles")
+    return n, ms, fl, missing // per_tile
 
 
 TIE_ORDERS = {"stable": 0, "reference": 1}
