@@ -123,10 +123,11 @@ __device__ __forceinline__ void gemm_stage(f32x4 (&acc)[NT], const float (&b1)[K
     }
 }
 
-template <int NT>
+// (T0: the first of the NT tiles -- 0 but for a wave of the split generic kernels, mlp_device_gs.h, which owns tiles [T0, T0 + NT))
+template <int NT, int T0 = 0>
 __device__ __forceinline__ void load_bias(f32x4 (&acc)[NT], const float* bias, int g) {
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[nt] = *reinterpret_cast<const f32x4*>(bias + 16 * nt + 4 * g);
+    for (int nt = 0; nt < NT; ++nt) acc[nt] = *reinterpret_cast<const f32x4*>(bias + 16 * (T0 + nt) + 4 * g);
 }
 
 template <int NT, bool RELU>
@@ -216,17 +217,24 @@ __device__ __forceinline__ float group_sum(float v) {  // sum over the 4 lane gr
     return v;
 }
 
+// A head row's chain over the tiles [T0, T0 + N) of an activation (k-step 4 tile + q ascending), continuing from `start`: the
+// whole row from 0 in the one-wave kernels, a wave's stretch in the split generic ones (mlp_device_gs.h)
+template <int N, int T0 = 0>
+__device__ __forceinline__ float head_chain(const float (&in)[4 * N], const float* row, float start) {
+    float part = start;
+#pragma unroll
+    for (int nt = 0; nt < N; ++nt) {
+        const f32x4 w4 = *reinterpret_cast<const f32x4*>(row + 4 * (T0 + nt));
+#pragma unroll
+        for (int q = 0; q < 4; ++q) part = fmaf(in[4 * nt + q], w4[q], part);
+    }
+    return part;
+}
+
 template <int H>
 __device__ __forceinline__ float alpha_gemv(const float (&in)[H / 4], const float* walpha, int g) {
-    float part = 0.0f;   // fc_alpha (models.py:71): 1-row GEMV on the VALU + lane-group reduction
-    const float* wa = walpha + g * (H / 4);
-#pragma unroll
-    for (int s = 0; s < H / 4; s += 4) {
-        const f32x4 w4 = *reinterpret_cast<const f32x4*>(wa + s);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) part = fmaf(in[s + q], w4[q], part);
-    }
-    return group_sum(part);
+    // fc_alpha (models.py:71): 1-row GEMV on the VALU + lane-group reduction
+    return group_sum(head_chain<H / 16>(in, walpha + g * (H / 4), 0.0f));
 }
 
 // A network without view directions (models.py:77-79): the colour rows of fc_out over the trunk output, three more GEMVs

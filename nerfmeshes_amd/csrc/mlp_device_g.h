@@ -179,15 +179,16 @@ __device__ __forceinline__ void enc_stages_g(f32x4 (&acc)[NTO], const float (&en
 
 // ---- training tape of the generic family: row-major [sample][width] rows of the REAL width (padding never leaves the
 // registers).  16-byte accesses when the row stride allows it (width % 4 == 0), element-wise otherwise (e.g. the 50-wide view
-// layer of a 100-wide network).
-template <int NT>
+// layer of a 100-wide network).  store_rows_g and relu_gate work on the tiles [T0, T0 + NT) of a row: all of them (T0 = 0) in
+// the one-wave kernels, a wave's half in the split ones (mlp_device_gs.h: GsHalf).
+template <int NT, int T0 = 0>
 __device__ __forceinline__ void store_rows_g(float* base, int width, int64_t sample, bool valid, const float (&op)[4 * NT], int g) {
     if (!valid) return;
     float* row = base + sample * width;
     const bool vec = (width & 3) == 0;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        const int k0 = 16 * nt + 4 * g;
+        const int k0 = 16 * (T0 + nt) + 4 * g;
         if (vec && k0 + 3 < width) {
             const f32x4 v = {op[4 * nt], op[4 * nt + 1], op[4 * nt + 2], op[4 * nt + 3]};
             *reinterpret_cast<f32x4*>(row + k0) = v;
@@ -351,15 +352,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? (NT <= 10 ? 4 : 2) : 1) void mlp
         float rgb[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            float part = 0.0f;
-            const float* wr = lds_wrgb + (ch * 4 + g) * KD;
-#pragma unroll
-            for (int s = 0; s < KD; s += 4) {
-                const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + s);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) part = fmaf(v[s + q], w4[q], part);
-            }
-            const float x = group_sum(part) + tail_bias[1 + ch];
+            const float x = group_sum(head_chain<NTD>(v, lds_wrgb + (ch * 4 + g) * KD, 0.0f)) + tail_bias[1 + ch];
             rgb[ch] = 1.0f / (1.0f + expf(-x));
         }
         if (valid && g == 0) {
@@ -375,13 +368,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? (NT <= 10 ? 4 : 2) : 1) void mlp
 // (hidden columns only; the encodings have no gradient) -- with the padded width classes of this header, ReLU' read off the
 // taped activations (a zero activation passes no gradient: the subgradient autograd uses) and each delta stored as rows of
 // the real width once its stage is done.  Stream: [layers_dir.0^T | fc_feat^T |] layers_xyz[L-2 .. 0]^T (mlp_api.hip).
-template <int NT>
+template <int NT, int T0 = 0>
 __device__ __forceinline__ void relu_gate(const f32x4 (&acc)[NT], const float* base, int width, int64_t sample, float (&op)[4 * NT], int g) {
     const float* row = base + sample * width;      // the taped activation of this lane's sample, read tile by tile (no second register array)
     const bool vec = (width & 3) == 0;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        const int k0 = 16 * nt + 4 * g;
+        const int k0 = 16 * (T0 + nt) + 4 * g;
         f32x4 a = {0.0f, 0.0f, 0.0f, 0.0f};
         if (vec && k0 + 3 < width) a = *reinterpret_cast<const f32x4*>(row + k0);
         else {

@@ -124,55 +124,6 @@ __device__ __forceinline__ void gs_stage_hidden(f32x4 (&acc)[N], const float (&o
     }
 }
 
-template <int NT, int HF, int N>
-__device__ __forceinline__ void gs_load_bias(f32x4 (&acc)[N], const float* bias, int g) {
-    static_assert(N == GsHalf<NT, HF>::N, "this wave's tiles");
-#pragma unroll
-    for (int i = 0; i < GsHalf<NT, HF>::N; ++i) acc[i] = *reinterpret_cast<const f32x4*>(bias + 16 * (GsHalf<NT, HF>::T0 + i) + 4 * g);
-}
-
-template <int N, bool RELU>
-__device__ __forceinline__ void gs_acc_to_own(const f32x4 (&acc)[N], float (&own)[4 * N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) own[4 * i + r] = RELU ? fmaxf(acc[i][r], 0.0f) : acc[i][r];
-}
-
-// this wave's stretch of a head chain (alpha_gemv's order: k-step 4 tile + q ascending), continuing from `start`
-template <int NT, int HF, int N4>
-__device__ __forceinline__ float gs_chain(const float (&own)[N4], const float* row, float start) {
-    static_assert(N4 == 4 * GsHalf<NT, HF>::N, "this wave's tiles");
-    float part = start;
-#pragma unroll
-    for (int i = 0; i < GsHalf<NT, HF>::N; ++i) {
-        const f32x4 w4 = *reinterpret_cast<const f32x4*>(row + 4 * (GsHalf<NT, HF>::T0 + i));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) part = fmaf(own[4 * i + q], w4[q], part);
-    }
-    return part;
-}
-
-// rows of the real width, this wave's tiles only (store_rows_g / load_rows_g / relu_gate of mlp_device_g.h)
-template <int NT, int HF, int N4>
-__device__ __forceinline__ void gs_store_rows(float* base, int width, int64_t sample, bool valid, const float (&own)[N4], int g) {
-    static_assert(N4 == 4 * GsHalf<NT, HF>::N, "this wave's tiles");
-    if (!valid) return;
-    float* row = base + sample * width;
-    const bool vec = (width & 3) == 0;
-#pragma unroll
-    for (int i = 0; i < GsHalf<NT, HF>::N; ++i) {
-        const int k0 = 16 * (GsHalf<NT, HF>::T0 + i) + 4 * g;
-        if (vec && k0 + 3 < width) {
-            *reinterpret_cast<f32x4*>(row + k0) = f32x4{own[4 * i], own[4 * i + 1], own[4 * i + 2], own[4 * i + 3]};
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (k0 + r < width) row[k0 + r] = own[4 * i + r];
-        }
-    }
-}
-
 // the stages of one encoding's columns for this wave's tiles (enc_stages_g of mlp_device_g.h: one part, or -- LONG -- two)
 template <int NTO, int HF, int KCH, bool LONG, int N>
 __device__ __forceinline__ void gs_enc_stages(f32x4 (&acc)[N], const float (&x)[3], const GEncArg* tab, int ns, int ident, int ch, int g,
@@ -237,12 +188,12 @@ __device__ __forceinline__ void gs_forward(const MlpArgs& args, const int num_la
         float own[4 * T::N];
         const char* gw = args.wstream;
         // ---- layer1: xyz_enc -> H, no activation (models.py:62)
-        gs_load_bias<NT, HF>(acc, lds_bias, g);
+        load_bias<T::N, T::T0>(acc, lds_bias, g);
         if constexpr (!LONG) gs_stage_regs<NT, HF, G_ENC_STEPS, KCH, true>(acc, encx, chx, gw, gw + enc_x_bytes, FIRST_H, lds, SLOT, par, wave, lane);
         else gs_enc_stages<NT, HF, KCH, true>(acc, p, lds_tab, args.g_nsx, args.g_idx, chx, opaque(g), gw, gw + enc_x_bytes, FIRST_H, lds, SLOT, par, wave, lane);
         gw += enc_x_bytes;
-        gs_acc_to_own<T::N, false>(acc, own);
-        if constexpr (TAPE) gs_store_rows<NT, HF>(args.tape_h, args.g_h, sample, valid, own, g);
+        acc_to_operand<T::N, false>(acc, own);
+        if constexpr (TAPE) store_rows_g<T::N, T::T0>(args.tape_h, args.g_h, sample, valid, own, g);
 
         // ---- layers_xyz[0 .. L-2], then (full evaluation only) fc_feat as iteration L-1 (models.py:63-70)
         float sigma = 0.0f;
@@ -251,13 +202,13 @@ __device__ __forceinline__ void gs_forward(const MlpArgs& args, const int num_la
         for (int i = 0; i < trunk_iters; ++i) {
             const bool is_feat = i == num_layers - 1;
             // fc_alpha on the pre-feature activation: the first wave's stretch of the chain travels with the first tiles
-            if (is_feat && HF == 0) part[0] = gs_chain<NT, HF>(own, lds_walpha + g * (HP / 4), 0.0f);
+            if (is_feat && HF == 0) part[0] = head_chain<T::N, T::T0>(own, lds_walpha + g * (HP / 4), 0.0f);
             gs_publish_first<NT, HF>(own, xch, lane);
             __syncthreads();
-            if (is_feat && HF == 1) sigma = group_sum(gs_chain<NT, HF>(own, lds_walpha + g * (HP / 4), part[0])) + tail_bias[0];
+            if (is_feat && HF == 1) sigma = group_sum(head_chain<T::N, T::T0>(own, lds_walpha + g * (HP / 4), part[0])) + tail_bias[0];
             const bool skip = !is_feat && ((args.skip_mask >> i) & 1u);
             const bool last_density = density_only && i == num_layers - 2;
-            gs_load_bias<NT, HF>(acc, lds_bias + HP * (1 + i), g);
+            load_bias<T::N, T::T0>(acc, lds_bias + HP * (1 + i), g);
             {
                 const char* after = gw + KH * STEP;
                 const char* tsrc = after;
@@ -277,10 +228,10 @@ __device__ __forceinline__ void gs_forward(const MlpArgs& args, const int num_la
                 else gs_enc_stages<NT, HF, KCH, true>(acc, p, lds_tab, args.g_nsx, args.g_idx, chx, opaque(g), gw, tsrc, tbytes, lds, SLOT, par, wave, lane);
                 gw = after;
             }
-            gs_acc_to_own<T::N, true>(acc, own);
+            acc_to_operand<T::N, true>(acc, own);
             if constexpr (TAPE) {
                 float* dst = is_feat ? args.tape_feat : args.tape_h + (int64_t)(1 + i) * args.n * args.g_h;
-                gs_store_rows<NT, HF>(dst, args.g_h, sample, valid, own, g);
+                store_rows_g<T::N, T::T0>(dst, args.g_h, sample, valid, own, g);
             }
         }
 
@@ -290,14 +241,14 @@ __device__ __forceinline__ void gs_forward(const MlpArgs& args, const int num_la
             if (HF == 0) {
 #pragma unroll
                 for (int ch = 0; ch < 4; ++ch)
-                    if (ch < rows) part[64 * ch] = gs_chain<NT, HF>(own, row_of(ch), 0.0f);
+                    if (ch < rows) part[64 * ch] = head_chain<T::N, T::T0>(own, row_of(ch), 0.0f);
             }
             __syncthreads();
             if (HF == 1) {
                 float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int ch = 0; ch < 4; ++ch)
-                    if (ch < rows) x[ch] = group_sum(gs_chain<NT, HF>(own, row_of(ch), part[64 * ch])) + tail_bias[ch];
+                    if (ch < rows) x[ch] = group_sum(head_chain<T::N, T::T0>(own, row_of(ch), part[64 * ch])) + tail_bias[ch];
                 if (flat) {
                     if (valid && g == 0) {
                         f32x4 o4;
@@ -316,7 +267,7 @@ __device__ __forceinline__ void gs_forward(const MlpArgs& args, const int num_la
         float v[4 * D::N];
         gs_publish_first<NT, HF>(own, xch, lane);
         __syncthreads();
-        gs_load_bias<NTD, HF>(accd, lds_bias + HP * (1 + num_layers), g);
+        load_bias<D::N, D::T0>(accd, lds_bias + HP * (1 + num_layers), g);
         {
             const char* after = gw + KH * STEPD;
             const bool has_enc = chd > 0;
@@ -326,20 +277,20 @@ __device__ __forceinline__ void gs_forward(const MlpArgs& args, const int num_la
             if (has_enc) gs_enc_stages<NTD, HF, KCH, LONG>(accd, d, lds_tab + (LONG ? G_ENC_PARTS : 1) * G_ENC_ARGS, args.g_nsd, args.g_idd, chd, g, gw, args.wstream,
                                                            wrap_bytes, lds, SLOT, par, wave, lane);
         }
-        gs_acc_to_own<D::N, true>(accd, v);
-        if constexpr (TAPE) gs_store_rows<NTD, HF>(args.tape_v, args.g_hd, sample, valid, v, g);
+        acc_to_operand<D::N, true>(accd, v);
+        if constexpr (TAPE) store_rows_g<D::N, D::T0>(args.tape_v, args.g_hd, sample, valid, v, g);
 
         // ---- fc_rgb + sigmoid (models.py:75): three chains over the view activation, handed from the first wave to the second
         if (HF == 0) {
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) part[64 * (1 + ch)] = gs_chain<NTD, HF>(v, lds_wrgb + (ch * 4 + g) * KD, 0.0f);
+            for (int ch = 0; ch < 3; ++ch) part[64 * (1 + ch)] = head_chain<D::N, D::T0>(v, lds_wrgb + (ch * 4 + g) * KD, 0.0f);
         }
         __syncthreads();
         if (HF == 1) {
             f32x4 o4;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) {
-                const float x = group_sum(gs_chain<NTD, HF>(v, lds_wrgb + (ch * 4 + g) * KD, part[64 * (1 + ch)])) + tail_bias[1 + ch];
+                const float x = group_sum(head_chain<D::N, D::T0>(v, lds_wrgb + (ch * 4 + g) * KD, part[64 * (1 + ch)])) + tail_bias[1 + ch];
                 o4[ch] = 1.0f / (1.0f + expf(-x));
             }
             o4[3] = sigma;
@@ -376,25 +327,6 @@ __global__ __launch_bounds__(2 * GS_PAIRS * 64, 2) void mlp_kernel_gs(const MlpA
 // ---- delta propagation (mlp_backward_kernel_g of mlp_device_g.h) on the same split: the transposed layers in reverse order, each
 // wave of a pair producing its half of a delta's tiles, gating them with ITS tiles of the taped activation and storing ITS part of
 // every delta row; the other half of the delta reaches the next stage through the exchange slots as in the forward kernel.
-template <int NT, int HF, int N, int N4>
-__device__ __forceinline__ void gs_relu_gate(const f32x4 (&acc)[N], const float* base, int width, int64_t sample, float (&own)[N4], int g) {
-    static_assert(N == GsHalf<NT, HF>::N && N4 == 4 * N, "this wave's tiles");
-    const float* row = base + sample * width;
-    const bool vec = (width & 3) == 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const int k0 = 16 * (GsHalf<NT, HF>::T0 + i) + 4 * g;
-        f32x4 a = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (vec && k0 + 3 < width) a = *reinterpret_cast<const f32x4*>(row + k0);
-        else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] = k0 + r < width ? row[k0 + r] : 0.0f;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) own[4 * i + r] = a[r] > 0.0f ? acc[i][r] : 0.0f;
-    }
-}
-
 template <int NT, int KCH, int HF>
 __device__ __forceinline__ void gs_backward(const MlpBwdArgs& args, const int num_layers, const int flat, char* lds,
                                             const float* lds_walpha, const float* lds_wrgb, const int wave, const int lane) {
@@ -469,7 +401,7 @@ __device__ __forceinline__ void gs_backward(const MlpBwdArgs& args, const int nu
                     }
                 }
             }
-            gs_store_rows<NTD, HF>(args.d_v, HD, sample, valid, dv, g);
+            store_rows_g<D::N, D::T0>(args.d_v, HD, sample, valid, dv, g);
             // ---- layers_dir.0^T (hidden columns): -> delta at relu(fc_feat) -> gated -> delta at fc_feat's output
 #pragma unroll
             for (int i = 0; i < T::N; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -477,8 +409,8 @@ __device__ __forceinline__ void gs_backward(const MlpBwdArgs& args, const int nu
             __syncthreads();
             gs_stage_hidden<NTD, NT, HF, KCH>(acc, dv, xch, gw, gw + KD * STEP, FIRST, lds, SLOT, par, wave, lane);
             gw += KD * STEP;
-            gs_relu_gate<NT, HF>(acc, args.tape_feat, H, sidx, own, g);
-            gs_store_rows<NT, HF>(args.d_feat, H, sample, valid, own, g);
+            relu_gate<T::N, T::T0>(acc, args.tape_feat, H, sidx, own, g);
+            store_rows_g<T::N, T::T0>(args.d_feat, H, sample, valid, own, g);
             // ---- fc_feat^T + fc_alpha^T: delta at the output of layers_xyz[L-2]
 #pragma unroll
             for (int i = 0; i < T::N; ++i) {
@@ -490,8 +422,8 @@ __device__ __forceinline__ void gs_backward(const MlpBwdArgs& args, const int nu
             gs_stage_hidden<NT, NT, HF, KCH>(acc, own, xch, gw, gw + KH * STEP, FIRST, lds, SLOT, par, wave, lane);
             gw += KH * STEP;
         }
-        gs_relu_gate<NT, HF>(acc, args.tape_h + (int64_t)(L - 1) * args.n * H, H, sidx, own, g);
-        gs_store_rows<NT, HF>(args.d_h + (int64_t)(L - 1) * args.n * H, H, sample, valid, own, g);
+        relu_gate<T::N, T::T0>(acc, args.tape_h + (int64_t)(L - 1) * args.n * H, H, sidx, own, g);
+        store_rows_g<T::N, T::T0>(args.d_h + (int64_t)(L - 1) * args.n * H, H, sample, valid, own, g);
         // ---- layers_xyz[i]^T, i = L-2 .. 0: delta at the input of layers_xyz[i] (gated by the ReLU of layers_xyz[i-1]; layer1 has none)
 #pragma unroll 1
         for (int i = L - 2; i >= 0; --i) {
@@ -503,9 +435,9 @@ __device__ __forceinline__ void gs_backward(const MlpBwdArgs& args, const int nu
             gs_stage_hidden<NT, NT, HF, KCH>(acc, own, xch, gw, i == 0 ? args.wstream : after, i == 0 ? wrap_bytes : FIRST, lds, SLOT, par,
                                              wave, lane);
             gw = after;
-            if (i > 0) gs_relu_gate<NT, HF>(acc, args.tape_h + (int64_t)i * args.n * H, H, sidx, own, g);
-            else gs_acc_to_own<T::N, false>(acc, own);
-            gs_store_rows<NT, HF>(args.d_h + (int64_t)i * args.n * H, H, sample, valid, own, g);
+            if (i > 0) relu_gate<T::N, T::T0>(acc, args.tape_h + (int64_t)i * args.n * H, H, sidx, own, g);
+            else acc_to_operand<T::N, false>(acc, own);
+            store_rows_g<T::N, T::T0>(args.d_h + (int64_t)i * args.n * H, H, sample, valid, own, g);
         }
     }
 }

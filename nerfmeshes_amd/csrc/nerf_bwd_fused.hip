@@ -657,16 +657,12 @@ int nm_mlp_backward_fused(nm_mlp* m, int64_t n, const nm_mlp_tape* tape, const f
     if (int rc = nm_mlp_export_layer1_transposed(m, w1t, stream_)) return rc;
     fa.w1t = w1t;
     fa.dx = 6 * d.num_encoding_fn_xyz + (d.include_input_xyz ? 3 : 0);
-    const int64_t wg_iters = n / FB_ROWS;
-    const int grid = (int)(wg_iters < cus ? wg_iters : cus);
-    const auto kernel = L <= 4 ? &mlp_backward_dw64_kernel<4> : &mlp_backward_dw64_kernel<FB_MAXL>;
-    if (int rc = ensure_dynamic_lds((const void*)kernel, FB_LDS)) return rc;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), FB_LDS, stream, a, fa, L);
-    // ---- the order-fixed reduction of the per-workgroup partials into the gradient tensors
+    // ---- the jobs of the order-fixed reduction of the per-workgroup partials into the gradient tensors (launched behind the kernel)
     const int dx = 6 * d.num_encoding_fn_xyz + (d.include_input_xyz ? 3 : 0), dd = 6 * d.num_encoding_fn_dir + (d.include_input_dir ? 3 : 0);
     FbReduce rb;
     int nj = 0;
-    auto job = [&](int off, int rows, int cols, int ld, int col0, float* out) { rb.job[nj++] = FbReduceJob{off, rows, cols, ld, col0, 64, 16, 1, 0, out}; };
+    auto push = [&](const FbReduceJob& j) { if (nj < FB_MAX_JOBS) rb.job[nj] = j; ++nj; };     // never past the array; nj is checked below
+    auto job = [&](int off, int rows, int cols, int ld, int col0, float* out) { push(FbReduceJob{off, rows, cols, ld, col0, 64, 16, 1, 0, out}); };
     job(FB_P_DIRF, 32, 64, 64 + dd, 0, grads->dir_weight);
     if (dd > 0) job(FB_P_DIRE, 32, dd, 64 + dd, 64, grads->dir_weight);
     job(FB_P_FEAT, 64, 64, 64, 0, grads->feat_weight);
@@ -676,15 +672,21 @@ int nm_mlp_backward_fused(nm_mlp* m, int64_t n, const nm_mlp_tape* tape, const f
         if (skip) job(FB_P_SKIP, 64, dx, 64 + dx, 64, grads->xyz_weight[i]);
     }
     job(FB_P_L1, 64, dx, dx, 0, grads->layer1_weight);
-    rb.job[nj++] = FbReduceJob{FB_P_HEAD + FB_H_RGB, 3, 32, 32, 0, 16, 64, 1, 0, grads->rgb_weight};            // rows 0..2 of d_last^T @ v
-    rb.job[nj++] = FbReduceJob{FB_P_HEAD + FB_H_ALPHA + 3 * 16, 1, 64, 64, 0, 16, 64, 1, 0, grads->alpha_weight};   // row 3 of d_last^T @ h[L-1]
+    push(FbReduceJob{FB_P_HEAD + FB_H_RGB, 3, 32, 32, 0, 16, 64, 1, 0, grads->rgb_weight});            // rows 0..2 of d_last^T @ v
+    push(FbReduceJob{FB_P_HEAD + FB_H_ALPHA + 3 * 16, 1, 64, 64, 0, 16, 64, 1, 0, grads->alpha_weight});   // row 3 of d_last^T @ h[L-1]
     rb.first_bias = nj;
     job(FB_P_BIAS + FB_B_DIR, 32, 1, 1, 0, grads->dir_bias);
     job(FB_P_BIAS + FB_B_FEAT, 64, 1, 1, 0, grads->feat_bias);
     for (int i = 0; i <= L - 2; ++i) job(FB_P_BIAS + FB_B_XYZ + i * 64, 64, 1, 1, 0, grads->xyz_bias[i]);
     job(FB_P_BIAS + FB_B_L1, 64, 1, 1, 0, grads->layer1_bias);
-    rb.job[nj++] = FbReduceJob{FB_P_HEAD + FB_H_BIAS, 3, 1, 1, 0, 0, 0, 1, 0, grads->rgb_bias};
-    rb.job[nj++] = FbReduceJob{FB_P_HEAD + FB_H_BIAS + 3, 1, 1, 1, 0, 0, 0, 1, 0, grads->alpha_bias};
+    push(FbReduceJob{FB_P_HEAD + FB_H_BIAS, 3, 1, 1, 0, 0, 0, 1, 0, grads->rgb_bias});
+    push(FbReduceJob{FB_P_HEAD + FB_H_BIAS + 3, 1, 1, 1, 0, 0, 0, 1, 0, grads->alpha_bias});
+    NM_REQUIRE(nj <= FB_MAX_JOBS, "fused backward: more reduction jobs than FbReduce holds");
+    const int64_t wg_iters = n / FB_ROWS;
+    const int grid = (int)(wg_iters < cus ? wg_iters : cus);
+    const auto kernel = L <= 4 ? &mlp_backward_dw64_kernel<4> : &mlp_backward_dw64_kernel<FB_MAXL>;
+    if (int rc = ensure_dynamic_lds((const void*)kernel, FB_LDS)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), FB_LDS, stream, a, fa, L);
     hipLaunchKernelGGL(fb_reduce_kernel, dim3(64, nj), dim3(256), 0, stream, fa.partial, rb, grid);
     NM_HIP_CHECK(hipGetLastError());
     return 0;

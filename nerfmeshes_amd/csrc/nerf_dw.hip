@@ -42,7 +42,6 @@ struct DwArgs {
 // x / per_job, sample part x % per_job.  With J jobs a job gets 1 / J of the CUs and J times the samples per workgroup: the
 // same matrix work, but J times fewer partials to write and to reduce (8 x 256^2 layers: 64 MB instead of 512 MB per network)
 // and one launch + one reduction instead of J of each.
-constexpr int DW_MAX_JOBS = 16;
 struct DwBatch {
     DwArgs job[DW_MAX_JOBS];
     int32_t jobs, per_job;
@@ -212,9 +211,8 @@ __global__ __launch_bounds__(512, 2) void dw_kernel(const DwBatch batch) {
 // order-fixed reduction of the partials: out[o][c] = sum_p partial[p][o][c] for c < cols (padding columns dropped); the
 // threads past rows * cols reduce the bias partials.  The additions run in index order p = 0, 1, 2, ... (deterministic);
 // the loads of 16 partials are issued together so the loop is bandwidth- rather than latency-bound.  One launch serves a
-// batch of jobs (blockIdx.y = job).
-struct DwReduceJob { const float* partial; const float* partial_bias; float* out; float* out_bias; int32_t out_ld, out_col0; };
-struct DwReduceBatch { DwReduceJob job[DW_MAX_JOBS]; };
+// batch of jobs (blockIdx.y = job; DwReduceBatch: nm_internal.h).  The general unit's dw_reduce_g_kernel is this kernel with the two
+// part strides as arguments; the tuned shapes keep this form: through the general one the 256-wide products measured about 3 % slower (readings: DESIGN.md 3.5, weight gradients).
 __global__ void dw_reduce_batch_kernel(const DwReduceBatch rb, int parts, int rows, int ld, int cols) {
     const DwReduceJob j = rb.job[blockIdx.y];
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -254,7 +252,7 @@ __global__ void dw_reduce_batch_kernel(const DwReduceBatch rb, int parts, int ro
 // rows and the product is HBM-bound anyway (act is read once: 2 FLOP / B), so this is a VALU kernel: a workgroup owns a
 // contiguous slice of samples, a thread four columns (one 16-byte load per row; a 256-wide row is one wavefront-wide
 // 1 KiB load, dlast[n] a broadcast 16-byte load), 16 fp32 accumulators.  The slice partials go through the same
-// order-fixed second pass as the MFMA kernel's (head_reduce_kernel: parts in index order -> deterministic).
+// order-fixed second pass as the MFMA kernel's (launch_head_reduce, nerf_dw_g.hip: parts in index order -> deterministic).
 template <int K>
 __global__ __launch_bounds__(256) void head_grad_kernel(const float* __restrict__ dlast, const float* __restrict__ act,
                                                         int64_t n, int rows_per_part, float* __restrict__ partial,
@@ -303,42 +301,6 @@ __global__ __launch_bounds__(256) void head_grad_kernel(const float* __restrict_
         reinterpret_cast<float4*>(partial_bias)[blockIdx.x] = s;
     }
 }
-
-// out[e] = sum_p partial[p][e], e < elems (+ the 4 bias sums behind them): 4 part-groups per element added up
-// sequentially (16 loads in flight), then the 4 group sums in index order.
-__global__ __launch_bounds__(256) void head_reduce_kernel(const float* __restrict__ partial,
-                                                          const float* __restrict__ partial_bias, int parts, int elems,
-                                                          float* __restrict__ out, float* __restrict__ out_bias) {
-    __shared__ float grp[4][64];
-    const int e = blockIdx.x * 64 + (threadIdx.x & 63), pg = threadIdx.x >> 6;
-    const int per = (parts + 3) / 4;
-    const int p0 = pg * per, p1 = p0 + per < parts ? p0 + per : parts;
-    const float* p = nullptr;
-    int64_t stride = 0;
-    if (e < elems) { p = partial + e; stride = elems; }
-    else if (e < elems + 4) { p = partial_bias + (e - elems); stride = 4; }
-    float s = 0.0f;
-    if (p) {
-        int k = p0;
-        for (; k + 16 <= p1; k += 16) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = p[(k + u) * stride];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) s += v[u];
-        }
-        for (; k < p1; ++k) s += p[k * stride];
-    }
-    grp[pg][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (pg == 0 && p) {
-        const float t = ((grp[0][threadIdx.x] + grp[1][threadIdx.x]) + grp[2][threadIdx.x]) + grp[3][threadIdx.x];
-        if (e < elems) out[e] = t;
-        else if (out_bias) out_bias[e - elems] = t;
-    }
-}
-
-constexpr int HEAD_MAX_PARTS = 512;
 
 struct DwPlan {
     int ab, bb, ksplit, rows;
@@ -451,9 +413,7 @@ int head_grad_tuned(const float* d_dlast, const float* d_act, int32_t in_feature
         hipLaunchKernelGGL(head_grad_kernel<128>, dim3(parts), dim3(256), 0, stream, d_dlast, d_act, n, (int)rows, partial, partial_bias);
     else
         hipLaunchKernelGGL(head_grad_kernel<64>, dim3(parts), dim3(256), 0, stream, d_dlast, d_act, n, (int)rows, partial, partial_bias);
-    const int elems = 4 * in_features;
-    hipLaunchKernelGGL(head_reduce_kernel, dim3((elems + 4 + 63) / 64), dim3(256), 0, stream, partial, partial_bias, parts,
-                       elems, d_dw, d_dbias);
+    launch_head_reduce(partial, partial_bias, parts, 4 * in_features, d_dw, d_dbias, stream);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }

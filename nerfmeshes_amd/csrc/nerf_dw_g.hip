@@ -76,11 +76,10 @@ struct DwGArgs {
 
 // a batch of products of ONE shape, stride set and row count (nm_weight_grad_batch): everything in `common` but the four
 // per-job pointers.  Workgroup x serves job x / per_job, sample part x % per_job (see DwBatch in nerf_dw.hip for the why).
-constexpr int DWG_MAX_JOBS = 16;
 struct DwGJob { const float* a; const float* b; float* partial; float* partial_bias; };
 struct DwGBatch {
     DwGArgs common;
-    DwGJob job[DWG_MAX_JOBS];
+    DwGJob job[DW_MAX_JOBS];
     int32_t jobs, per_job;
 };
 
@@ -351,10 +350,8 @@ __global__ __launch_bounds__(512, 2) void dw_kernel_g(const DwGBatch batch) {
 
 // order-fixed reduction of the partials (parts in index order, 16 loads in flight); threads past rows * cols do the biases;
 // blockIdx.y = job of a batch
-struct DwGReduceJob { const float* partial; const float* partial_bias; float* out; float* out_bias; int32_t out_ld, out_col0; };
-struct DwGReduceBatch { DwGReduceJob job[DWG_MAX_JOBS]; };
-__global__ void dw_reduce_g_kernel(const DwGReduceBatch rb, int parts, int64_t part_stride, int bias_stride, int rows, int ld, int cols) {
-    const DwGReduceJob j = rb.job[blockIdx.y];
+__global__ void dw_reduce_g_kernel(const DwReduceBatch rb, int parts, int64_t part_stride, int bias_stride, int rows, int ld, int cols) {
+    const DwReduceJob j = rb.job[blockIdx.y];
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t elems = (int64_t)rows * cols;
     const float* p;
@@ -468,7 +465,7 @@ __global__ __launch_bounds__(256) void head_grad_g_kernel(const float* __restric
     }
 }
 
-__global__ __launch_bounds__(256) void head_reduce_g_kernel(const float* __restrict__ partial,
+__global__ __launch_bounds__(256) void head_reduce_kernel(const float* __restrict__ partial,
                                                             const float* __restrict__ partial_bias, int parts, int elems,
                                                             float* __restrict__ out, float* __restrict__ out_bias) {
     __shared__ float grp[4][64];
@@ -500,6 +497,12 @@ __global__ __launch_bounds__(256) void head_reduce_g_kernel(const float* __restr
     }
 }
 
+void launch_head_reduce(const float* partial, const float* partial_bias, int parts, int elems, float* out, float* out_bias,
+                        hipStream_t stream) {
+    hipLaunchKernelGGL(head_reduce_kernel, dim3((elems + 4 + 63) / 64), dim3(256), 0, stream, partial, partial_bias, parts, elems, out,
+                       out_bias);
+}
+
 // ---- host side: the planner ------------------------------------------------------------------------------------------
 typedef void (*DwGKernel)(const DwGBatch);
 constexpr int DWG_MAX_TA = 6, DWG_MAX_TB = 8, DWG_MAX_TILES = 36;     // tiles per wave: TA x TB <= 36 (144 accumulator registers)
@@ -524,7 +527,6 @@ static const DwGKernel g_dwg_kernels[DWG_MAX_TA][DWG_MAX_TB] = {NM_DWG_ROW(1), N
 
 constexpr int DWG_LDS_BYTES = 160 * 1024;
 constexpr int DWG_SLACK = 2048;          // what the last image's padded-tile reads may run past it
-constexpr int HEAD_G_MAX_PARTS = 512;
 
 struct DwGPlan {
     int nba, nbb, wa, wb, wk, ta, tb, rows, grid_x;
@@ -709,7 +711,7 @@ extern "C" int64_t nm_weight_grad_workspace_bytes_ex(int32_t out_features, int32
 extern "C" int nm_weight_grad_batch(int device_cus, int32_t jobs, const nm_weight_grad_job* job, int32_t out_features,
                                     int32_t delta_stride, int32_t in_features, int32_t act_stride, int64_t n, void* d_workspace,
                                     void* stream_) {
-    NM_REQUIRE(job && jobs >= 1 && jobs <= DWG_MAX_JOBS && d_workspace && n > 0, "bad argument");
+    NM_REQUIRE(job && jobs >= 1 && jobs <= DW_MAX_JOBS && d_workspace && n > 0, "bad argument");
     NM_REQUIRE(out_features >= 1 && in_features >= 1 && delta_stride >= out_features && act_stride >= in_features,
                "weight_grad: a row stride is smaller than its feature count");
     bool a_x4 = true, b_x4 = true;
@@ -757,12 +759,12 @@ extern "C" int nm_weight_grad_batch(int device_cus, int32_t jobs, const nm_weigh
     const int parts = (int)per_job * p.wk;
     const int64_t job_floats = (int64_t)parts * ((int64_t)a.out_pad * a.in_pad + a.out_pad);
     batch.jobs = jobs; batch.per_job = (int)per_job;
-    DwGReduceBatch rb;
+    DwReduceBatch rb;
     for (int j = 0; j < jobs; ++j) {
         float* partial = static_cast<float*>(d_workspace) + j * job_floats;
         float* partial_bias = partial + (int64_t)parts * a.out_pad * a.in_pad;
         batch.job[j] = DwGJob{job[j].d_delta, job[j].d_act, partial, partial_bias};
-        rb.job[j] = DwGReduceJob{partial, partial_bias, job[j].d_dw, job[j].d_dbias, job[j].dw_ld, job[j].dw_col0};
+        rb.job[j] = DwReduceJob{partial, partial_bias, job[j].d_dw, job[j].d_dbias, job[j].dw_ld, job[j].dw_col0};
     }
     const int lds_bytes = 4 * (a.A.img + a.B.img) + DWG_SLACK;
     NM_REQUIRE(lds_bytes <= DWG_LDS_BYTES, "weight_grad: LDS budget exceeded");
@@ -800,7 +802,7 @@ extern "C" int nm_weight_grad_plan(int32_t out_features, int32_t delta_stride, i
 }
 
 extern "C" int64_t nm_head_grad_workspace_bytes_ex(int32_t in_features) {
-    return in_features > 0 ? (int64_t)HEAD_G_MAX_PARTS * 4 * ((int64_t)in_features + 1) * 4 : 0;
+    return in_features > 0 ? (int64_t)HEAD_MAX_PARTS * 4 * ((int64_t)in_features + 1) * 4 : 0;
 }
 
 // d_dlast (n, 4) contiguous, d_act (n, >= in_features) with row stride act_stride: any width.
@@ -818,11 +820,11 @@ extern "C" int nm_head_grad_ex(const float* d_dlast, const float* d_act, int32_t
     const int tpr = cols < 256 ? cols : 256;                     // threads per row
     const int groups = (cols + tpr - 1) / tpr;                   // column groups (grid.y): widths beyond 256 slots
     const int rpp = 256 / tpr;
-    int64_t rows = (n + HEAD_G_MAX_PARTS - 1) / HEAD_G_MAX_PARTS;
+    int64_t rows = (n + HEAD_MAX_PARTS - 1) / HEAD_MAX_PARTS;
     rows = (rows + 8 * rpp - 1) / (8 * rpp) * (8 * rpp);
     const int parts = (int)((n + rows - 1) / rows);
     float* partial = static_cast<float*>(d_workspace);
-    float* partial_bias = partial + (int64_t)HEAD_G_MAX_PARTS * 4 * in_features;
+    float* partial_bias = partial + (int64_t)HEAD_MAX_PARTS * 4 * in_features;
     const int lds_bytes = (rpp * 4 * tpr * vec + rpp * 4) * 4;
     if (vec4)
         hipLaunchKernelGGL(head_grad_g_kernel<4>, dim3(parts, groups), dim3(256), lds_bytes, stream, d_dlast, d_act, act_stride,
@@ -830,9 +832,7 @@ extern "C" int nm_head_grad_ex(const float* d_dlast, const float* d_act, int32_t
     else
         hipLaunchKernelGGL(head_grad_g_kernel<1>, dim3(parts, groups), dim3(256), lds_bytes, stream, d_dlast, d_act, act_stride,
                            in_features, tpr, n, (int)rows, partial, partial_bias);
-    const int elems = 4 * in_features;
-    hipLaunchKernelGGL(head_reduce_g_kernel, dim3((elems + 4 + 63) / 64), dim3(256), 0, stream, partial, partial_bias, parts,
-                       elems, d_dw, d_dbias);
+    launch_head_reduce(partial, partial_bias, parts, 4 * in_features, d_dw, d_dbias, stream);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }

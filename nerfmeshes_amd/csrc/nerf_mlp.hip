@@ -161,13 +161,11 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args_in, int density_only, hipStr
         NM_REQUIRE(b && m->d_stream_b3, "no bf16x3 kernel for this network");
         const int lds_bytes = 3 * b->chunk_units * B3_UNIT + tuned_cache_bytes(H, L, 3 * H / 2 + 32);   // + the two band tables
         NM_REQUIRE(lds_bytes <= 160 * 1024, "LDS budget exceeded (bf16x3 ring + bias cache): too many layers");
-        auto b3_kernel = b->kernel;
-        unsigned b3_threads = 512;
-        if (int rc = ensure_dynamic_lds((const void*)b3_kernel, lds_bytes)) return rc;
+        if (int rc = ensure_dynamic_lds((const void*)b->kernel, lds_bytes)) return rc;
         MlpArgs a = args;
         a.wstream = static_cast<const char*>(m->d_stream_b3);
         const unsigned grid = persistent_grid((a.n + 127) / 128, m->num_cus);
-        hipLaunchKernelGGL(b3_kernel, dim3(grid), dim3(b3_threads), lds_bytes, stream, a, L, density_only);
+        hipLaunchKernelGGL(b->kernel, dim3(grid), dim3(512), lds_bytes, stream, a, L, density_only);
         NM_HIP_CHECK(hipGetLastError());
         return 0;
     }

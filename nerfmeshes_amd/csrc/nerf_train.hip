@@ -231,13 +231,12 @@ __global__ __launch_bounds__(256) void encode_samples_rows_kernel(const EncodeAr
 // ---- plan tables -------------------------------------------------------------------------------------------
 struct TrainPlan {
     int H, FX, FD;
-    int ring_slots;                                                // LDS ring of mlp_kernel (mlp_device.h)
     void (*forward)(const MlpArgs, const int, const int);
     void (*forward_flat)(const MlpArgs, const int, const int);     // the taping kernel that also serves use_viewdirs = 0 networks
 };
 template <int H, int FX, int FD>
 static TrainPlan make_train_plan() {
-    return TrainPlan{H, FX, FD, 2, &mlp_kernel<H, FX, FD, 8, KC, true>, &mlp_kernel<H, FX, FD, 8, KC, true, true>};
+    return TrainPlan{H, FX, FD, &mlp_kernel<H, FX, FD, 8, KC, true>, &mlp_kernel<H, FX, FD, 8, KC, true, true>};
 }
 static const TrainPlan g_train_plans[] = {
     make_train_plan<256, 10, 4>(), make_train_plan<128, 10, 4>(), make_train_plan<64, 10, 4>(),
@@ -315,7 +314,7 @@ int nm_mlp_forward_train(nm_mlp* m, const float* d_origins, int origins_per_ray,
         a.tape_encd = flat ? nullptr : tape->d_enc_dir;
     }
     const int H = d.hidden_size, L = d.num_layers;
-    const int ring = plan->ring_slots * KC * (H / 16) * 256;
+    const int ring = 2 * KC * (H / 16) * 256;      // the 2-slot LDS ring of mlp_kernel (mlp_device.h)
     const int lds_bytes = ring + tuned_cache_bytes(H, L, flat ? 3 * H : 3 * H / 2);
     const auto kernel = flat ? plan->forward_flat : plan->forward;
     if (int rc = ensure_dynamic_lds((const void*)kernel, lds_bytes)) return rc;

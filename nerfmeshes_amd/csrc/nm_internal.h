@@ -231,6 +231,16 @@ struct DwgEpilogue { float* out; const float* bias; const float* mask; int64_t l
 int dwg_gemm(const float* A, int out, int lda, const float* B, int64_t in, int64_t ldb, int rows, float* partial, hipStream_t stream,
              const DwgEpilogue* epilogue = nullptr);
 
+// ---- what the two weight-gradient units share (nerf_dw.hip: the kernels tuned for the shipped shapes; nerf_dw_g.hip: any shape)
+constexpr int DW_MAX_JOBS = 16;          // products of one shape in one launch (nm_weight_grad_batch)
+constexpr int HEAD_MAX_PARTS = 512;      // sample slices of a head-gradient launch (sizes nm_head_grad_workspace_bytes_ex)
+// One job of the order-fixed second pass over the per-workgroup partials (dw_reduce_batch_kernel / dw_reduce_g_kernel): out[o][out_col0 + c]
+struct DwReduceJob { const float* partial; const float* partial_bias; float* out; float* out_bias; int32_t out_ld, out_col0; };
+struct DwReduceBatch { DwReduceJob job[DW_MAX_JOBS]; };
+// the heads' second pass (head_reduce_kernel, nerf_dw_g.hip): out[e] = sum_p partial[p][e], e < elems, and (out_bias non-null) the 4 bias sums
+void launch_head_reduce(const float* partial, const float* partial_bias, int parts, int elems, float* out, float* out_bias,
+                        hipStream_t stream);
+
 // The render path's two network calls (ray_ops.hip: render_impl): rays from buffers (`gen` null) or from the pose, into WORKSPACE
 // radiance that only the compositor reads, with MlpArgs::skip_empty set -- a sample with raw sigma <= 0 has alpha == weight == 0
 // exactly (no noise is added on this path), so the rgb of a tile without density is written as zeros instead of being computed.
