@@ -290,6 +290,7 @@ static int upload_indices(nm_mlp* m, const PackedIndex& px) {
     NM_HIP_CHECK(hipMalloc(&m->d_blob, m->blob_bytes));
     NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_check), 16));
     NM_HIP_CHECK(hipMemset(m->d_check, 0, 16));
+    if (m->plan->kernel_skip) NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_tile_queue), TILE_QUEUE_SLOTS * TILE_QUEUE_STRIDE * sizeof(uint32_t)));
     NM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&m->d_index), m->blob_bytes));
     NM_HIP_CHECK(hipMemcpy(m->d_index, px.index.data(), m->blob_bytes, hipMemcpyHostToDevice));
     if (m->precision == NM_PREC_BF16X3) {
@@ -574,6 +575,7 @@ void nm_mlp_destroy(nm_mlp* m) {
     if (m->d_blob) (void)hipFree(m->d_blob);
     if (m->d_index) (void)hipFree(m->d_index);
     if (m->d_check) (void)hipFree(m->d_check);
+    if (m->d_tile_queue) (void)hipFree(m->d_tile_queue);
     if (m->d_index_b3) (void)hipFree(m->d_index_b3);
     if (m->d_tmp_b3) (void)hipFree(m->d_tmp_b3);
     if (m->d_stream_b3) (void)hipFree(m->d_stream_b3);

@@ -88,6 +88,13 @@ __device__ __forceinline__ void gemm_stage3(f32x4 (&acc)[NT], const float (&b1)[
 // SKIP: the render path's instantiation (MlpArgs::skip_empty): a tile on which no sample has density writes
 // {0, 0, 0, sigma} and skips fc_feat, the view layer and fc_rgb; in ray modes with samples % 16 == 0 a tile is NW adjacent rays x
 // 16 consecutive samples (MlpArgs::ray_tiles).  A separate instantiation so that every other entry point runs the kernel it ran.
+// Its tiles cost unequal time (an empty one about 0.83 of a full one), and in ray-tile order a static stride hands a workgroup the
+// same few depth slots for its whole life -- the slots in front of the object are nearly all empty --, so SKIP draws its tiles from
+// a queue instead (MlpArgs::tile_queue): the first is blockIdx.x, every further one gridDim.x + the value one lane's
+// atomicAdd returned.  The tile after this one is claimed early in this one (behind layer1) and handed to the other waves through
+// LDS under the trunk's barriers, so the round trip is hidden and `has_next` is known before the last stage, which needs it.  A
+// workgroup makes one claim per tile it runs and stops at the first one past the end: no workgroup waits for another, and a launch
+// makes exactly wg_iters claims.
 template <int H, int FX, int FD, int NW, int KCH, bool FLAT = false, bool SKIP = false>   // FLAT: see mlp_kernel
 // Occupancy: networks up to 128 wide are compiled for FOUR waves per SIMD (128 registers: two 8-wave workgroups per CU; the
 // 128-wide instances spill 9 -- 17 registers outside the k-step loops for it).  With VALU issue time adding to matrix time on
@@ -105,6 +112,9 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
     // SKIP's vote word, behind fc_rgb's rows (the cache is 4 H (L + 4) + 16 bytes rounded up to 256: 240 bytes are spare; the
     // FLAT heads' wider rows never meet SKIP).  It holds the stamp of the last iteration on which some wave saw density.
     int* lds_vote = reinterpret_cast<int*>(lds_wrgb + 3 * H / 2);
+    // ... and behind it the two words through which lane 0 publishes its claims, alternating (the next claim is written while
+    // the last one may still be unread by a slower wave of the iteration before)
+    uint32_t* lds_claim = reinterpret_cast<uint32_t*>(lds_vote + 1);
     if (SKIP && threadIdx.x == 0) *lds_vote = 0;
     for (int i = threadIdx.x; i < nbias; i += NW * 64) lds_bias[i] = args.bias[i];
     for (int i = threadIdx.x; i < H; i += NW * 64) lds_walpha[i] = args.walpha[i];
@@ -135,8 +145,10 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
     carry[0] = *reinterpret_cast<const f32x4*>(lds + lane * 16);
     carry[1] = *reinterpret_cast<const f32x4*>(lds + lane * 16 + 1024);
 
-    for (int64_t it = blockIdx.x; it < wg_iters; it += gridDim.x) {
-        const bool has_next = it + gridDim.x < wg_iters;
+    int64_t next_it = 0;     // SKIP: the tile claimed for the iteration after this one
+    int turn = 0;
+    for (int64_t it = blockIdx.x; it < wg_iters; it = SKIP ? next_it : it + gridDim.x) {
+        bool has_next = !SKIP && it + gridDim.x < wg_iters;     // SKIP: known once the claim is read (before fc_feat)
         // linear order: wave w of iteration `it` owns 16 consecutive samples; ray_tiles: ray NW * block + w, depth slot k
         int64_t sample = (it * NW + wave) * 16 + col;
         bool valid = sample < args.n;
@@ -153,7 +165,7 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
         const float dummy[1] = {0.0f};
         float encx[N::EX];
         encode<FX, N::EX>(encx, p, args.bands_xyz, g);
-        const NextChunks wrap = enc_next(args.wstream, has_next);
+        NextChunks wrap = enc_next(args.wstream, has_next);
 
         f32x4 acc[N::NT];
         float in[N::KH];
@@ -163,6 +175,9 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
         gemm_stage3<N::NT, N::EX, 0, NW, N::LDSBUF, KCH>(acc, encx, dummy, gw, hidden_next(gw + N::EX * N::STEP), lds, slot, carry, wave, lane);
         gw += N::EX * N::STEP;
         acc_to_operand<N::NT, false>(acc, in);
+        // The claim of the tile after this one.  The compiler waits for the returned value where the atomic is issued, so it is
+        // issued here and not in the prologue: in front of the trunk's stages this wave's wait runs under its SIMD partner's MFMAs.
+        if (SKIP && threadIdx.x == 0) lds_claim[turn] = atomicAdd(args.tile_queue, 1u);
 
         // ---- layers_xyz[0 .. L-2], then (full evaluation only) fc_feat as iteration L-1 (models.py:63-70)
         float sigma = 0.0f;
@@ -180,6 +195,11 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
                 if (dense) *lds_vote = epoch;
                 __syncthreads();
                 empty_tile = __builtin_amdgcn_readfirstlane(*lds_vote) != epoch;
+                // the same barrier (and every one of the trunk before it) published the claim; nothing up to here issues the wrap-around DMA
+                next_it = (int64_t)gridDim.x + (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_claim[turn]);
+                turn ^= 1;
+                has_next = next_it < wg_iters;
+                wrap = enc_next(args.wstream, has_next);
                 if (empty_tile) break;
             }
             const bool skip = !is_feat && ((args.skip_mask >> i) & 1u);

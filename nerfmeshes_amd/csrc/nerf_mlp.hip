@@ -151,6 +151,9 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args_in, int density_only, hipStr
     if (!(args.skip_empty && p->kernel_skip && density_only == 0 && m->precision == NM_PREC_F32)) args.skip_empty = 0;
     args.ray_tiles = args.skip_empty && (args.mode == MODE_RAYS || args.mode == MODE_VIEW) && args.samples % 16 == 0;
     if (args.ray_tiles && mlp_wg_iters(args, p->wg_samples) > INT32_MAX) args.ray_tiles = 0;   // the kernel splits `it` in 32 bits
+    // the skipping kernel claims its tiles from a 32-bit counter of the handle's
+    if (args.skip_empty && (!m->d_tile_queue || mlp_wg_iters(args, p->wg_samples) > INT32_MAX)) args.skip_empty = args.ray_tiles = 0;
+    args.tile_queue = nullptr;
     if (!args.skip_empty) args.skip_count = nullptr;
     DeviceGuard guard(m->device);
     const int L = m->desc.num_layers, H = m->desc.hidden_size;
@@ -174,7 +177,16 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args_in, int density_only, hipStr
     NM_REQUIRE(lds_bytes <= 160 * 1024, "LDS budget exceeded (ring + bias cache)");
     if (int rc = ensure_dynamic_lds((const void*)kernel, lds_bytes)) return rc;
     const int64_t wg_iters = mlp_wg_iters(args, p->wg_samples);
-    const unsigned grid = persistent_grid(wg_iters, (int64_t)m->num_cus * p->wg_per_cu);
+    unsigned grid = persistent_grid(wg_iters, (int64_t)m->num_cus * p->wg_per_cu);
+    if (args.skip_empty) {
+        // Tiles of unequal cost, drawn from a queue: exactly the workgroups that are resident at once (mlp_kernel3's launch bounds
+        // put two of the networks up to 128 wide on a CU), each running until the queue is empty.  The counter is zero when the
+        // kernel starts: set in stream order, no allocation and no host synchronisation here.
+        const int64_t resident = (int64_t)m->num_cus * p->wg_per_cu * (p->H <= 128 ? 2 : 1);
+        grid = (unsigned)(wg_iters < resident ? wg_iters : resident);
+        args.tile_queue = m->d_tile_queue + (size_t)(__atomic_fetch_add(&m->tile_queue_turn, 1u, __ATOMIC_RELAXED) % TILE_QUEUE_SLOTS) * TILE_QUEUE_STRIDE;
+        NM_HIP_CHECK(hipMemsetAsync(args.tile_queue, 0, sizeof(uint32_t), stream));
+    }
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(p->NW * 64), lds_bytes, stream, args, (int)m->desc.num_layers, density_only);
     NM_HIP_CHECK(hipGetLastError());
     return 0;

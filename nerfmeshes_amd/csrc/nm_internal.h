@@ -128,10 +128,12 @@ struct MlpArgs {
     int32_t g_nsx, g_idx, g_chx;   // xyz: k-steps that carry arguments, 1 = an identity step follows, whole chunks in the stream
     int32_t g_nsd, g_idd, g_chd;   // direction encoding likewise (g_chd = 0: no encoded direction columns at all)
     int32_t g_h, g_hd;             // the REAL widths hidden_size and hidden_size // 2: row strides of the generic training tape
-    // render-internal evaluation (render_impl in ray_ops.hip only; launch_mlp clears all three where the plan has no kernel_skip)
+    // render-internal evaluation (render_impl in ray_ops.hip only; launch_mlp clears all four where the plan has no kernel_skip)
     int32_t skip_empty;      // a workgroup tile on which no sample has raw sigma > 0 gets {0, 0, 0, sigma} and skips the colour branch
     int32_t ray_tiles;       // RAYS / VIEW with samples % 16 == 0: a tile is wg_samples / 16 adjacent rays x 16 consecutive samples
     uint32_t* skip_count;    // null, or the launch's counter of skipped tiles (profiling: mlp_api.hip)
+    uint32_t* tile_queue;    // skip_empty launches: the device word their workgroups claim tiles from (mlp_device_r3.h), zero when the
+                             // launch starts; launch_mlp sets it from the handle
 };
 
 // Workgroup iterations of a tuned forward launch: THE expression, shared by launch_mlp (grid size) and the kernels (loop bound).
@@ -199,6 +201,8 @@ struct DeviceGuard {
     }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
+
+constexpr int TILE_QUEUE_SLOTS = 16, TILE_QUEUE_STRIDE = 32;    // words of nm_mlp::d_tile_queue; uint32_t between two of them
 
 // Persistent-style grid for wg_iters workgroup iterations with `resident` workgroups co-resident on the chip: a few workgroups
 // per CU queue so the tail is balanced, and the per-workgroup iteration count is even across the grid where possible.
@@ -277,4 +281,10 @@ struct nm_mlp {
     // float offset, in the packed image, of the plain copies nm_mlp_linear_layer1_finish reads: layers_xyz[0].weight (H, H),
     // layer1.weight^T (dx, H), layer1.bias (H); 0: none (layer-wise path, one-layer networks)
     size_t plain_off;
+    // Tile queues of the skipping render kernel (MlpArgs::tile_queue): TILE_QUEUE_SLOTS counter words, one cache line apart, allocated
+    // with the handle.  Every such launch takes the next word in turn and zeroes it in stream order in front of the kernel, so launches
+    // queued behind each other on one stream never share a live word, and launches on different streams do only when more than
+    // TILE_QUEUE_SLOTS of them are in flight at once.
+    uint32_t* d_tile_queue;
+    mutable uint32_t tile_queue_turn;
 };
