@@ -50,6 +50,8 @@ extern "C" {
  * surface point cloud).  Additions only. */
 /* 6, later: + nm_mesh_simplify_cluster (+ _workspace_bytes), nm_mesh_simplify_emit: mesh simplification by vertex clustering
  * (mesh_nerf --simplify-cell).  Additions only. */
+/* 6, later: + nm_mesh_smooth_build (+ _workspace_bytes), nm_mesh_smooth_run, nm_mesh_vertex_normals: Taubin smoothing of the
+ * mesh and the vertex normals of the result (mesh_nerf --smooth-iters).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -810,6 +812,69 @@ int nm_mesh_simplify_emit(const void* d_workspace, const float* d_verts, int64_t
                           int64_t num_faces, const float* d_normals, float origin_x, float origin_y, float origin_z, float cell,
                           int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
                           float* d_out_normals, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Taubin smoothing of a mesh (mesh_nerf --smooth-iters; DESIGN.md, "Mesh smoothing").  All arrays on the device: d_verts
+ * (V,3) fp32, d_faces (F,3) int32.  A uniform umbrella Laplacian applied with a factor lambda in (0, 1], then with mu in
+ * [-1, 0] (mu = 0: the second half-step is skipped, which is plain Laplacian smoothing).  Every fp32 / fp64 operation below
+ * is rounded on its own, division and sqrt correctly rounded, and every per-vertex sum is an exact integer sum, so a numpy
+ * restatement (tests/mesh_smooth.py) reproduces every output bit for bit, whatever the order of the workgroups, of a
+ * neighbour list or of the numbering.
+ *
+ *   validity   a vertex with a non-finite coordinate is BAD; a face with an index outside [0, V) (never dereferenced) is BAD.
+ *              Both are counted; a caller should treat either count as an error (hip_ops.mesh_smooth raises).  A face with
+ *              two equal corners is DEGENERATE: counted, it contributes no edge.
+ *   edges      every other face contributes its three undirected edges (min, max).  u and v are NEIGHBOURS when an edge joins
+ *              them; a neighbour counts once however many faces share the edge (duplicate faces, both windings, fans).
+ *   boundary   an edge on exactly one face is a BOUNDARY edge and its two ends are boundary vertices; an edge on more than two
+ *              faces is NON-MANIFOLD (counted, not boundary).  Boundary vertices are pinned unless NM_MESH_SMOOTH_FREE_BOUNDARY;
+ *              a vertex of degree 0 (ISOLATED) never moves.  A pinned or isolated vertex leaves bit for bit as it came.
+ *   half-step  with factor f, degree n, e = the binary exponent of the largest |coordinate| of the INPUT mesh (every
+ *              |x| < 2^e; frexp's) and shift = 40 - e:
+ *                q  = (int64) rint(ldexp((double) x, shift)) clamped to [-2^43, 2^43] (a NaN to the lower bound)
+ *                hi = sum (q >> 20), lo = sum (q & 0xFFFFF) over the neighbours, per component (|hi| < 2^54, lo < 2^51: exact)
+ *                m  = ldexp(((double) hi * 2^20 + (double) lo) / (double) n, -shift)
+ *                x' = (float)((double) x + (double) f * (m - (double) x))
+ *              every vertex reads the previous half-step's positions.  A mesh whose largest |coordinate| is 0 is returned as is.
+ *   normals    per non-degenerate face n = cross(b - a, c - a) in fp32 (each component left - right of two rounded
+ *              products), len = sqrt((nx nx + ny ny) + nz nz); a face whose len is zero or not finite is skipped;
+ *              q = (int64) rint((double) ((n / len) * flip) * 2^30) per component is added to the three corners (int64:
+ *              exact).  With s = (float) S per component: normal = s / sqrt((sx sx + sy sy) + sz sz), or, when S is the
+ *              zero vector, the vertex's input normal ((0, 0, 0) when d_in_normals is NULL).
+ *
+ * nm_mesh_smooth_build: validates, builds the edge table, the boundary bits and the adjacency (CSR, 64-bit offsets); returns
+ *   on the HOST (the one synchronisation of the stream) h_counts[NM_MESH_SMOOTH_COUNTS]: edges, boundary edges, non-manifold
+ *   edges, boundary vertices, isolated vertices, degenerate faces, bad vertices, bad faces and the exponent e (0 for a largest
+ *   coordinate of 0) -- the NM_MESH_SMOOTH_* indices below.
+ * nm_mesh_smooth_run: with that workspace and THE SAME vertices, launches the 2 * iterations half-steps (iterations when
+ *   mu = 0) with no host round trip; the second position buffer lives in the workspace; d_out_verts (V,3) must not be d_verts.
+ *   iterations in [0, 1000]; 0 copies the input.  flags: 0 or NM_MESH_SMOOTH_FREE_BOUNDARY.
+ * nm_mesh_vertex_normals: the vertex normals of (d_verts, d_faces) into d_out_normals (V,3); flip is +1 or -1; d_in_normals
+ *   (V,3) or NULL.  The workspace is one of nm_mesh_smooth_workspace_bytes(V, F); the call clears the part it uses and leaves
+ *   what nm_mesh_smooth_build put there alone.  No host synchronisation.
+ * V and F are in [0, 2^31 - 64).  The workspace (nm_mesh_smooth_workspace_bytes, 0 for sizes out of range; 256-byte aligned;
+ * 12 bytes per slot of a table of the smallest power of two >= 6 F slots, 4 * 6 F for the neighbour lists, 52 V for the
+ * rest) must stay untouched between build and run.  Argument errors -- a null array with a non-zero size, lambda, mu or
+ * iterations out of range, unknown flags, a flip that is not +-1 -- return 2 before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_MESH_SMOOTH_FREE_BOUNDARY 1
+#define NM_MESH_SMOOTH_EDGES 0
+#define NM_MESH_SMOOTH_BOUNDARY_EDGES 1
+#define NM_MESH_SMOOTH_NONMANIFOLD_EDGES 2
+#define NM_MESH_SMOOTH_BOUNDARY_VERTICES 3
+#define NM_MESH_SMOOTH_ISOLATED_VERTICES 4
+#define NM_MESH_SMOOTH_DEGENERATE 5
+#define NM_MESH_SMOOTH_BAD_VERTICES 6
+#define NM_MESH_SMOOTH_BAD_FACES 7
+#define NM_MESH_SMOOTH_EXPONENT 8
+#define NM_MESH_SMOOTH_COUNTS 9
+int64_t nm_mesh_smooth_workspace_bytes(int64_t num_vertices, int64_t num_faces);
+int nm_mesh_smooth_build(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces, void* d_workspace,
+                         int64_t* h_counts, void* stream);
+int nm_mesh_smooth_run(const void* d_workspace, const float* d_verts, int64_t num_vertices, int32_t iterations, float lambda,
+                       float mu, int32_t flags, float* d_out_verts, void* stream);
+int nm_mesh_vertex_normals(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
+                           const float* d_in_normals, int32_t flip, void* d_workspace, float* d_out_normals, void* stream);
 
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex

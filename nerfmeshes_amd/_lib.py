@@ -207,6 +207,11 @@ SIGNATURES = {
                                            C.c_float, C.c_int32, c_void_p, C.POINTER(C.c_int64), c_void_p]),
     "nm_mesh_simplify_emit": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float, C.c_float,
                                         C.c_float, C.c_float, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_smooth_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "nm_mesh_smooth_build": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.POINTER(C.c_int64), c_void_p]),
+    "nm_mesh_smooth_run": (C.c_int, [c_void_p, c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_int32, c_void_p, c_void_p]),
+    "nm_mesh_vertex_normals": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int32, c_void_p, c_void_p,
+                                         c_void_p]),
     "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 

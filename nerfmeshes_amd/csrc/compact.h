@@ -1,4 +1,4 @@
-// Ordered compaction on the device, shared by surface_filter.hip, mesh_components.hip, mesh_simplify.hip and mesh_metrics.hip:
+// Ordered compaction on the device, shared by surface_filter.hip, mesh_components.hip, mesh_simplify.hip, mesh_smooth.hip and mesh_metrics.hip:
 // keep bits (one __ballot word per 64 elements, the words in element order) -> prefix sums of the words' popcounts -> every kept
 // element's output row is the prefix of its word + the popcount of the lower bits, which is numpy's cumsum(keep) - 1.  The output
 // order is the input order by construction, whatever order the workgroups ran in: there is no atomic queue.
@@ -71,6 +71,13 @@ __device__ __forceinline__ bool bit_test(const unsigned long long* __restrict__ 
 __device__ __forceinline__ int64_t bit_rank(const unsigned long long* __restrict__ words, const uint32_t* __restrict__ prefix,
                                             int64_t i) {
     return (int64_t)prefix[i >> 6] + __popcll(words[i >> 6] & ((1ull << (i & 63)) - 1ull));
+}
+
+// splitmix64's finaliser: the hash of the open-addressing tables (mesh_simplify.hip, mesh_smooth.hip)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 27; x *= 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
 }
 
 // the three vertex indices of face f -> false: one lies outside [0, nv) (a negative index fails the unsigned comparison)

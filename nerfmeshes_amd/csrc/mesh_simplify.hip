@@ -73,12 +73,6 @@ struct MsGrid { float o[3]; float cell; };
 
 #define MS_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-__device__ __forceinline__ unsigned long long ms_mix(unsigned long long x) {     // splitmix64's finaliser
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-
 // cell of a vertex -> false: bad
 __device__ __forceinline__ bool ms_cell(const MsGrid& g, const float (&x)[3], float (&c)[3], unsigned long long& key) {
     bool ok = true;
@@ -101,7 +95,7 @@ __device__ __forceinline__ long long ms_quantise(float t) {
 // The slot of `key`, claimed if no vertex of that cell came before.  At most V keys live in >= 2 V slots, so an empty slot
 // always ends the walk; `cap` iterations bound it all the same (-> cap: not placed).
 __device__ __forceinline__ uint64_t ms_find_or_insert(MsSlot* table, uint64_t cap, unsigned long long key) {
-    uint64_t s = ms_mix(key) & (cap - 1);
+    uint64_t s = mix64(key) & (cap - 1);
     for (uint64_t i = 0; i < cap; ++i, s = (s + 1) & (cap - 1)) {
         unsigned long long k = __hip_atomic_load(&table[s].key, MS_RELAXED_AGENT);
         if (k == MS_EMPTY && __hip_atomic_compare_exchange_strong(&table[s].key, &k, key, __ATOMIC_RELAXED, MS_RELAXED_AGENT)) return s;
@@ -260,7 +254,7 @@ __global__ __launch_bounds__(256) void ms_insert_faces(const int32_t* __restrict
     int r[3], t[3];
     if (f >= nf || !ms_corners(faces, f, nv, rep, r) || ms_degenerate(r)) return;
     ms_canonical(r, t);
-    uint64_t s = ms_mix(ms_mix(((unsigned long long)(unsigned)t[0] << 32) | (unsigned)t[1]) ^ (unsigned long long)(unsigned)t[2]) & (fcap - 1);
+    uint64_t s = mix64(mix64(((unsigned long long)(unsigned)t[0] << 32) | (unsigned)t[1]) ^ (unsigned long long)(unsigned)t[2]) & (fcap - 1);
     uint32_t placed = 0u;                                            // a walk that ran out (it cannot: <= F triples in >= 2 F slots)
     for (uint64_t i = 0; i < fcap; ++i, s = (s + 1) & (fcap - 1)) {  // leaves slot 0 unowned by f: the face counts as a duplicate
         int o = __hip_atomic_load(ftab + s, MS_RELAXED_AGENT);

@@ -822,6 +822,60 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     return out_verts, out_faces, out_normals, info
 
 
+SMOOTH_MAX_ITERATIONS = 1000
+SMOOTH_FREE_BOUNDARY = 1                 # NM_MESH_SMOOTH_FREE_BOUNDARY
+
+
+def mesh_smooth(verts, faces, normals=None, iterations=10, lam=0.5, mu=-0.53, free_boundary=False, flip=None):
+    """Taubin's lambda | mu smoothing on the device (nm_mesh_smooth_build + _run + nm_mesh_vertex_normals; semantics in
+    include/nerfmeshes_hip.h): `iterations` times a uniform umbrella half-step with factor lam in (0, 1], then one with mu in
+    [-1, 0] (mu = 0: plain Laplacian smoothing).  Boundary vertices -- the ends of an edge on exactly one face -- stay where
+    they are unless free_boundary; a vertex on no edge never moves.  verts (V,3) f32, faces (F,3) i32, normals (V,3) f32 or
+    None, all on the GPU.  -> (verts, normals, info): the same numbering; normals are the area-independent sum of the unit
+    face normals of the RESULT times flip (+1: the winding's own side; -1: the other, which is the side marching cubes'
+    normals point to), a vertex without one keeping its input normal (or zero) -- None where None came in and no flip was
+    asked for (flip=None, which is +1 where normals came); info = dict(vertices, faces, edges, boundary_edges,
+    nonmanifold_edges, boundary_vertices, isolated_vertices, degenerate_faces, exponent).  Raises ValueError for a vertex
+    with a non-finite coordinate and for a face index out of range (the one read-back)."""
+    lib = _lib.load()
+    iterations = int(iterations)
+    lam, mu = float(np.float32(lam)), float(np.float32(mu))
+    if not 0 <= iterations <= SMOOTH_MAX_ITERATIONS:
+        raise ValueError(f"mesh_smooth: iterations must be in [0, {SMOOTH_MAX_ITERATIONS}], got {iterations}")
+    if not 0.0 < lam <= 1.0:
+        raise ValueError(f"mesh_smooth: lam must be in (0, 1], got {lam}")
+    if not -1.0 <= mu <= 0.0:
+        raise ValueError(f"mesh_smooth: mu must be in [-1, 0], got {mu}")
+    if flip not in (None, 1, -1):
+        raise ValueError(f"mesh_smooth: flip must be +1 or -1, got {flip}")
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = _dev32(verts, dev, "verts")
+    normals = _dev32(normals, dev, "normals") if normals is not None else None
+    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)):
+        raise ValueError("mesh_smooth: the per-vertex arrays disagree on the vertex count")
+    ws = _mesh_workspace(int(lib.nm_mesh_smooth_workspace_bytes(nv, nf)), "mesh smooth", nv, nf, dev)
+    counts = (C.c_int64 * 9)()
+    _mesh_check(lib, lib.nm_mesh_smooth_build(_ptr(verts), nv, _ptr(faces), nf, _ptr(ws), counts, _stream()), "nm_mesh_smooth_build")
+    edges, boundary_edges, nonmanifold, boundary_vertices, isolated, degenerate, bad_v, bad_f, exponent = (int(x) for x in counts)
+    if bad_v:
+        raise ValueError(f"mesh smooth: {bad_v} vertices have a non-finite coordinate")
+    if bad_f:
+        raise ValueError(f"mesh smooth: {bad_f} faces have a vertex index outside [0, {nv})")
+    out_verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    flags = SMOOTH_FREE_BOUNDARY if free_boundary else 0
+    _mesh_check(lib, lib.nm_mesh_smooth_run(_ptr(ws), _ptr(verts), nv, iterations, lam, mu, flags, _ptr(out_verts), _stream()),
+                "nm_mesh_smooth_run")
+    out_normals = None
+    if normals is not None or flip is not None:
+        out_normals = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+        _mesh_check(lib, lib.nm_mesh_vertex_normals(_ptr(out_verts), nv, _ptr(faces), nf, _ptr(normals), 1 if flip is None else flip,
+                                                    _ptr(ws), _ptr(out_normals), _stream()), "nm_mesh_vertex_normals")
+    info = dict(vertices=nv, faces=nf, edges=edges, boundary_edges=boundary_edges, nonmanifold_edges=nonmanifold,
+                boundary_vertices=boundary_vertices, isolated_vertices=isolated, degenerate_faces=degenerate, exponent=exponent)
+    return out_verts, out_normals, info
+
+
 def _mesh_arrays(verts, faces, what):
     """(V,3) fp32 vertices and (F,3) int32 faces of one mesh on the GPU (host arrays are copied over), checked."""
     verts = _dev32(verts if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.as_tensor(verts).cuda(), name="verts")

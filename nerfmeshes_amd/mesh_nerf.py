@@ -290,6 +290,27 @@ def filter_components(vertices, triangles, normals, min_faces, keep_largest):
     return vertices, triangles, normals
 
 
+SMOOTH_FLIP = -1            # marching cubes winds its triangles against its normals (tests/test_mesh_smooth.py pins it)
+
+
+def smooth_mesh(vertices, triangles, normals, args):
+    """`--smooth-iters N` on the device (hip_ops.mesh_smooth): N iterations of Taubin's filter -- an umbrella half-step with
+    `--smooth-lambda`, then one with `--smooth-mu` -- on the full-resolution mesh; boundary vertices (the grid box clips most
+    exports) stay in place unless `--smooth-boundary free`.  The numbering and the triangles stay; the normals are recomputed
+    from the smoothed triangles, on the side marching cubes' normals point to."""
+    old = vertices
+    vertices, normals, info = hip_ops.mesh_smooth(vertices, triangles.to(torch.int32), normals, iterations=args.smooth_iters,
+                                                  lam=args.smooth_lambda, mu=args.smooth_mu,
+                                                  free_boundary=args.smooth_boundary == "free", flip=SMOOTH_FLIP)
+    voxel = 2.0 * args.limit / args.res
+    moved = float(torch.linalg.vector_norm(vertices - old.to(vertices), dim=1).max()) / voxel if vertices.shape[0] else 0.0
+    kept = 0 if args.smooth_boundary == "free" else info["boundary_vertices"]
+    print(f"Smooth: {args.smooth_iters} iterations (lambda {args.smooth_lambda:g}, mu {args.smooth_mu:g}): {info['vertices']} vertices, "
+          f"{kept} boundary vertices kept in place, {info['isolated_vertices']} isolated, {info['nonmanifold_edges']} non-manifold "
+          f"edges, largest displacement {moved:.4f} voxels")
+    return vertices, triangles, normals
+
+
 def simplify_mesh(vertices, triangles, normals, cell_voxels, args):
     """`--simplify-cell K` on the device (hip_ops.mesh_simplify): vertex clustering on a grid of K-voxel cells, K * (2 * limit /
     res) world units, anchored at (-limit,)*3 -- the vertices of one cell become their exact mean (one alone stays bit for bit),
@@ -335,7 +356,10 @@ def export_marching_cubes(model, args, cfg, device):
     keeps the unfiltered geometry.  Under torch.distributed every rank filters the gathered mesh redundantly.
     `--simplify-cell K` clusters the vertices (simplify_mesh) after that filter -- its thresholds count original triangles -- and
     before `--target-mesh`, the network normals and the appearance query, which all see the final geometry; the cache keeps the
-    unsimplified mesh, and every rank simplifies redundantly."""
+    unsimplified mesh, and every rank simplifies redundantly.
+    `--smooth-iters N` smooths the full-resolution mesh (smooth_mesh) between the component filter and the clustering, which
+    then averages smoothed positions and the recomputed normals; the cache keeps the unsmoothed mesh, and every rank smooths
+    redundantly."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
     normals_mode = getattr(args, "normals", "grid")
     if normals_mode == "network" and getattr(args, "route", "kernel") == "script":
@@ -352,6 +376,16 @@ def export_marching_cubes(model, args, cfg, device):
             raise ValueError("--simplify-cell has no --route script: the reference's script has no such step")
         if not 0.0 < simplify_cell < float("inf"):
             raise ValueError(f"--simplify-cell must be finite and >= 0, got {simplify_cell}")
+    smooth_iters = int(getattr(args, "smooth_iters", 0))
+    if smooth_iters or any(getattr(args, name, default) != default for name, default in
+                           (("smooth_lambda", 0.5), ("smooth_mu", -0.53), ("smooth_boundary", "fixed"))):
+        if getattr(args, "route", "kernel") == "script":
+            raise ValueError("--smooth-iters / --smooth-lambda / --smooth-mu / --smooth-boundary have no --route script: the "
+                             "reference's script has no such step")
+        if not (0 <= smooth_iters <= hip_ops.SMOOTH_MAX_ITERATIONS and 0.0 < args.smooth_lambda <= 1.0
+                and -1.0 <= args.smooth_mu <= 0.0):
+            raise ValueError(f"--smooth-iters must be in [0, {hip_ops.SMOOTH_MAX_ITERATIONS}], --smooth-lambda in (0, 1] and "
+                             "--smooth-mu in [-1, 0]")
     target_mesh = getattr(args, "target_mesh", None)
     if target_mesh:
         if getattr(args, "route", "kernel") == "script":
@@ -368,6 +402,8 @@ def export_marching_cubes(model, args, cfg, device):
         vertices, triangles, normals = (torch.as_tensor(t).to(device) for t in (vertices, triangles, normals))
         if min_faces or keep_largest:
             vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
+        if smooth_iters:
+            vertices, triangles, normals = smooth_mesh(vertices, triangles, normals, args)
         if simplify_cell:
             vertices, triangles, normals = simplify_mesh(vertices, triangles, normals, simplify_cell, args)
     else:
@@ -376,6 +412,8 @@ def export_marching_cubes(model, args, cfg, device):
         unfiltered = vertices, triangles, normals          # what the cache keeps, so that the filter can be tuned on it
         if min_faces or keep_largest:                      # first: a filter that leaves nothing raises before anything is written
             vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
+        if smooth_iters:
+            vertices, triangles, normals = smooth_mesh(vertices, triangles, normals, args)
         if simplify_cell:                                  # likewise: no triangle left raises here
             vertices, triangles, normals = simplify_mesh(vertices, triangles, normals, simplify_cell, args)
         if cache_new or args.override_cache_mesh:
@@ -485,6 +523,17 @@ def build_parser():
                    help="(addition) simplify the mesh by vertex clustering: the vertices in one cell of a grid of this many voxels "
                         "per edge become their mean, degenerate and duplicate triangles go; after the component filter, before "
                         "the normals and the appearance query (0 = off)")
+    p.add_argument("--smooth-iters", type=_non_negative, default=0,
+                   help="(addition) smooth the mesh with this many iterations of Taubin's lambda | mu filter on the GPU: after "
+                        "the component filter, before --simplify-cell, the normals and the appearance query; the vertex normals "
+                        "are recomputed from the smoothed triangles (0 = off)")
+    p.add_argument("--smooth-lambda", type=float, default=0.5,
+                   help="(addition) factor of the first, shrinking half-step of every --smooth-iters iteration, in (0, 1]")
+    p.add_argument("--smooth-mu", type=float, default=-0.53,
+                   help="(addition) factor of the second, inflating half-step, in [-1, 0]; 0 skips it: plain Laplacian smoothing")
+    p.add_argument("--smooth-boundary", choices=("fixed", "free"), default="fixed",
+                   help="(addition) fixed (default): the vertices on an open edge of the mesh, where the grid box clips it, stay "
+                        "in place; free: they move like any other vertex")
     p.add_argument("--target-mesh", type=str, default=None,
                    help="(addition) an OBJ file: print the chamfer distance between the extracted mesh and it (sampled and searched "
                         "on the GPU, world coordinates) and write <save-dir>/<mesh-name stem>.chamfer.json")
