@@ -129,9 +129,14 @@ int64_t nm_mlp_flops_per_sample(const nm_mlp* mlp, int density_only);
  * skipped tiles did not run -- skipped tiles x tile samples x (flops_per_sample(0) - flops_per_sample(1)); the tiles
  * are counted on the device (one counter per launch, allocated on every device by nm_mlp_profile_enable(1)) while
  * profiling is on.  A device has 2^20 counters: a skipping launch beyond that many since the last read evaluates
- * every tile (slower, and counted as such), so read at least that often. */
+ * every tile (slower, and counted as such), so read at least that often.
+ * Tiles that the render calls' ray termination did not evaluate at all (see nm_render_rays) are counted in a second word
+ * per launch and leave total_flops with tile samples x flops_per_sample(0) each.  nm_mlp_profile_read_tiles is
+ * nm_mlp_profile_read that also returns the two tile counts of the stretch (either pointer may be NULL). */
 int nm_mlp_profile_enable(int on);
 int nm_mlp_profile_read(int64_t* launches, double* total_ms, double* total_flops);
+int nm_mlp_profile_read_tiles(int64_t* launches, double* total_ms, double* total_flops, int64_t* skipped_tiles,
+                              int64_t* terminated_tiles);
 
 /* BaseModel.sample_points / FlexibleNeRFModel.forward  (src/models/model_base.py:65-73,
  * src/nerf/models.py:60-80): d_points (n,3), d_dirs (n,3) -> d_radiance (n,4) = [sigmoid rgb, raw sigma]. */
@@ -239,7 +244,14 @@ int nm_sample_pdf(const float* d_t, const float* d_weights, const float* d_u, in
  * The radiance held in the workspace is internal: where no sample of a workgroup tile (128 samples: 8 adjacent rays x
  * 16 consecutive samples when the sample count is a multiple of 16, else 128 consecutive samples) has raw sigma > 0,
  * the fused 256-wide and 128-wide (10 xyz frequencies) fp32 kernels store {0, 0, 0, sigma} for the tile and do not evaluate its colour -- alpha
- * and weight of such samples are exactly 0, so every output map has the bits it has with the colours computed. */
+ * and weight of such samples are exactly 0, so every output map has the bits it has with the colours computed.
+ * Ray termination: a call of at least two 8-ray blocks per resident workgroup, with sample counts that are multiples of 16,
+ * does not evaluate a tile at all once the compositor's fp32 transmittance is provably 0 on all of its rays (a bound on
+ * log2 of the product of the factors in front of it, kept per ray in the workspace, is below -160); the tile's radiance
+ * is {0, 0, 0, 0}, its weights are the +0 they would have been.  The maps keep their bits for every finite sigma.  A
+ * non-finite sigma BEHIND a ray that is already at transmittance 0 therefore no longer reaches the maps (it would have
+ * made them NaN through 0 * alpha); in front of that point it propagates as before.  NM_RAY_TERMINATION=0 in the
+ * environment switches ray termination off. */
 typedef struct nm_render_cfg {
     int32_t num_coarse, num_fine;      /* cfg.nerf.train.num_coarse / num_fine (model_nerf.py:30-31) */
     int32_t lindisp;                   /* cfg.nerf.{train,validation}.lindisp */

@@ -80,6 +80,8 @@ SIGNATURES = {
     "nm_mlp_flops_per_sample": (C.c_int64, [c_void_p, C.c_int]),
     "nm_mlp_profile_enable": (C.c_int, [C.c_int]),
     "nm_mlp_profile_read": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "nm_mlp_profile_read_tiles": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "nm_mlp_sample_points": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]),
     "nm_mlp_sample_density": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]),
     "nm_mlp_density_grad_workspace_bytes": (C.c_int64, [c_void_p, C.c_int64]),

@@ -168,8 +168,9 @@ MlpArgs ray_mode_args(const nm_mlp* m, const float* d_origins, int origins_per_r
 
 // ---- optional per-launch timing of the dominant kernel (bench.py's roofline leg) ---------------
 // A launch that may skip the colour branch of tiles without density (MlpArgs::skip_empty) counts them in a device word of its own:
-// `slot` indexes g_prof_skips (-1: the launch cannot skip), `skip_flops` is what one skipped tile did not execute.
-struct ProfRec { hipEvent_t start, stop; double flops; int slot, device; double skip_flops; };
+// `slot` indexes g_prof_skips (-1: the launch cannot skip), `skip_flops` is what one skipped tile did not execute.  Tiles that ray
+// termination did not evaluate at all (MlpArgs::att) are counted in the word PROF_SKIP_SLOTS behind it; each is `dead_flops` less.
+struct ProfRec { hipEvent_t start, stop; double flops; int slot, device; double skip_flops, dead_flops; };
 static bool g_prof_on = false;
 static std::vector<ProfRec> g_prof;
 constexpr int PROF_SKIP_SLOTS = 1 << 20;          // skipping launches per device between two reads (4 MB of counters per device)
@@ -186,14 +187,16 @@ static int launch_mlp_timed(const nm_mlp* m, const MlpArgs& a, int density_only,
     NM_HIP_CHECK(hipEventCreate(&r.start));
     NM_HIP_CHECK(hipEventCreate(&r.stop));
     r.flops = (double)a.n * (double)(density_only == 1 ? m->flops_density : m->flops_full);
-    r.slot = -1; r.device = -1; r.skip_flops = 0;
+    r.slot = -1; r.device = -1; r.skip_flops = 0; r.dead_flops = 0;
     MlpArgs counted = a;
     if (a.skip_empty && !density_only && !m->lw) {
         ProfSkips* ps = m->device >= 0 && m->device < (int)g_prof_skips.size() ? &g_prof_skips[m->device] : nullptr;
         if (ps && ps->d && ps->used < PROF_SKIP_SLOTS) {
             r.slot = ps->used++; r.device = m->device;
             r.skip_flops = (double)m->plan->wg_samples * (double)(m->flops_full - m->flops_density);
+            r.dead_flops = (double)m->plan->wg_samples * (double)m->flops_full;
             counted.skip_count = ps->d + r.slot;
+            counted.dead_count = ps->d + PROF_SKIP_SLOTS + r.slot;
         } else {
             // more than PROF_SKIP_SLOTS skipping launches since the last read (documented in the public header): without a
             // counter the launch evaluates every tile, so that it executes every FLOP it is credited with
@@ -383,8 +386,8 @@ int nm_mlp_profile_enable(int on) {
         std::vector<ProfSkips> slots(count);
         for (int dev = 0; dev < count; ++dev) {
             DeviceGuard guard(dev);
-            NM_HIP_CHECK(hipMalloc(&slots[dev].d, PROF_SKIP_SLOTS * sizeof(uint32_t)));
-            NM_HIP_CHECK(hipMemset(slots[dev].d, 0, PROF_SKIP_SLOTS * sizeof(uint32_t)));
+            NM_HIP_CHECK(hipMalloc(&slots[dev].d, 2 * PROF_SKIP_SLOTS * sizeof(uint32_t)));      // skipped | terminated
+            NM_HIP_CHECK(hipMemset(slots[dev].d, 0, 2 * PROF_SKIP_SLOTS * sizeof(uint32_t)));
         }
         g_prof_skips.swap(slots);
     }
@@ -393,8 +396,13 @@ int nm_mlp_profile_enable(int on) {
 }
 
 int nm_mlp_profile_read(int64_t* launches, double* total_ms, double* total_flops) {
+    return nm_mlp_profile_read_tiles(launches, total_ms, total_flops, nullptr, nullptr);
+}
+
+int nm_mlp_profile_read_tiles(int64_t* launches, double* total_ms, double* total_flops, int64_t* skipped_tiles, int64_t* terminated_tiles) {
     double ms = 0, fl = 0;
-    std::vector<uint32_t> skips;
+    int64_t n_skipped = 0, n_dead = 0;
+    std::vector<uint32_t> skips, deads;
     for (ProfRec& r : g_prof) {
         NM_HIP_CHECK(hipEventSynchronize(r.stop));
         float t = 0;
@@ -409,10 +417,19 @@ int nm_mlp_profile_read(int64_t* launches, double* total_ms, double* total_flops
         skips.resize(ps.used);
         NM_HIP_CHECK(hipMemcpy(skips.data(), ps.d, skips.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         NM_HIP_CHECK(hipMemset(ps.d, 0, skips.size() * sizeof(uint32_t)));
+        deads.resize(ps.used);
+        NM_HIP_CHECK(hipMemcpy(deads.data(), ps.d + PROF_SKIP_SLOTS, deads.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        NM_HIP_CHECK(hipMemset(ps.d + PROF_SKIP_SLOTS, 0, deads.size() * sizeof(uint32_t)));
         for (const ProfRec& r : g_prof)
-            if (r.slot >= 0 && r.device == dev) fl -= (double)skips[r.slot] * r.skip_flops;
+            if (r.slot >= 0 && r.device == dev) {
+                fl -= (double)skips[r.slot] * r.skip_flops + (double)deads[r.slot] * r.dead_flops;
+                n_skipped += skips[r.slot];
+                n_dead += deads[r.slot];
+            }
         ps.used = 0;
     }
+    if (skipped_tiles) *skipped_tiles = n_skipped;
+    if (terminated_tiles) *terminated_tiles = n_dead;
     if (launches) *launches = (int64_t)g_prof.size();
     if (total_ms) *total_ms = ms;
     if (total_flops) *total_flops = fl;
@@ -627,7 +644,8 @@ int nm_mlp_eval_rays(nm_mlp* m, const float* d_origins, int origins_per_ray, con
 
 namespace nm {
 int nm_mlp_eval_render_internal(nm_mlp* m, const RayGen* gen, const float* d_origins, int origins_per_ray, const float* d_dirs,
-                                const float* d_t, int64_t rays, int32_t samples, float* d_radiance, hipStream_t stream) {
+                                const float* d_t, int64_t rays, int32_t samples, float* d_radiance, float* d_att, int64_t att_floats,
+                                hipStream_t stream) {
     NM_REQUIRE(m && (gen || (d_origins && d_dirs)) && d_t && d_radiance && rays >= 0 && samples > 0, "bad argument");
     MlpArgs a = ray_mode_args(m, d_origins, origins_per_ray, d_dirs, d_t, rays, samples, d_radiance);
     if (gen) {
@@ -636,6 +654,7 @@ int nm_mlp_eval_render_internal(nm_mlp* m, const RayGen* gen, const float* d_ori
         a.gen = *gen;
     }
     a.skip_empty = 1;
+    a.att = d_att; a.att_floats = d_att ? att_floats : 0;
     return launch_mlp_timed(m, a, 0, stream);
 }
 }  // namespace nm

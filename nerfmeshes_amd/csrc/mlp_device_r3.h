@@ -95,6 +95,13 @@ __device__ __forceinline__ void gemm_stage3(f32x4 (&acc)[NT], const float (&b1)[
 // LDS under the trunk's barriers, so the round trip is hidden and `has_next` is known before the last stage, which needs it.  A
 // workgroup makes one claim per tile it runs and stops at the first one past the end: no workgroup waits for another, and a launch
 // makes exactly wg_iters claims.
+// Ray termination (MlpArgs::att; ray-tile launches of at least two ray blocks per resident workgroup): the queue runs
+// slot-major (tile `it` = depth slot it / ray_blocks of ray block it % ray_blocks), every wave adds an upper bound of log2 of its
+// ray's transmittance factors over the tile to the ray's entry of the slot before and stores it, and the claiming wave reads the 8
+// entries of the slot in front of the tile it claimed: where all are below -160 the compositor's fp32 transmittance is 0 on the
+// whole tile, which is then not evaluated at all -- it writes zeros (top of the tile loop).  The verdict travels in the top bit of
+// the claim word.  The table is read and written at agent scope (the XCDs' L2s are not coherent); an entry that is missing when
+// it is read only loses a verdict.
 template <int H, int FX, int FD, int NW, int KCH, bool FLAT = false, bool SKIP = false>   // FLAT: see mlp_kernel
 // Occupancy: networks up to 128 wide are compiled for FOUR waves per SIMD (128 registers: two 8-wave workgroups per CU; the
 // 128-wide instances spill 9 -- 17 registers outside the k-step loops for it).  With VALU issue time adding to matrix time on
@@ -147,6 +154,35 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
 
     int64_t next_it = 0;     // SKIP: the tile claimed for the iteration after this one
     int turn = 0;
+    // Ray termination is compiled into the 256-wide instances only: in the 128-wide one, held to 128 registers for four waves per
+    // SIMD, it spilled 38 registers (156 B of scratch) where the kernel spills 16; that instance is the code it was.
+    constexpr bool TERM = SKIP && H > 128;
+    const bool term = TERM && args.att != nullptr;      // launch_mlp: ray tiles, slot-major order
+    // this wave's entry of the table for tile `t` (slot-major: t = k * ray_blocks + block; a row is ray_blocks * NW rays)
+    auto att_entry = [&](int64_t t, uint32_t& k) -> float* {
+        k = (uint32_t)t / args.att_blocks;
+        return args.att + ((size_t)(uint32_t)t * NW + wave);     // (k * ray_blocks + block) * NW + wave
+    };
+    bool dead = false;       // the verdict on tile `it` (a workgroup's first tile is evaluated)
+    // wave 0: claim a tile and start the loads of its rays' entries of the slot before (lanes 0 .. NW-1 one ray each).  An entry
+    // that is not loaded (first slot, past the end) counts as alive.
+    auto claim_tile = [&](float& pre) -> uint32_t {
+        uint32_t c = 0;
+        if (lane == 0) c = atomicAdd(args.tile_queue, 1u);
+        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+        pre = 0.0f;
+        if (term) {
+            const int64_t nx = (int64_t)gridDim.x + c;
+            if (nx < wg_iters && nx >= (int64_t)args.att_blocks && lane < NW)      // not the first slot: the row before, NW entries
+                pre = __hip_atomic_load(args.att + ((size_t)((uint32_t)nx - args.att_blocks) * NW + lane), __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return c;
+    };
+    auto claim_word = [&](uint32_t c, float pre) -> uint32_t {     // all NW entries below -160: the tile is dead
+        const bool all_dead = term && __ballot(lane < NW && !(pre < -160.0f)) == 0;
+        return c | (all_dead ? 0x80000000u : 0u);
+    };
     for (int64_t it = blockIdx.x; it < wg_iters; it = SKIP ? next_it : it + gridDim.x) {
         bool has_next = !SKIP && it + gridDim.x < wg_iters;     // SKIP: known once the claim is read (before fc_feat)
         // linear order: wave w of iteration `it` owns 16 consecutive samples; ray_tiles: ray NW * block + w, depth slot k
@@ -154,10 +190,38 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
         bool valid = sample < args.n;
         if (SKIP && args.ray_tiles) {   // (32-bit split: launch_mlp keeps wg_iters below 2^31 in this mode; the 64-bit division costs registers)
             const uint32_t depth_slots = (uint32_t)args.samples >> 4;
-            const uint32_t block = (uint32_t)it / depth_slots;
+            // block-major: it = block * depth_slots + k | ray termination, slot-major: it = k * ray_blocks + block
+            const uint32_t div = term ? args.att_blocks : depth_slots;       // (!TERM: the division by depth_slots alone, as it was)
+            const uint32_t q = (uint32_t)it / div, r = (uint32_t)it - q * div;
+            const uint32_t block = term ? r : q;
             const int64_t ray_first = ((int64_t)block * NW + wave) * args.samples;
-            sample = ray_first + (((uint32_t)it - block * depth_slots) << 4) + col;
+            sample = ray_first + ((term ? q : r) << 4) + col;
             valid = ray_first < args.n;
+        }
+        if (TERM && dead) {
+            // Every ray of the tile has transmittance 0 in front of it: whatever the network gives here has weight alpha * 0 = +0, so
+            // the tile is written as zeros (finite, and sigma 0 keeps T at 0) and nothing is evaluated.  Dead is absorbing.  The
+            // weight ring is not touched: it holds layer1's first two chunks from the last tile's wrap-around DMA.
+            if (valid && g == 0) {
+                f32x4 o4 = {0.0f, 0.0f, 0.0f, 0.0f};
+                *reinterpret_cast<f32x4*>(args.out + 4 * sample) = o4;
+            }
+            uint32_t k;
+            float* const entry = att_entry(it, k);
+            if (lane == 0) __hip_atomic_store(entry, -1e30f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (args.dead_count && threadIdx.x == 0) atomicAdd(args.dead_count, 1u);
+            if (wave == 0) {
+                float pre;
+                const uint32_t c = claim_tile(pre);
+                const uint32_t word = claim_word(c, pre);
+                if (lane == 0) lds_claim[turn] = word;
+            }
+            __syncthreads();
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_claim[turn]);
+            turn ^= 1;
+            next_it = (int64_t)gridDim.x + (word & 0x7fffffffu);
+            dead = (word >> 31) != 0;
+            continue;
         }
         const int64_t sidx = valid ? sample : args.n - 1;
         const SamplePD smp = fetch_sample(args, sidx);
@@ -177,7 +241,16 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
         acc_to_operand<N::NT, false>(acc, in);
         // The claim of the tile after this one.  The compiler waits for the returned value where the atomic is issued, so it is
         // issued here and not in the prologue: in front of the trunk's stages this wave's wait runs under its SIMD partner's MFMAs.
-        if (SKIP && threadIdx.x == 0) lds_claim[turn] = atomicAdd(args.tile_queue, 1u);
+        // With ray termination the claimed tile is judged here as well (a second round trip of wave 0 alone; holding the entries in
+        // a register across the trunk's first stage instead, whose barriers wait for every load anyway, measured 0.2 % slower).
+        if constexpr (TERM) {
+            if (wave == 0) {
+                float pre;
+                const uint32_t claimed = claim_tile(pre);
+                const uint32_t word = claim_word(claimed, pre);
+                if (lane == 0) lds_claim[turn] = word;
+            }
+        } else if (SKIP && threadIdx.x == 0) lds_claim[turn] = atomicAdd(args.tile_queue, 1u);
 
         // ---- layers_xyz[0 .. L-2], then (full evaluation only) fc_feat as iteration L-1 (models.py:63-70)
         float sigma = 0.0f;
@@ -186,7 +259,34 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
 #pragma unroll 1
         for (int i = 0; i < trunk_iters; ++i) {
             const bool is_feat = i == num_layers - 1;
+            // ray termination: the sample's interval and the ray's entry of the slot before, asked for in front of the density head
+            float t_here = 0.0f, t_after = 0.0f, att_before = 0.0f;
+            float* entry = nullptr;
+            bool last_of_ray = false;
+            if (term && is_feat) {
+                uint32_t k;
+                entry = att_entry(it, k);
+                last_of_ray = (k << 4) + col + 1 == (uint32_t)args.samples;
+                if (valid) {
+                    t_here = args.c[sample];
+                    if (!last_of_ray) t_after = args.c[sample + 1];
+                    if (lane == 0 && k > 0)
+                        att_before = __hip_atomic_load(entry - (size_t)args.att_blocks * NW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
             if (is_feat) sigma = alpha_gemv<H>(in, lds_walpha, g) + tail_bias[0];
+            if (term && is_feat) {
+                // The compositor's factor of this sample, (1 - alpha) + 1e-10f, as an upper bound of its log2: + 2^-23 for a quantum of
+                // difference in 1 - alpha (where alpha rounds to 1 that moves log2 by whole units), + 2^-8 for expf, the norm and the sum.
+                // A NaN sigma is no density to the compositor either (fmaxf).  Padding rays are dead.
+                const float dist = (last_of_ray ? 1e10f : t_after - t_here) * nm_norm3(d[0], d[1], d[2]);
+                const float a = 1.0f - expf(-(fmaxf(sigma, 0.0f) * dist));
+                float c = log2f(((1.0f - a) + 1e-10f) + 0x1p-23f) + 0x1p-8f;
+#pragma unroll
+                for (int m = 1; m < 16; m <<= 1) c += __shfl_xor(c, m);
+                if (lane == 0)
+                    __hip_atomic_store(entry, valid ? att_before + c : -1e30f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             if (SKIP && is_feat) {
                 // Workgroup-uniform vote (the stages below hold barriers: every wave must take the same branch): a wave on which some
                 // valid sample has density -- or a NaN sigma, which must keep propagating -- stamps this iteration's number.
@@ -196,7 +296,9 @@ __global__ __launch_bounds__(NW * 64, H <= 128 ? 4 : 2) void mlp_kernel3(const M
                 __syncthreads();
                 empty_tile = __builtin_amdgcn_readfirstlane(*lds_vote) != epoch;
                 // the same barrier (and every one of the trunk before it) published the claim; nothing up to here issues the wrap-around DMA
-                next_it = (int64_t)gridDim.x + (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_claim[turn]);
+                const uint32_t word = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_claim[turn]);
+                next_it = (int64_t)gridDim.x + (word & 0x7fffffffu);
+                dead = (word >> 31) != 0;
                 turn ^= 1;
                 has_next = next_it < wg_iters;
                 wrap = enc_next(args.wstream, has_next);

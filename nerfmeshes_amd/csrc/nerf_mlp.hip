@@ -26,6 +26,7 @@
 //
 // Roofline: MFMA (fp32 matrix peak 157.3 TFLOP/s).  593 408 MAC per sample for the 8x256 net; the
 // kernel issues 9 280 MFMAs (1 024 MAC each) per 16-sample tile = 99.9 % useful work.
+#include <cstdlib>
 #include <iterator>
 #include <vector>
 
@@ -142,6 +143,11 @@ int forward_lds_bytes(const MlpPlan& p, int H, int L, int head_floats) {
     return p.ring_bytes + tuned_cache_bytes(H, L, head_floats);
 }
 
+static bool ray_termination_enabled() {
+    const char* e = std::getenv("NM_RAY_TERMINATION");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
 int launch_mlp(const nm_mlp* m, const MlpArgs& args_in, int density_only, hipStream_t stream) {
     const MlpPlan* p = m->plan;
     if (args_in.n <= 0) return 0;
@@ -155,6 +161,9 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args_in, int density_only, hipStr
     if (args.skip_empty && (!m->d_tile_queue || mlp_wg_iters(args, p->wg_samples) > INT32_MAX)) args.skip_empty = args.ray_tiles = 0;
     args.tile_queue = nullptr;
     if (!args.skip_empty) args.skip_count = nullptr;
+    float* const att = args.ray_tiles ? args.att : nullptr;       // ray termination: decided below, where the grid is known
+    args.att = nullptr;
+    args.att_blocks = 0;
     DeviceGuard guard(m->device);
     const int L = m->desc.num_layers, H = m->desc.hidden_size;
     NM_REQUIRE(density_only != 2 || (m->precision == NM_PREC_F32 && p->kernel_flat), "no kernel for use_viewdirs=0 networks in this plan");
@@ -186,7 +195,19 @@ int launch_mlp(const nm_mlp* m, const MlpArgs& args_in, int density_only, hipStr
         grid = (unsigned)(wg_iters < resident ? wg_iters : resident);
         args.tile_queue = m->d_tile_queue + (size_t)(__atomic_fetch_add(&m->tile_queue_turn, 1u, __ATOMIC_RELAXED) % TILE_QUEUE_SLOTS) * TILE_QUEUE_STRIDE;
         NM_HIP_CHECK(hipMemsetAsync(args.tile_queue, 0, sizeof(uint32_t), stream));
+        // Ray termination (mlp_device_r3.h): only where a ray block's tile of the slot before has long been evaluated when a tile is
+        // claimed in slot-major order, that is with at least two ray blocks per resident workgroup; below that the launch is what it
+        // was (block-major order, no table).  The 128-wide skip kernel does not have it (mlp_device_r3.h).  NM_RAY_TERMINATION=0
+        // switches it off (A/B in one build).
+        const int64_t depth_slots = args.samples / 16, ray_blocks = att ? wg_iters / depth_slots : 0;
+        const int64_t table = depth_slots * ray_blocks * p->NW;
+        if (att && p->H > 128 && ray_blocks >= 2 * (int64_t)grid && table <= args.att_floats && ray_termination_enabled()) {
+            args.att = att;
+            args.att_blocks = (uint32_t)ray_blocks;
+            NM_HIP_CHECK(hipMemsetAsync(att, 0, (size_t)table * sizeof(float), stream));
+        }
     }
+    if (!args.att) args.dead_count = nullptr;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(p->NW * 64), lds_bytes, stream, args, (int)m->desc.num_layers, density_only);
     NM_HIP_CHECK(hipGetLastError());
     return 0;

@@ -134,6 +134,13 @@ struct MlpArgs {
     uint32_t* skip_count;    // null, or the launch's counter of skipped tiles (profiling: mlp_api.hip)
     uint32_t* tile_queue;    // skip_empty launches: the device word their workgroups claim tiles from (mlp_device_r3.h), zero when the
                              // launch starts; launch_mlp sets it from the handle
+    // Ray termination (mlp_device_r3.h): att[depth slot][ray, padded to whole ray blocks] = an upper bound of log2 of the product of
+    // the ray's transmittance factors over the slots up to this one (0: nothing known), zero when the launch starts.  Set by
+    // render_impl together with att_floats, the floats there are; launch_mlp clears it unless the launch takes part and sets att_blocks.
+    float* att;
+    int64_t att_floats;
+    uint32_t att_blocks;     // ray blocks of the launch: tile it = depth slot it / att_blocks of ray block it % att_blocks
+    uint32_t* dead_count;    // null, or the launch's counter of terminated tiles (profiling: mlp_api.hip)
 };
 
 // Workgroup iterations of a tuned forward launch: THE expression, shared by launch_mlp (grid size) and the kernels (loop bound).
@@ -248,8 +255,10 @@ void launch_head_reduce(const float* partial, const float* partial_bias, int par
 // The render path's two network calls (ray_ops.hip: render_impl): rays from buffers (`gen` null) or from the pose, into WORKSPACE
 // radiance that only the compositor reads, with MlpArgs::skip_empty set -- a sample with raw sigma <= 0 has alpha == weight == 0
 // exactly (no noise is added on this path), so the rgb of a tile without density is written as zeros instead of being computed.
+// `d_att` (att_floats floats of workspace): the ray-termination table of MlpArgs::att; the launch zeroes what it uses of it.
 int nm_mlp_eval_render_internal(nm_mlp* m, const RayGen* gen, const float* d_origins, int origins_per_ray, const float* d_dirs,
-                                const float* d_t, int64_t rays, int32_t samples, float* d_radiance, hipStream_t stream);
+                                const float* d_t, int64_t rays, int32_t samples, float* d_radiance, float* d_att, int64_t att_floats,
+                                hipStream_t stream);
 
 }  // namespace nm
 

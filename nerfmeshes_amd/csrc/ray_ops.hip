@@ -673,6 +673,10 @@ int nm_sample_pdf_rand(const float* d_t, const float* d_weights, const float* d_
 
 static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// The ray-termination table of the network launches (MlpArgs::att): one float per 16-sample depth slot and ray, the rays padded to
+// whole ray blocks (at most 16 rays: a tuned kernel has at most 16 waves), for the longer of the two passes.
+static inline size_t att_table_floats(int64_t rays, int32_t samples) { return (size_t)((rays + 15) / 16 * 16) * (size_t)((samples + 15) / 16); }
+
 int64_t nm_render_workspace_bytes(int64_t rays, int32_t num_coarse, int32_t num_fine) {
     const size_t sc = (size_t)num_coarse, sf = (size_t)(num_coarse + (num_fine > 0 ? num_fine : 0));
     size_t b = 0;
@@ -683,6 +687,7 @@ int64_t nm_render_workspace_bytes(int64_t rays, int32_t num_coarse, int32_t num_
         b += align256(rays * sf * 4);    // t fine
         b += align256(rays * sf * 16);   // radiance fine
     }
+    b += align256(att_table_floats(rays, (int32_t)sf) * 4);     // ray termination table (both passes use it in turn)
     return (int64_t)b;
 }
 
@@ -698,10 +703,13 @@ static int render_impl(nm_mlp* coarse, nm_mlp* fine, const nm_render_cfg* cfg, c
     float* t_c = reinterpret_cast<float*>(ws); ws += align256(rays * (size_t)sc * 4);
     float* rad_c = reinterpret_cast<float*>(ws); ws += align256(rays * (size_t)sc * 16);
     float* w_c = reinterpret_cast<float*>(ws); ws += align256(rays * (size_t)sc * 4);
+    // the ray-termination table: behind everything else this call uses of the workspace
+    const size_t att_floats = att_table_floats(rays, fine ? sf : sc);
+    float* att = reinterpret_cast<float*>(ws + (fine ? align256(rays * (size_t)sf * 4) + align256(rays * (size_t)sf * 16) : 0));
     int rc;
     auto mlp = [&](nm_mlp* m, const float* t, int samples, float* rad) -> int {
         // `rad` is workspace only the compositor below reads, and no noise is added to sigma: tiles without density skip the colour branch
-        return nm_mlp_eval_render_internal(m, gen, d_origins, origins_per_ray, d_dirs, t, rays, samples, rad, stream);
+        return nm_mlp_eval_render_internal(m, gen, d_origins, origins_per_ray, d_dirs, t, rays, samples, rad, att, (int64_t)att_floats, stream);
     };
     // RaySampleInterval -> intervals_to_ray_points -> model_coarse -> volume_renderer (model_nerf.py:52-62)
     if ((rc = launch_coarse_intervals(d_u_coarse, d_near, d_far, bounds_per_ray, cfg->lindisp, rays, sc, t_c, stream))) return rc;

@@ -369,6 +369,16 @@ def mlp_profile_read():
     return n.value, ms.value, fl.value
 
 
+def mlp_profile_read_tiles():
+    """mlp_profile_read() and the two tile counts of the stretch: (launches, kernel ms, executed flops, skipped tiles,
+    terminated tiles).  A skipped tile (no sample with density) ran the trunk and the density head only; a terminated one
+    (every ray of it behind transmittance 0: the render calls' ray termination) ran nothing."""
+    n, ms, fl, sk, dead = C.c_int64(), C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+    check(_lib.load().nm_mlp_profile_read_tiles(C.byref(n), C.byref(ms), C.byref(fl), C.byref(sk), C.byref(dead)),
+          "nm_mlp_profile_read_tiles")
+    return n.value, ms.value, fl.value, sk.value, dead.value
+
+
 def mlp_profile_read_skipped(model, samples):
     """mlp_profile_read() for a profiled stretch in which networks of `model`'s shape evaluated `samples` samples in full:
     (launches, kernel ms, executed flops, skipped tiles).  The library counts skipped tiles per launch and reports them as the
