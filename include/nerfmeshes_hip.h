@@ -52,6 +52,8 @@ extern "C" {
  * (mesh_nerf --simplify-cell).  Additions only. */
 /* 6, later: + nm_mesh_smooth_build (+ _workspace_bytes), nm_mesh_smooth_run, nm_mesh_vertex_normals: Taubin smoothing of the
  * mesh and the vertex normals of the result (mesh_nerf --smooth-iters).  Additions only. */
+/* 6, later: + nm_mesh_rasterize (+ nm_mesh_raster_workspace_bytes), nm_mesh_interpolate: a deterministic software rasteriser of
+ * the coloured mesh (mesh_render, mesh_nerf --render-views).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -887,6 +889,73 @@ int nm_mesh_smooth_run(const void* d_workspace, const float* d_verts, int64_t nu
                        float mu, int32_t flags, float* d_out_verts, void* stream);
 int nm_mesh_vertex_normals(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
                            const float* d_in_normals, int32_t flip, void* d_workspace, float* d_out_normals, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Rasteriser of a mesh (mesh_render, mesh_nerf --render-views; DESIGN.md, "Mesh render"): which face a pinhole camera sees at
+ * every pixel, its depth and its barycentrics.  All arrays on the device: d_verts (V,3) fp32, d_faces (F,3) int32.  Coverage is
+ * exact integer work and visibility a 64-bit minimum, every fp32 / fp64 operation is rounded on its own and division is
+ * correctly rounded, so a numpy restatement (tests/mesh_raster.py) reproduces every output bit for bit, whatever the order of
+ * the workgroups and whichever path drew a face.
+ *
+ *   view       a non-NDC nm_view: R = c2w[:3,:3], t = c2w[:3,3], height and width in [1, 16384], focal finite and > 0.
+ *   vertex     in fp64: d = (double) p - (double) t; xc = (R00 dx + R10 dy) + R20 dz, yc and zc with columns 1 and 2 of R;
+ *              w = (float)(-zc); u = (xc / (double) w) focal + width 0.5; v = -(yc / (double) w) focal + height 0.5;
+ *              X = rint(u 256), Y = rint(v 256): 8 sub-pixel bits.  Pixel (row j, column i) is sampled at (X, Y) = (256 i,
+ *              256 j), without a half-pixel offset: get_ray_bundle's convention.  The camera-space ray is (x, y, -1) and w the
+ *              distance along the camera's axis; get_ray_bundle normalises its directions, so the NeRF's depth_map is w times
+ *              |(x, y, -1)| of the pixel (mesh_render.ray_lengths).  A vertex is NOT FINITE when a coordinate or w is not finite, OUT OF RANGE
+ *              when not |u 256| <= 2^24 or not |v 256| <= 2^24 (every edge function then stays below 2^51 in int64).
+ *   face       rejected, and counted under the FIRST of these reasons that holds: an index outside [0, V) (never
+ *              dereferenced); a corner not finite; a corner with w < near (there is no near-plane clipping: the count tells);
+ *              a corner out of range; back-facing under NM_MESH_RASTER_CULL_BACK (A > 0: clockwise on the screen, whose Y axis
+ *              points down; front faces wind counter-clockwise as seen, the OBJ convention); no pixel centre inside the
+ *              bounding box clipped to the screen; A == 0.  A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) in int64.
+ *   coverage   e0 = (X2 - X1)(Py - Y1) - (Y2 - Y1)(Px - X1), e1 and e2 with the corners rotated, in int64.  For A < 0 every e,
+ *              every edge vector and A change sign: the face with two corners swapped, the barycentrics staying in the face's
+ *              own corner order.  A pixel is inside when every e > 0, or e == 0 on a top or left edge (edge vector (dx, dy):
+ *              dy < 0, or dy == 0 and dx > 0).  A sheet of triangles covers every pixel exactly once, vertices on pixel
+ *              centres included.
+ *   depth      lk = (double) ek / (double) A; ik = 1.0 / (double) wk; q = (l0 i0 + l1 i1) + l2 i2; depth = (float)(1.0 / q);
+ *              bk = (float)((lk ik) / q).  A pixel whose depth is not finite or not > 0 is not covered.
+ *   winner     the minimum over the covering faces of (bits of depth) << 32 | face index: the nearest face, an exact tie to
+ *              the smallest index.
+ *
+ * nm_mesh_rasterize -> d_face_id (H,W) int32 (-1: nothing drawn), d_depth (H,W) fp32 (0), d_bary (H,W,3) fp32 (0) and, on the
+ *   DEVICE, d_counts[NM_MESH_RASTER_COUNTS] int64: the faces drawn, those rejected under each reason, those of the drawn ones
+ *   that took the large path, the covered pixels and the fragments -- the (face, pixel) pairs that passed the coverage and depth
+ *   rules, each of which is a candidate for the pixel's word: the most atomics a frame can issue -- the NM_MESH_RASTER_*
+ *   indices below.  A face whose clipped bounding box
+ *   holds more than large_threshold (>= 0) pixel centres is drawn by a whole wave, the others by one lane each: the same
+ *   bytes, another speed.  The entry allocates nothing and never waits for the host; it can be captured into a graph.
+ * nm_mesh_interpolate: out[p][c] = (b0 a0[c] + b1 a1[c]) + b2 a2[c] in fp32 with ak the rows of d_attributes (V,C), C in
+ *   [1, 16], at the corners of face d_face_id[p]; d_background[c] where the id is not in [0, F) or the face has an index
+ *   outside [0, V).  d_out is (pixels, C).  Capturable likewise.
+ * V and F are in [0, 2^31 - 64).  The workspace (nm_mesh_raster_workspace_bytes, 0 for sizes out of range; 256-byte aligned):
+ * 8 H W for the visibility words, 12 V for the projected vertices, 4 F for the queue of the large path.  Argument errors -- a
+ * null array with a non-zero size, an NDC view, near not finite and > 0, unknown flags, C out of range -- return 2 before any
+ * HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_MESH_RASTER_CULL_BACK 1
+#define NM_MESH_RASTER_DRAWN 0
+#define NM_MESH_RASTER_BAD_INDEX 1
+#define NM_MESH_RASTER_NOT_FINITE 2
+#define NM_MESH_RASTER_NEAR 3
+#define NM_MESH_RASTER_OUT_OF_RANGE 4
+#define NM_MESH_RASTER_CULLED 5
+#define NM_MESH_RASTER_OFF_SCREEN 6
+#define NM_MESH_RASTER_DEGENERATE 7
+#define NM_MESH_RASTER_LARGE 8
+#define NM_MESH_RASTER_COVERED 9
+#define NM_MESH_RASTER_FRAGMENTS 10
+#define NM_MESH_RASTER_COUNTS 11
+#define NM_MESH_INTERPOLATE_MAX_CHANNELS 16
+int64_t nm_mesh_raster_workspace_bytes(int64_t num_vertices, int64_t num_faces, int32_t height, int32_t width);
+int nm_mesh_rasterize(const nm_view* view, const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
+                      float near, int32_t flags, int32_t large_threshold, void* d_workspace, int32_t* d_face_id, float* d_depth,
+                      float* d_bary, int64_t* d_counts, void* stream);
+int nm_mesh_interpolate(const int32_t* d_face_id, const float* d_bary, int64_t num_pixels, const int32_t* d_faces, int64_t num_faces,
+                        const float* d_attributes, int64_t num_vertices, int32_t channels, const float* d_background, float* d_out,
+                        void* stream);
 
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex

@@ -214,6 +214,11 @@ SIGNATURES = {
     "nm_mesh_smooth_run": (C.c_int, [c_void_p, c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_int32, c_void_p, c_void_p]),
     "nm_mesh_vertex_normals": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int32, c_void_p, c_void_p,
                                          c_void_p]),
+    "nm_mesh_raster_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "nm_mesh_rasterize": (C.c_int, [C.POINTER(View), c_void_p, C.c_int64, c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_int32,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_interpolate": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, C.c_int32, c_void_p,
+                                      c_void_p, c_void_p]),
     "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 

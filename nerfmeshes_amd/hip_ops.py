@@ -886,6 +886,60 @@ def mesh_smooth(verts, faces, normals=None, iterations=10, lam=0.5, mu=-0.53, fr
     return out_verts, out_normals, info
 
 
+RASTER_CULL_BACK = 1                     # NM_MESH_RASTER_CULL_BACK
+RASTER_LARGE_THRESHOLD = 128             # pixel centres in a face's clipped bounding box above which a whole wave draws it: the
+                                         # same bytes, another speed (tests/tools/time_mesh_render.py measures it)
+RASTER_COUNTS = ("drawn", "bad_index", "not_finite", "near", "out_of_range", "culled", "off_screen", "degenerate", "large",
+                 "covered", "fragments")  # the NM_MESH_RASTER_* indices
+INTERPOLATE_MAX_CHANNELS = 16
+
+
+def mesh_rasterize(verts, faces, view, near, cull_back=False, large_threshold=None):
+    """Which face of a mesh a pinhole camera sees at every pixel (nm_mesh_rasterize; the rule in include/nerfmeshes_hip.h).
+    verts (V,3) f32, faces (F,3) i32 on the GPU, view: a non-NDC hip_ops.make_view, near > 0: a face with a corner nearer is
+    not drawn (there is no clipping).  -> (face_id (H,W) int32, -1 where nothing was drawn; depth (H,W) f32: the distance
+    along the camera's axis, 0 where nothing was drawn; bary (H,W,3) f32; counts: dict of RASTER_COUNTS -- the read-back of
+    this call).  Both windings are drawn unless cull_back, which drops the faces that wind clockwise on the screen."""
+    lib = _lib.load()
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = _dev32(verts, dev, "verts")
+    if verts.shape != (nv, 3):
+        raise ValueError(f"mesh_rasterize: verts must be (V,3), got {tuple(verts.shape)}")
+    height, width = int(view.height), int(view.width)
+    threshold = RASTER_LARGE_THRESHOLD if large_threshold is None else int(large_threshold)
+    ws = _mesh_workspace(int(lib.nm_mesh_raster_workspace_bytes(nv, nf, height, width)), "mesh raster", nv, nf, dev)
+    face_id = torch.empty(height, width, dtype=torch.int32, device=dev)
+    depth = torch.empty(height, width, dtype=torch.float32, device=dev)
+    bary = torch.empty(height, width, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(len(RASTER_COUNTS), dtype=torch.int64, device=dev)
+    rc = lib.nm_mesh_rasterize(C.byref(view), _ptr(verts), nv, _ptr(faces), nf, float(near), RASTER_CULL_BACK if cull_back else 0,
+                               threshold, _ptr(ws), _ptr(face_id), _ptr(depth), _ptr(bary), _ptr(counts), _stream())
+    _mesh_check(lib, rc, "nm_mesh_rasterize")
+    return face_id, depth, bary, dict(zip(RASTER_COUNTS, (int(x) for x in counts.tolist())))
+
+
+def mesh_interpolate(raster, faces, attributes, background):
+    """Per-vertex attributes at every pixel of a mesh_rasterize result (nm_mesh_interpolate): raster = (face_id, depth, bary,
+    ...) as returned, faces the (F,3) i32 faces it was drawn from, attributes (V,C) f32 with C in [1, 16], background: C
+    floats for the pixels nothing was drawn at.  -> (H,W,C) f32: (b0 a0 + b1 a1) + b2 a2 in fp32."""
+    lib = _lib.load()
+    face_id, bary = raster[0], raster[2]
+    attributes = _dev32(attributes, face_id.device, "attributes")
+    if attributes.dim() != 2:
+        raise ValueError(f"mesh_interpolate: attributes must be (V,C), got {tuple(attributes.shape)}")
+    faces, nv, nf = _mesh_faces(faces, attributes.shape[0])
+    channels = int(attributes.shape[1])
+    background = _dev32(torch.as_tensor(background, dtype=torch.float32).reshape(-1), face_id.device, "background")
+    if background.numel() != channels:
+        raise ValueError(f"mesh_interpolate: {background.numel()} background values for {channels} channels")
+    out = torch.empty(*face_id.shape, channels, dtype=torch.float32, device=face_id.device)
+    rc = lib.nm_mesh_interpolate(_ptr(face_id), _ptr(bary), face_id.numel(), _ptr(faces), nf, _ptr(attributes), nv, channels,
+                                 _ptr(background), _ptr(out), _stream())
+    _mesh_check(lib, rc, "nm_mesh_interpolate")
+    return out
+
+
 def _mesh_arrays(verts, faces, what):
     """(V,3) fp32 vertices and (F,3) int32 faces of one mesh on the GPU (host arrays are copied over), checked."""
     verts = _dev32(verts if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.as_tensor(verts).cuda(), name="verts")

@@ -392,6 +392,12 @@ def export_marching_cubes(model, args, cfg, device):
             raise ValueError("--target-mesh has no --route script: the reference's script has no such step")
         if int(args.chamfer_samples) < 1:
             raise ValueError(f"--chamfer-samples must be >= 1, got {args.chamfer_samples}")
+    render_views = int(getattr(args, "render_views", 0))
+    if render_views:
+        if getattr(args, "route", "kernel") == "script":
+            raise ValueError("--render-views has no --route script: the reference's script has no such step")
+        if render_views < 0 or not 1 <= int(args.render_size) <= 16384:
+            raise ValueError("--render-views must be >= 0 and --render-size in [1, 16384]")
     from . import dist as nd
     cache_path = os.path.join(args.save_dir, args.cache_name)
     cached = os.path.exists(cache_path)
@@ -469,7 +475,33 @@ def export_marching_cubes(model, args, cfg, device):
         model.set_precision("f32")
     if rank == 0:
         export_obj(vertices.cpu(), triangles.cpu(), diffuse, normals.cpu(), os.path.join(args.save_dir, args.mesh_name))
+    if render_views:
+        render_report(model, vertices, triangles, diffuse, args, cfg, device)
     return vertices, triangles, normals, diffuse
+
+
+def render_report(model, vertices, triangles, diffuse, args, cfg, device):
+    """`--render-views N`: the exported mesh drawn from N orbit poses at --render-size (mesh_render.evaluate) against the
+    network's own render of each pose -- PSNR, depth difference, silhouette IoU --, printed; rank 0 writes
+    <save-dir>/<mesh-name stem>.render.json.  Under torch.distributed the views are dealt out over the ranks."""
+    from . import dist as nd
+    from . import mesh_render, synthetic
+    if not (hasattr(model, "can_query_view") and model.can_query_view()):
+        raise ValueError("--render-views needs a model that renders a view from its pose (query_view)")
+    size = int(args.render_size)
+    views = mesh_render.orbit_views(int(args.render_views), size, size, synthetic.LEGO_FOCAL_800 * size / 800.0)
+    bounds = torch.tensor([cfg.dataset.near, cfg.dataset.far], dtype=torch.float32)
+    background = (1.0,) * 3 if cfg.dataset.white_background else (0.0,) * 3
+    report = mesh_render.evaluate(vertices, triangles.to(torch.int32), torch.as_tensor(diffuse), views, cfg.dataset.near / 4,
+                                  background, model=model, bounds=bounds, chunksize=cfg.nerf.validation.chunksize,
+                                  compare_nerf=True, device=device)
+    for line in mesh_render.format_report(report):
+        print(line)
+    if nd.world()[0] == 0:
+        path = os.path.join(args.save_dir, os.path.splitext(args.mesh_name)[0] + ".render.json")
+        mesh_render.write_report(report, path)
+        print(f"Mesh render report saved to {path}")
+    return report
 
 
 def _non_negative(text):
@@ -539,6 +571,11 @@ def build_parser():
                         "on the GPU, world coordinates) and write <save-dir>/<mesh-name stem>.chamfer.json")
     p.add_argument("--chamfer-samples", type=int, default=100000, help="(addition) points sampled on each mesh for --target-mesh")
     p.add_argument("--chamfer-seed", type=int, default=0, help="(addition) seed of the device generator the samples are drawn from")
+    p.add_argument("--render-views", type=_non_negative, default=0,
+                   help="(addition) after the OBJ is written, draw the mesh from this many orbit poses on the GPU and report it "
+                        "against the network's own render of each pose: PSNR, depth difference, silhouette IoU; writes "
+                        "<save-dir>/<mesh-name stem>.render.json (0 = off)")
+    p.add_argument("--render-size", type=int, default=800, help="(addition) side in pixels of the --render-views images")
     p.add_argument("--gather", choices=("triangles", "grid"), default="triangles",
                    help="(addition, multi-GPU) what travels between the ranks: the emitted triangles of per-slab marching "
                         "cubes (default) or the density grid")

@@ -189,3 +189,27 @@ def load_obj(path):
     v = np.asarray(verts, dtype=np.float64).astype(np.float32).reshape(-1, 3)
     f = np.asarray(faces, dtype=np.int64).astype(np.int32).reshape(-1, 3)
     return torch.from_numpy(v), torch.from_numpy(f)
+
+
+def load_obj_attributes(path):
+    """`load_obj` plus what `export_obj` writes beside the positions -> (verts, faces, colors, normals): colors (V,3) f32
+    from `v x y z r g b` lines, None unless EVERY vertex line carries three colour columns; normals (V,3) f32 from the `vn`
+    lines, None unless there are exactly as many as vertices (export_obj's `f a//a` pairs normal i with vertex i).  The
+    printed numbers read back to the fp32 values that were written."""
+    verts, faces = load_obj(path)
+    colors, normals = [], []
+    with open(path, "r", errors="replace") as fh:
+        for lineno, line in enumerate(fh, 1):
+            if line.startswith(("v ", "v\t", "vn ", "vn\t")):
+                parts = line.split()
+                try:
+                    if parts[0] == "vn":
+                        normals.append((float(parts[1]), float(parts[2]), float(parts[3])))
+                    elif len(parts) >= 7:
+                        colors.append((float(parts[4]), float(parts[5]), float(parts[6])))
+                except (IndexError, ValueError):
+                    raise ValueError(f"{path}:{lineno}: cannot read the numbers of {line.strip()!r}") from None
+    count = verts.shape[0]
+    as_rows = lambda rows: torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(np.float32).reshape(-1, 3))  # noqa: E731
+    return (verts, faces, as_rows(colors) if count and len(colors) == count else None,
+            as_rows(normals) if count and len(normals) == count else None)
