@@ -297,6 +297,7 @@ __global__ void perturb_intervals_kernel(const float* __restrict__ t, const floa
 //   w_k = alpha_k * T_k,  T_k = prod_{j<k} (1 - alpha_j + 1e-10),  alpha_k = 1 - exp(-relu(sigma_k + noise_k) * dist_k)
 //   dL/dw_k = G_rgb . rgb_k + G_acc + G_depth * t_k + G_w[k] (- sum(G_rgb) with a white background)
 //   dL/dalpha_k = dL/dw_k * T_k - (sum_{j>k} dL/dw_j * w_j) / (1 - alpha_k + 1e-10)
+//   dL/dsigma_k = dL/dalpha_k * dist_k * exp(-relu(sigma_k + noise_k) * dist_k)   where sigma_k + noise_k > 0
 // One wave per ray, lane owns PER consecutive samples (the forward kernel's layout): T_k from the same fp64 exclusive
 // product scan as the forward, the suffix sums sum_{j>k} dL/dw_j * w_j from an fp64 suffix scan (reverse lane order).
 // (Until round 5: one THREAD per ray, two sequential sweeps over its samples with T_k / alpha_k parked in the output rows --
@@ -320,13 +321,13 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
     const float gacc = (g.d_acc_map ? g.d_acc_map[ray] : 0.0f) - (white_bg ? (gr + gg + gb) : 0.0f);
     const float gdepth = g.d_depth_map ? g.d_depth_map[ray] : 0.0f;
 
-    float alpha[PER], dist[PER], dw[PER], raw[PER];
+    float alpha[PER], decay[PER], dist[PER], dw[PER], raw[PER];
     f32x4 rad[PER];
     double local = 1.0;
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
         const int s = lane * PER + q;
-        alpha[q] = 0.0f; dist[q] = 0.0f; dw[q] = 0.0f; raw[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
+        alpha[q] = 0.0f; decay[q] = 1.0f; dist[q] = 0.0f; dw[q] = 0.0f; raw[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
         if (s < samples) {
             const float ts = tr[s];
             rad[q] = rr[s];
@@ -334,7 +335,8 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
             d = d * norm;
             dist[q] = d;
             raw[q] = rad[q][3] + (noise ? noise[ray * samples + s] : 0.0f);
-            alpha[q] = 1.0f - expf(-fmaxf(raw[q], 0.0f) * d);
+            decay[q] = expf(-fmaxf(raw[q], 0.0f) * d);          // d alpha / d (sigma * dist): autograd keeps exp's result
+            alpha[q] = 1.0f - decay[q];
             local *= (double)((1.0f - alpha[q]) + 1e-10f);
             dw[q] = (gr * rad[q][0] + gg * rad[q][1] + gb * rad[q][2]) + gacc + gdepth * ts;
             if (g.d_weights) dw[q] += g.d_weights[ray * samples + s];
@@ -360,7 +362,8 @@ __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __
             const float keep = (1.0f - alpha[q]) + 1e-10f;
             const float dalpha = dw[q] * T[q] - (float)suffix / keep;
             suffix += (double)(dw[q] * w);
-            const float dsigma = raw[q] > 0.0f ? dalpha * dist[q] * (1.0f - alpha[q]) : 0.0f;
+            // (not 1 - alpha: the subtraction has lost exp's low bits, all of them from alpha == 1.0f on)
+            const float dsigma = raw[q] > 0.0f ? dalpha * dist[q] * decay[q] : 0.0f;
             out[s] = f32x4{w * gr, w * gg, w * gb, dsigma};
         }
     }
@@ -442,8 +445,38 @@ __global__ __launch_bounds__(256) void composite_long_kernel(const float* __rest
     }
 }
 
-// backward, two sweeps: the first yields total = sum_j dL/dw_j * w_j, the second walks the samples again with the running
-// prefix, so that the suffix sum_{j>k} of the one-pass kernel is total - prefix_k - dL/dw_k * w_k (all fp64)
+// (1 - alpha + 1e-10) over the 512 samples from `base` on, times `carry`: the transmittance in front of the next segment, formed as
+// composite_long_kernel forms it (the same fp64 products in the same order)
+__device__ __forceinline__ double long_segment_transmittance(const float* __restrict__ tr, const f32x4* __restrict__ rr,
+                                                             const float* __restrict__ noise_row, int samples, float norm, int base,
+                                                             int lane, double carry) {
+    constexpr int PER = 8;
+    float keep[PER];
+    double local = 1.0;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int s = base + lane * PER + q;
+        keep[q] = 1.0f;
+        if (s < samples) {
+            const float ts = tr[s];
+            float d = (s + 1 < samples) ? (tr[s + 1] - ts) : 1e10f;
+            d = d * norm;
+            const float alpha = 1.0f - expf(-fmaxf(rr[s][3] + (noise_row ? noise_row[s] : 0.0f), 0.0f) * d);
+            keep[q] = (1.0f - alpha) + 1e-10f;
+            local *= (double)keep[q];
+        }
+    }
+    double run = carry * wave_exclusive_scan<true>(local, lane);
+#pragma unroll
+    for (int q = 0; q < PER; ++q) run *= (double)keep[q];
+    return shfl_f64(run, 63);
+}
+
+// backward: the segments from the far end to the near one, each as the one-pass kernel does its samples, with the sum of
+// dL/dw_j * w_j over the segments already done carried in fp64.  (total - prefix in a near-to-far walk is the same number on
+// paper; behind a surface, where the true sum is 1e-10 of the total or less, it is the rounding error of the total.)  The
+// transmittance in front of a segment is the product over the segments before it, formed again for each: one more pass over
+// the ray's depths and densities per segment in front.
 __global__ __launch_bounds__(256) void composite_backward_long_kernel(const float* __restrict__ radiance, const float* __restrict__ t,
                                                                       const float* __restrict__ dirs, const float* __restrict__ noise,
                                                                       int64_t rays, int samples, int white_bg, nm_bundle_grads g,
@@ -454,64 +487,62 @@ __global__ __launch_bounds__(256) void composite_backward_long_kernel(const floa
     if (ray >= rays) return;
     const float norm = torch_norm3(dirs[3 * ray], dirs[3 * ray + 1], dirs[3 * ray + 2]);
     const float* tr = t + ray * samples;
+    const float* noise_row = noise ? noise + ray * samples : nullptr;
     const f32x4* rr = reinterpret_cast<const f32x4*>(radiance) + ray * samples;
     f32x4* out = reinterpret_cast<f32x4*>(grad_radiance) + ray * samples;
     float gr = 0.0f, gg = 0.0f, gb = 0.0f;
     if (g.d_rgb_map) { gr = g.d_rgb_map[3 * ray]; gg = g.d_rgb_map[3 * ray + 1]; gb = g.d_rgb_map[3 * ray + 2]; }
     const float gacc = (g.d_acc_map ? g.d_acc_map[ray] : 0.0f) - (white_bg ? (gr + gg + gb) : 0.0f);
     const float gdepth = g.d_depth_map ? g.d_depth_map[ray] : 0.0f;
-    double total = 0.0;
-    for (int sweep = 0; sweep < 2; ++sweep) {
-        double carry = 1.0, prefix = 0.0;                     // transmittance / sum of dL/dw_j * w_j in front of this segment
-        for (int base = 0; base < samples; base += 64 * PER) {
-            float alpha[PER], dist[PER], dw[PER], raw[PER];
-            f32x4 rad[PER];
-            double local = 1.0;
+    double behind = 0.0;                                      // sum of dL/dw_j * w_j over the segments behind this one
+    for (int base = (samples - 1) / (64 * PER) * (64 * PER); base >= 0; base -= 64 * PER) {
+        double carry = 1.0;                                   // transmittance in front of this segment
+        for (int b = 0; b < base; b += 64 * PER) carry = long_segment_transmittance(tr, rr, noise_row, samples, norm, b, lane, carry);
+        float alpha[PER], decay[PER], dist[PER], dw[PER], raw[PER];
+        f32x4 rad[PER];
+        double local = 1.0;
 #pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                const int s = base + lane * PER + q;
-                alpha[q] = 0.0f; dist[q] = 0.0f; dw[q] = 0.0f; raw[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
-                if (s < samples) {
-                    const float ts = tr[s];
-                    rad[q] = rr[s];
-                    float d = (s + 1 < samples) ? (tr[s + 1] - ts) : 1e10f;
-                    d = d * norm;
-                    dist[q] = d;
-                    raw[q] = rad[q][3] + (noise ? noise[ray * samples + s] : 0.0f);
-                    alpha[q] = 1.0f - expf(-fmaxf(raw[q], 0.0f) * d);
-                    local *= (double)((1.0f - alpha[q]) + 1e-10f);
-                    dw[q] = (gr * rad[q][0] + gg * rad[q][1] + gb * rad[q][2]) + gacc + gdepth * ts;
-                    if (g.d_weights) dw[q] += g.d_weights[ray * samples + s];
-                }
-            }
-            double run = carry * wave_exclusive_scan<true>(local, lane);
-            float T[PER];
-            double own = 0.0;
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                T[q] = (float)run;
-                run *= (double)((1.0f - alpha[q]) + 1e-10f);
-                own += (double)(dw[q] * (alpha[q] * T[q]));
-            }
-            carry = shfl_f64(run, 63);
-            const double before = prefix + wave_exclusive_scan<false>(own, lane);    // everything in front of this lane's samples
-            prefix = shfl_f64(before + own, 63);
-            if (sweep == 0) continue;
-            double done = before;
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                const int s = base + lane * PER + q;
-                if (s < samples) {
-                    const float w = alpha[q] * T[q];
-                    const float keep = (1.0f - alpha[q]) + 1e-10f;
-                    done += (double)(dw[q] * w);
-                    const float dalpha = dw[q] * T[q] - (float)(total - done) / keep;
-                    const float dsigma = raw[q] > 0.0f ? dalpha * dist[q] * (1.0f - alpha[q]) : 0.0f;
-                    out[s] = f32x4{w * gr, w * gg, w * gb, dsigma};
-                }
+        for (int q = 0; q < PER; ++q) {
+            const int s = base + lane * PER + q;
+            alpha[q] = 0.0f; decay[q] = 1.0f; dist[q] = 0.0f; dw[q] = 0.0f; raw[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
+            if (s < samples) {
+                const float ts = tr[s];
+                rad[q] = rr[s];
+                float d = (s + 1 < samples) ? (tr[s + 1] - ts) : 1e10f;
+                d = d * norm;
+                dist[q] = d;
+                raw[q] = rad[q][3] + (noise_row ? noise_row[s] : 0.0f);
+                decay[q] = expf(-fmaxf(raw[q], 0.0f) * d);
+                alpha[q] = 1.0f - decay[q];
+                local *= (double)((1.0f - alpha[q]) + 1e-10f);
+                dw[q] = (gr * rad[q][0] + gg * rad[q][1] + gb * rad[q][2]) + gacc + gdepth * ts;
+                if (g.d_weights) dw[q] += g.d_weights[ray * samples + s];
             }
         }
-        total = prefix;
+        double run = carry * wave_exclusive_scan<true>(local, lane);
+        float T[PER];
+        double own = 0.0;
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            T[q] = (float)run;
+            run *= (double)((1.0f - alpha[q]) + 1e-10f);
+            own += (double)(dw[q] * (alpha[q] * T[q]));
+        }
+        const double after = wave_exclusive_scan<false>(shfl_f64(own, 63 - lane), lane);    // the lanes above this one, as the one-pass kernel
+        double suffix = behind + shfl_f64(after, 63 - lane);
+#pragma unroll
+        for (int q = PER - 1; q >= 0; --q) {
+            const int s = base + lane * PER + q;
+            if (s < samples) {
+                const float w = alpha[q] * T[q];
+                const float keep = (1.0f - alpha[q]) + 1e-10f;
+                const float dalpha = dw[q] * T[q] - (float)suffix / keep;
+                suffix += (double)(dw[q] * w);
+                const float dsigma = raw[q] > 0.0f ? dalpha * dist[q] * decay[q] : 0.0f;
+                out[s] = f32x4{w * gr, w * gg, w * gb, dsigma};
+            }
+        }
+        behind = shfl_f64(suffix, 0);                         // lane 0 has walked down to the segment's first sample
     }
 }
 

@@ -257,7 +257,8 @@ def test_coarse_intervals_bit_exact(ops, lindisp, per_ray):
 
 
 # 513 / 700 / 1500: beyond one 512-sample pass -- the segmented kernel (the reference takes any count: modules.py:67-121)
-@pytest.mark.parametrize("samples", [32, 64, 192, 200, 512, 513, 700, 1500])
+# 100 / 300: composite_kernel<2> and lanes of composite_kernel<8> without a sample
+@pytest.mark.parametrize("samples", [32, 64, 100, 192, 200, 300, 512, 513, 700, 1500])
 @pytest.mark.parametrize("white", [False, True])
 def test_composite_vs_oracle(ops, samples, white):
     g = torch.Generator().manual_seed(samples)

@@ -231,11 +231,9 @@ def _model(cfg_kw, seed=0):
     return models.NeRFModel(cfg).cuda()
 
 
-def test_end_to_end_loss_gradients_vs_oracle_autograd():
-    """NeRFModel.forward in train() mode, loss as training_step's (coarse + fine MSE), backward: gradients of all
-    54 parameter tensors against fp64 autograd through the oracle on the SAME sample depths."""
+def _end_to_end_loss_gradients(num_coarse, num_fine):
     kw = dict(num_layers=4, hidden_size=64, skip_step=2, num_encoding_fn_xyz=6, num_encoding_fn_dir=4)
-    model = _model(dict(num_coarse=16, num_fine=16, train_noise_std=0.0, **kw))
+    model = _model(dict(num_coarse=num_coarse, num_fine=num_fine, train_noise_std=0.0, **kw))
     with torch.no_grad():     # a scene with visible structure: scale sigma
         for net in (model.model_coarse, model.model_fine):
             net.fc_alpha.weight.mul_(40.0)
@@ -249,14 +247,14 @@ def test_end_to_end_loss_gradients_vs_oracle_autograd():
     loss.backward()
 
     spec = O.MLPSpec(**kw)
-    rs = O.RenderSpec(num_coarse=16, num_fine=16, training=True)
+    rs = O.RenderSpec(num_coarse=num_coarse, num_fine=num_fine, training=True)
     total, grads = 0.0, {}
-    t_c = O.coarse_intervals(2.0, 6.0, 16, rays)
+    t_c = O.coarse_intervals(2.0, 6.0, num_coarse, rays)
     # the fine depths the model used: the same kernel call on the same coarse weights (the oracle's inverse CDF moves a
     # few depths in thin pdf bins, which is the resampling's conditioning and not what this test is about)
     from nerfmeshes_amd import hip_ops
     t_f = hip_ops.sample_pdf(t_c.cuda(), coarse.weights.detach(), model.sample_pdf.u).cpu()
-    assert float((t_f - O.sample_pdf_intervals(t_c, coarse.weights.detach().cpu(), 16)).abs().median()) == 0.0
+    assert float((t_f - O.sample_pdf_intervals(t_c, coarse.weights.detach().cpu(), num_fine)).abs().median()) == 0.0
     for name, net, t in (("model_coarse", model.model_coarse, t_c), ("model_fine", model.model_fine, t_f)):
         wd = {k: v.detach().double().cpu().requires_grad_(True) for k, v in net.named_parameters()}
         pts = O.ray_points(t.double(), d.double(), o[:1].double()).reshape(-1, 3)
@@ -272,6 +270,18 @@ def test_end_to_end_loss_gradients_vs_oracle_autograd():
         for k, p in net.named_parameters():
             assert p.grad is not None, (name, k)
             assert _rel(p.grad, grads[name][k]) < 5e-4, (name, k, _rel(p.grad, grads[name][k]))
+
+
+def test_end_to_end_loss_gradients_vs_oracle_autograd():
+    """NeRFModel.forward in train() mode, loss as training_step's (coarse + fine MSE), backward: gradients of all
+    54 parameter tensors against fp64 autograd through the oracle on the SAME sample depths."""
+    _end_to_end_loss_gradients(16, 16)
+
+
+def test_end_to_end_loss_gradients_with_a_100_sample_fine_pass():
+    """The same with 40 + 60 samples: the fine pass composites 100 samples per ray, two per lane (composite_kernel<2> and
+    composite_backward_kernel<2>, which no 16 + 16 configuration reaches)."""
+    _end_to_end_loss_gradients(40, 60)
 
 
 @pytest.mark.parametrize("adam", [dict(), dict(fused=True), dict(foreach=False)], ids=["multi-tensor", "fused", "single-tensor"])
