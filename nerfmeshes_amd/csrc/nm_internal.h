@@ -39,8 +39,8 @@ enum MlpMode : int { MODE_POINTS = 0, MODE_RAYS = 1, MODE_GRID = 2, MODE_VIEW = 
 
 // Pinhole rays generated inside the consuming kernel from the camera pose (get_ray_bundle,
 // /root/reference/src/nerf/nerf_helpers.py:226-277, optionally followed by ndc_rays, :280-307): ray r of a launch
-// is pixel `first + r` (row-major).  The expressions are the ones ray_bundle_kernel / ndc_rays_kernel use, so a
-// render from the pose is bit-identical to a render from a materialised ray buffer.
+// is pixel `first + r` (row-major).  nm_ray_bundle and nm_view_rays materialise rays through nm_gen_ray and ndc_rays_kernel
+// calls nm_ndc_ray, so a render from the pose is bit-identical to a render from a materialised ray buffer.
 struct RayGen {
     float rot[9];            // c2w[:3,:3], row-major
     float origin[3];         // c2w[:3,3]

@@ -1,5 +1,6 @@
 // Per-ray primitives of the NeRF render path for gfx950: one 64-lane wavefront per ray, the
-// sample axis (<= 256) lives in the wave, scans and reductions are wavefront shuffles.
+// sample axis lives in the wave (compositing: up to 512 samples in one pass, 8 per lane, and any
+// count beyond that in segments of 512), scans and reductions are wavefront shuffles.
 //
 // Replaces (reference file:line under /root/reference/src):
 //   nerf/nerf_helpers.py:226-277  get_ray_bundle
@@ -30,6 +31,11 @@ __device__ __forceinline__ double shfl_up_f64(double v, int delta) {
     return __hiloint2double(hi, lo);
 }
 
+__device__ __forceinline__ double shfl_f64(double v, int src) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    return __hiloint2double(__shfl(hi, src), __shfl(lo, src));
+}
+
 // exclusive multiplicative / additive scan across the 64 lanes, fp64
 template <bool MUL>
 __device__ __forceinline__ double wave_exclusive_scan(double v, int lane) {
@@ -46,30 +52,17 @@ __device__ __forceinline__ double wave_exclusive_scan(double v, int lane) {
 __device__ __forceinline__ float torch_norm3(float x, float y, float z) { return nm_norm3(x, y, z); }
 
 // ---- R0: pinhole rays -----------------------------------------------------------------------
-struct Pose { float r[9]; };
-
-__global__ void ray_bundle_kernel(Pose pose, int height, int width, float focal, int64_t first, int64_t count,
-                                  float* __restrict__ dirs) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const int64_t pix = first + i;
-    const int row = (int)(pix / width), colx = (int)(pix - (int64_t)row * width);
-    const float x = ((float)colx - (float)(width * 0.5)) / focal;
-    const float y = -((float)row - (float)(height * 0.5)) / focal;
-    const float z = -1.0f;
-    const float n = torch_norm3(x, y, z);
-    const float dx = x / n, dy = y / n, dz = z / n;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) dirs[3 * i + a] = (dx * pose.r[3 * a] + dy * pose.r[3 * a + 1]) + dz * pose.r[3 * a + 2];
-}
-
+// the rays of `gen`, materialised; out_o == nullptr: the directions only (get_ray_bundle: one origin for all rays)
 __global__ void view_rays_kernel(const RayGen gen, int64_t rays, float* __restrict__ out_o, float* __restrict__ out_d) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rays) return;
     float o[3], d[3];
     nm_gen_ray(gen, i, o, d);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { out_o[3 * i + a] = o[a]; out_d[3 * i + a] = d[a]; }
+    for (int a = 0; a < 3; ++a) {
+        if (out_o) out_o[3 * i + a] = o[a];
+        out_d[3 * i + a] = d[a];
+    }
 }
 
 // ndc_rays (nerf_helpers.py:280-307) over n rays; origins (1,3) shared or (n,3)
@@ -127,13 +120,97 @@ __global__ void coarse_intervals_kernel(const float* __restrict__ u, const float
 }
 
 // ---- R4: alpha compositing ----------------------------------------------------------------------
-// One wave per ray; lane owns PER consecutive samples.
+// One wave per ray; a lane owns PER consecutive samples of a segment of 64 * PER.  LONG = false: the ray is one segment
+// (<= 512 samples).  LONG = true (PER = 8; no shipped config has such rays, modules.py:67-121 takes any count): segments of
+// 512, the transmittance carried from segment to segment in fp64.
+struct RayRows {             // one ray's rows of the inputs
+    const float* t;
+    const f32x4* rad;
+    const float* noise;      // or null
+    int samples;
+    float norm;              // of the ray's direction
+};
+
+__device__ __forceinline__ RayRows ray_rows(const float* __restrict__ radiance, const float* __restrict__ t,
+                                            const float* __restrict__ noise, int64_t ray, int samples, float norm) {
+    return RayRows{t + ray * samples, reinterpret_cast<const f32x4*>(radiance) + ray * samples,
+                   noise ? noise + ray * samples : nullptr, samples, norm};
+}
+
+// A lane's samples first .. first + PER - 1 (modules.py:82-93); past the ray's end a sample has alpha 0 and nothing is read.
 template <int PER>
+struct LaneSamples {
+    float t[PER], dist[PER], raw[PER], decay[PER];       // raw = sigma + noise, decay = exp(-relu(raw) * dist)
+    f32x4 rad[PER];
+    __device__ __forceinline__ float alpha(int q) const { return 1.0f - decay[q]; }
+    __device__ __forceinline__ float keep(int q) const { return (1.0f - alpha(q)) + 1e-10f; }
+};
+
+// Loads the lane's samples; returns the transmittance in front of the first of them: `carry` (the product of every keep() in
+// front of the segment) times the fp64 exclusive product scan over the lanes.
+template <int PER>
+__device__ __forceinline__ double load_samples(const RayRows& in, int first, int lane, double carry, LaneSamples<PER>& L) {
+    double local = 1.0;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int s = first + q;
+        L.t[q] = 0.0f; L.dist[q] = 0.0f; L.raw[q] = 0.0f; L.decay[q] = 1.0f; L.rad[q] = f32x4{0, 0, 0, 0};
+        if (s < in.samples) {
+            L.t[q] = in.t[s];
+            L.rad[q] = in.rad[s];
+            float d = (s + 1 < in.samples) ? (in.t[s + 1] - L.t[q]) : 1e10f;
+            d = d * in.norm;
+            L.dist[q] = d;
+            L.raw[q] = L.rad[q][3] + (in.noise ? in.noise[s] : 0.0f);
+            L.decay[q] = expf(-fmaxf(L.raw[q], 0.0f) * d);      // d alpha / d (sigma * dist) too: autograd keeps exp's result
+            local *= (double)L.keep(q);
+        }
+    }
+    return carry * wave_exclusive_scan<true>(local, lane);
+}
+
+// One segment of the forward: weights and mask of its samples, their terms added to the lane's five sums {r, g, b, acc, depth}.
+// Returns the lane's running product behind its last sample (lane 63: the transmittance in front of the next segment).
+template <int PER>
+__device__ __forceinline__ double composite_segment(const RayRows& in, int base, int lane, double carry, float thr,
+                                                    float* __restrict__ weights, float* __restrict__ mask_weights,
+                                                    float (&sum)[5]) {
+    LaneSamples<PER> L;
+    double run = load_samples<PER>(in, base + lane * PER, lane, carry, L);
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int s = base + lane * PER + q;
+        if (s < in.samples) {
+            const float T = (float)run;           // fp64 running product rounded per element, as torch.cumprod
+            const float w = L.alpha(q) * T;
+            if (weights) weights[s] = w;
+            if (mask_weights) mask_weights[s] = T > thr ? 1.0f : 0.0f;
+            sum[0] += w * L.rad[q][0]; sum[1] += w * L.rad[q][1]; sum[2] += w * L.rad[q][2];
+            sum[3] += w;
+            sum[4] += w * L.t[q];
+            run *= (double)L.keep(q);
+        }
+    }
+    return run;
+}
+
+// The transmittance behind the full segment at `base`, formed as composite_segment forms it (the same fp64 products in the same order)
+template <int PER>
+__device__ __forceinline__ double transmittance_segment(const RayRows& in, int base, int lane, double carry) {
+    LaneSamples<PER> L;
+    double run = load_samples<PER>(in, base + lane * PER, lane, carry, L);
+#pragma unroll
+    for (int q = 0; q < PER; ++q) run *= (double)L.keep(q);
+    return run;
+}
+
+template <int PER, bool LONG>
 __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict__ radiance,
                                                         const float* __restrict__ t, const float* __restrict__ dirs,
                                                         const float* __restrict__ noise, int64_t rays, int samples,
                                                         float thr, int white_bg, int training, nm_bundle_out out,
                                                         const RayGen gen) {
+    static_assert(!LONG || PER == 8, "rays of more than 512 samples are composited in segments of 512");
     const int lane = threadIdx.x & 63;
     const int64_t ray = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (ray >= rays) return;
@@ -145,43 +222,19 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* __restrict_
     } else {
         norm = torch_norm3(dirs[3 * ray], dirs[3 * ray + 1], dirs[3 * ray + 2]);
     }
-    const float* tr = t + ray * samples;
-    const f32x4* rr = reinterpret_cast<const f32x4*>(radiance) + ray * samples;
-
-    float alpha[PER], tt[PER];
-    f32x4 rad[PER];
-    double local = 1.0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int s = lane * PER + q;
-        alpha[q] = 0.0f; tt[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
-        if (s < samples) {
-            tt[q] = tr[s];
-            rad[q] = rr[s];
-            float dist = (s + 1 < samples) ? (tr[s + 1] - tt[q]) : 1e10f;
-            dist = dist * norm;
-            const float sig = fmaxf(rad[q][3] + (noise ? noise[ray * samples + s] : 0.0f), 0.0f);   // modules.py:82-93
-            alpha[q] = 1.0f - expf(-sig * dist);
-            local *= (double)((1.0f - alpha[q]) + 1e-10f);
-        }
+    const RayRows in = ray_rows(radiance, t, noise, ray, samples, norm);
+    float* weights = out.d_weights ? out.d_weights + ray * samples : nullptr;
+    float* mask_weights = out.d_mask_weights ? out.d_mask_weights + ray * samples : nullptr;
+    float sum[5] = {0, 0, 0, 0, 0};
+    if constexpr (LONG) {
+        double carry = 1.0;                       // product of (1 - alpha + 1e-10) over every earlier segment
+#pragma unroll 1
+        for (int base = 0; base < samples; base += 64 * PER)     // lane 63 has walked to the end of the segment
+            carry = shfl_f64(composite_segment<PER>(in, base, lane, carry, thr, weights, mask_weights, sum), 63);
+    } else {
+        composite_segment<PER>(in, 0, lane, 1.0, thr, weights, mask_weights, sum);
     }
-    double run = wave_exclusive_scan<true>(local, lane);  // product of everything before this lane
-    float r = 0, g = 0, b = 0, acc = 0, depth = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int s = lane * PER + q;
-        if (s < samples) {
-            const float T = (float)run;           // fp64 running product rounded per element, as torch.cumprod
-            const float w = alpha[q] * T;
-            if (out.d_weights) out.d_weights[ray * samples + s] = w;
-            if (out.d_mask_weights) out.d_mask_weights[ray * samples + s] = T > thr ? 1.0f : 0.0f;
-            r += w * rad[q][0]; g += w * rad[q][1]; b += w * rad[q][2];
-            acc += w;
-            depth += w * tt[q];
-            run *= (double)((1.0f - alpha[q]) + 1e-10f);
-        }
-    }
-    r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); acc = wave_sum(acc); depth = wave_sum(depth);
+    float r = wave_sum(sum[0]), g = wave_sum(sum[1]), b = wave_sum(sum[2]), acc = wave_sum(sum[3]), depth = wave_sum(sum[4]);
     if (lane == 0) {
         float disp = 1.0f / fmaxf(1e-10f, depth / acc);
         if (disp != disp || (depth / acc) != (depth / acc)) disp = 0.0f;  // NaN -> 0 (modules.py:107)
@@ -298,263 +351,115 @@ __global__ void perturb_intervals_kernel(const float* __restrict__ t, const floa
 //   dL/dw_k = G_rgb . rgb_k + G_acc + G_depth * t_k + G_w[k] (- sum(G_rgb) with a white background)
 //   dL/dalpha_k = dL/dw_k * T_k - (sum_{j>k} dL/dw_j * w_j) / (1 - alpha_k + 1e-10)
 //   dL/dsigma_k = dL/dalpha_k * dist_k * exp(-relu(sigma_k + noise_k) * dist_k)   where sigma_k + noise_k > 0
-// One wave per ray, lane owns PER consecutive samples (the forward kernel's layout): T_k from the same fp64 exclusive
-// product scan as the forward, the suffix sums sum_{j>k} dL/dw_j * w_j from an fp64 suffix scan (reverse lane order).
+// One wave per ray, the forward kernel's layout and segments: T_k from the same fp64 exclusive product scan as the forward, the
+// suffix sums sum_{j>k} dL/dw_j * w_j from an fp64 suffix scan (reverse lane order) and a walk from the lane's last sample down.
 // (Until round 5: one THREAD per ray, two sequential sweeps over its samples with T_k / alpha_k parked in the output rows --
 // 2048 threads for a 2048-ray batch, 0.12 ms per call, 0.25 ms of every training iteration.)
+struct RayGrads {            // one ray's upstream gradients
+    float r, g, b, acc, depth;       // acc: G_acc - sum(G_rgb) with a white background
+    const float* weights;            // the ray's row, or null
+};
+
+// One segment of the backward: `carry` is the transmittance in front of it, `behind` the sum of dL/dw_j * w_j over the samples
+// behind it.  Writes the segment's rows of the radiance gradient; returns the lane's suffix sum in front of its first sample
+// (lane 0: `behind` of the segment in front).
 template <int PER>
+__device__ __forceinline__ double composite_backward_segment(const RayRows& in, const RayGrads& G, int base, int lane, double carry,
+                                                             double behind, f32x4* __restrict__ out) {
+    LaneSamples<PER> L;
+    double run = load_samples<PER>(in, base + lane * PER, lane, carry, L);
+    float dw[PER], T[PER];
+    double own = 0.0;                                          // sum of dL/dw_j * w_j over this lane's samples
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int s = base + lane * PER + q;
+        dw[q] = 0.0f;
+        if (s < in.samples) {
+            dw[q] = (G.r * L.rad[q][0] + G.g * L.rad[q][1] + G.b * L.rad[q][2]) + G.acc + G.depth * L.t[q];
+            if (G.weights) dw[q] += G.weights[s];
+        }
+        T[q] = (float)run;                                     // fp64 running product rounded per element, as the forward
+        run *= (double)L.keep(q);
+        own += (double)(dw[q] * (L.alpha(q) * T[q]));
+    }
+    // suffix over the lanes above this one: exclusive additive scan in reversed lane order.  Accumulated from the far end: total -
+    // prefix in a near-to-far walk is the same number on paper; behind a surface, where the true sum is 1e-10 of the total or
+    // less, it is the rounding error of the total.
+    const double after = wave_exclusive_scan<false>(shfl_f64(own, 63 - lane), lane);
+    double suffix = behind + shfl_f64(after, 63 - lane);
+#pragma unroll
+    for (int q = PER - 1; q >= 0; --q) {
+        const int s = base + lane * PER + q;
+        if (s < in.samples) {
+            const float w = L.alpha(q) * T[q];
+            const float dalpha = dw[q] * T[q] - (float)suffix / L.keep(q);
+            suffix += (double)(dw[q] * w);
+            // (decay, not 1 - alpha: the subtraction has lost exp's low bits, all of them from alpha == 1.0f on)
+            const float dsigma = L.raw[q] > 0.0f ? dalpha * L.dist[q] * L.decay[q] : 0.0f;
+            out[s] = f32x4{w * G.r, w * G.g, w * G.b, dsigma};
+        }
+    }
+    return suffix;
+}
+
+// LONG: the segments from the far end to the near one.  The transmittance in front of a segment is the product over the segments
+// before it, formed again for each: one more pass over the ray's depths and densities per segment in front.
+template <int PER, bool LONG>
 __global__ __launch_bounds__(256) void composite_backward_kernel(const float* __restrict__ radiance,
                                                                  const float* __restrict__ t,
                                                                  const float* __restrict__ dirs,
                                                                  const float* __restrict__ noise, int64_t rays, int samples,
                                                                  int white_bg, nm_bundle_grads g,
                                                                  float* __restrict__ grad_radiance) {
+    static_assert(!LONG || PER == 8, "rays of more than 512 samples are composited in segments of 512");
     const int lane = threadIdx.x & 63;
     const int64_t ray = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (ray >= rays) return;
-    const float norm = torch_norm3(dirs[3 * ray], dirs[3 * ray + 1], dirs[3 * ray + 2]);
-    const float* tr = t + ray * samples;
-    const f32x4* rr = reinterpret_cast<const f32x4*>(radiance) + ray * samples;
+    const RayRows in = ray_rows(radiance, t, noise, ray, samples, torch_norm3(dirs[3 * ray], dirs[3 * ray + 1], dirs[3 * ray + 2]));
     f32x4* out = reinterpret_cast<f32x4*>(grad_radiance) + ray * samples;
     float gr = 0.0f, gg = 0.0f, gb = 0.0f;
     if (g.d_rgb_map) { gr = g.d_rgb_map[3 * ray]; gg = g.d_rgb_map[3 * ray + 1]; gb = g.d_rgb_map[3 * ray + 2]; }
     const float gacc = (g.d_acc_map ? g.d_acc_map[ray] : 0.0f) - (white_bg ? (gr + gg + gb) : 0.0f);
-    const float gdepth = g.d_depth_map ? g.d_depth_map[ray] : 0.0f;
-
-    float alpha[PER], decay[PER], dist[PER], dw[PER], raw[PER];
-    f32x4 rad[PER];
-    double local = 1.0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int s = lane * PER + q;
-        alpha[q] = 0.0f; decay[q] = 1.0f; dist[q] = 0.0f; dw[q] = 0.0f; raw[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
-        if (s < samples) {
-            const float ts = tr[s];
-            rad[q] = rr[s];
-            float d = (s + 1 < samples) ? (tr[s + 1] - ts) : 1e10f;
-            d = d * norm;
-            dist[q] = d;
-            raw[q] = rad[q][3] + (noise ? noise[ray * samples + s] : 0.0f);
-            decay[q] = expf(-fmaxf(raw[q], 0.0f) * d);          // d alpha / d (sigma * dist): autograd keeps exp's result
-            alpha[q] = 1.0f - decay[q];
-            local *= (double)((1.0f - alpha[q]) + 1e-10f);
-            dw[q] = (gr * rad[q][0] + gg * rad[q][1] + gb * rad[q][2]) + gacc + gdepth * ts;
-            if (g.d_weights) dw[q] += g.d_weights[ray * samples + s];
+    const RayGrads G{gr, gg, gb, gacc, g.d_depth_map ? g.d_depth_map[ray] : 0.0f, g.d_weights ? g.d_weights + ray * samples : nullptr};
+    if constexpr (LONG) {
+        double behind = 0.0;
+#pragma unroll 1
+        for (int base = (samples - 1) / (64 * PER) * (64 * PER); base >= 0; base -= 64 * PER) {
+            double carry = 1.0;
+#pragma unroll 1
+            for (int b = 0; b < base; b += 64 * PER) carry = shfl_f64(transmittance_segment<PER>(in, b, lane, carry), 63);
+            // lane 0 has walked down to the segment's first sample
+            behind = shfl_f64(composite_backward_segment<PER>(in, G, base, lane, carry, behind, out), 0);
         }
-    }
-    double run = wave_exclusive_scan<true>(local, lane);      // product of everything before this lane
-    float T[PER];
-    double own = 0.0;                                          // sum of dL/dw_j * w_j over this lane's samples
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        T[q] = (float)run;                                     // fp64 running product rounded per element, as the forward
-        run *= (double)((1.0f - alpha[q]) + 1e-10f);
-        own += (double)(dw[q] * (alpha[q] * T[q]));
-    }
-    // suffix over the lanes above this one: exclusive additive scan in reversed lane order
-    double after = wave_exclusive_scan<false>(__shfl(own, 63 - lane), lane);
-    double suffix = __shfl(after, 63 - lane);
-#pragma unroll
-    for (int q = PER - 1; q >= 0; --q) {
-        const int s = lane * PER + q;
-        if (s < samples) {
-            const float w = alpha[q] * T[q];
-            const float keep = (1.0f - alpha[q]) + 1e-10f;
-            const float dalpha = dw[q] * T[q] - (float)suffix / keep;
-            suffix += (double)(dw[q] * w);
-            // (not 1 - alpha: the subtraction has lost exp's low bits, all of them from alpha == 1.0f on)
-            const float dsigma = raw[q] > 0.0f ? dalpha * dist[q] * decay[q] : 0.0f;
-            out[s] = f32x4{w * gr, w * gg, w * gb, dsigma};
-        }
-    }
-}
-
-// ---- rays of MORE than 512 samples (no shipped config has them; /root/reference/src/nerf/modules.py:67-121 takes any count):
-// the same arithmetic in segments of 512 samples (8 per lane), the transmittance carried from segment to segment in fp64.
-// The <= 512 kernels above keep their one-pass form (and their bits).
-__device__ __forceinline__ double shfl_f64(double v, int src) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    return __hiloint2double(__shfl(hi, src), __shfl(lo, src));
-}
-
-__global__ __launch_bounds__(256) void composite_long_kernel(const float* __restrict__ radiance, const float* __restrict__ t,
-                                                             const float* __restrict__ dirs, const float* __restrict__ noise,
-                                                             int64_t rays, int samples, float thr, int white_bg, int training,
-                                                             nm_bundle_out out, const RayGen gen) {
-    constexpr int PER = 8;
-    const int lane = threadIdx.x & 63;
-    const int64_t ray = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (ray >= rays) return;
-    float norm;
-    if (gen.enabled) {
-        float go[3], gd[3];
-        nm_gen_ray(gen, ray, go, gd);
-        norm = torch_norm3(gd[0], gd[1], gd[2]);
     } else {
-        norm = torch_norm3(dirs[3 * ray], dirs[3 * ray + 1], dirs[3 * ray + 2]);
-    }
-    const float* tr = t + ray * samples;
-    const f32x4* rr = reinterpret_cast<const f32x4*>(radiance) + ray * samples;
-    double carry = 1.0;                                       // product of (1 - alpha + 1e-10) over every earlier segment
-    float r = 0, g = 0, b = 0, acc = 0, depth = 0;
-    for (int base = 0; base < samples; base += 64 * PER) {
-        float alpha[PER], tt[PER];
-        f32x4 rad[PER];
-        double local = 1.0;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int s = base + lane * PER + q;
-            alpha[q] = 0.0f; tt[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
-            if (s < samples) {
-                tt[q] = tr[s];
-                rad[q] = rr[s];
-                float dist = (s + 1 < samples) ? (tr[s + 1] - tt[q]) : 1e10f;
-                dist = dist * norm;
-                const float sig = fmaxf(rad[q][3] + (noise ? noise[ray * samples + s] : 0.0f), 0.0f);
-                alpha[q] = 1.0f - expf(-sig * dist);
-                local *= (double)((1.0f - alpha[q]) + 1e-10f);
-            }
-        }
-        double run = carry * wave_exclusive_scan<true>(local, lane);
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int s = base + lane * PER + q;
-            if (s < samples) {
-                const float T = (float)run;
-                const float w = alpha[q] * T;
-                if (out.d_weights) out.d_weights[ray * samples + s] = w;
-                if (out.d_mask_weights) out.d_mask_weights[ray * samples + s] = T > thr ? 1.0f : 0.0f;
-                r += w * rad[q][0]; g += w * rad[q][1]; b += w * rad[q][2];
-                acc += w;
-                depth += w * tt[q];
-                run *= (double)((1.0f - alpha[q]) + 1e-10f);
-            }
-        }
-        carry = shfl_f64(run, 63);                            // lane 63 has walked to the end of the segment
-    }
-    r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); acc = wave_sum(acc); depth = wave_sum(depth);
-    if (lane == 0) {
-        float disp = 1.0f / fmaxf(1e-10f, depth / acc);
-        if (disp != disp || (depth / acc) != (depth / acc)) disp = 0.0f;
-        if (!training && acc < 1.0f) depth = 0.0f;
-        if (white_bg) { const float bg = 1.0f - acc; r += bg; g += bg; b += bg; }
-        if (out.d_rgb_map) { out.d_rgb_map[3 * ray] = r; out.d_rgb_map[3 * ray + 1] = g; out.d_rgb_map[3 * ray + 2] = b; }
-        if (out.d_depth_map) out.d_depth_map[ray] = depth;
-        if (out.d_acc_map) out.d_acc_map[ray] = acc;
-        if (out.d_disp_map) out.d_disp_map[ray] = disp;
-    }
-}
-
-// (1 - alpha + 1e-10) over the 512 samples from `base` on, times `carry`: the transmittance in front of the next segment, formed as
-// composite_long_kernel forms it (the same fp64 products in the same order)
-__device__ __forceinline__ double long_segment_transmittance(const float* __restrict__ tr, const f32x4* __restrict__ rr,
-                                                             const float* __restrict__ noise_row, int samples, float norm, int base,
-                                                             int lane, double carry) {
-    constexpr int PER = 8;
-    float keep[PER];
-    double local = 1.0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const int s = base + lane * PER + q;
-        keep[q] = 1.0f;
-        if (s < samples) {
-            const float ts = tr[s];
-            float d = (s + 1 < samples) ? (tr[s + 1] - ts) : 1e10f;
-            d = d * norm;
-            const float alpha = 1.0f - expf(-fmaxf(rr[s][3] + (noise_row ? noise_row[s] : 0.0f), 0.0f) * d);
-            keep[q] = (1.0f - alpha) + 1e-10f;
-            local *= (double)keep[q];
-        }
-    }
-    double run = carry * wave_exclusive_scan<true>(local, lane);
-#pragma unroll
-    for (int q = 0; q < PER; ++q) run *= (double)keep[q];
-    return shfl_f64(run, 63);
-}
-
-// backward: the segments from the far end to the near one, each as the one-pass kernel does its samples, with the sum of
-// dL/dw_j * w_j over the segments already done carried in fp64.  (total - prefix in a near-to-far walk is the same number on
-// paper; behind a surface, where the true sum is 1e-10 of the total or less, it is the rounding error of the total.)  The
-// transmittance in front of a segment is the product over the segments before it, formed again for each: one more pass over
-// the ray's depths and densities per segment in front.
-__global__ __launch_bounds__(256) void composite_backward_long_kernel(const float* __restrict__ radiance, const float* __restrict__ t,
-                                                                      const float* __restrict__ dirs, const float* __restrict__ noise,
-                                                                      int64_t rays, int samples, int white_bg, nm_bundle_grads g,
-                                                                      float* __restrict__ grad_radiance) {
-    constexpr int PER = 8;
-    const int lane = threadIdx.x & 63;
-    const int64_t ray = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (ray >= rays) return;
-    const float norm = torch_norm3(dirs[3 * ray], dirs[3 * ray + 1], dirs[3 * ray + 2]);
-    const float* tr = t + ray * samples;
-    const float* noise_row = noise ? noise + ray * samples : nullptr;
-    const f32x4* rr = reinterpret_cast<const f32x4*>(radiance) + ray * samples;
-    f32x4* out = reinterpret_cast<f32x4*>(grad_radiance) + ray * samples;
-    float gr = 0.0f, gg = 0.0f, gb = 0.0f;
-    if (g.d_rgb_map) { gr = g.d_rgb_map[3 * ray]; gg = g.d_rgb_map[3 * ray + 1]; gb = g.d_rgb_map[3 * ray + 2]; }
-    const float gacc = (g.d_acc_map ? g.d_acc_map[ray] : 0.0f) - (white_bg ? (gr + gg + gb) : 0.0f);
-    const float gdepth = g.d_depth_map ? g.d_depth_map[ray] : 0.0f;
-    double behind = 0.0;                                      // sum of dL/dw_j * w_j over the segments behind this one
-    for (int base = (samples - 1) / (64 * PER) * (64 * PER); base >= 0; base -= 64 * PER) {
-        double carry = 1.0;                                   // transmittance in front of this segment
-        for (int b = 0; b < base; b += 64 * PER) carry = long_segment_transmittance(tr, rr, noise_row, samples, norm, b, lane, carry);
-        float alpha[PER], decay[PER], dist[PER], dw[PER], raw[PER];
-        f32x4 rad[PER];
-        double local = 1.0;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int s = base + lane * PER + q;
-            alpha[q] = 0.0f; decay[q] = 1.0f; dist[q] = 0.0f; dw[q] = 0.0f; raw[q] = 0.0f; rad[q] = f32x4{0, 0, 0, 0};
-            if (s < samples) {
-                const float ts = tr[s];
-                rad[q] = rr[s];
-                float d = (s + 1 < samples) ? (tr[s + 1] - ts) : 1e10f;
-                d = d * norm;
-                dist[q] = d;
-                raw[q] = rad[q][3] + (noise_row ? noise_row[s] : 0.0f);
-                decay[q] = expf(-fmaxf(raw[q], 0.0f) * d);
-                alpha[q] = 1.0f - decay[q];
-                local *= (double)((1.0f - alpha[q]) + 1e-10f);
-                dw[q] = (gr * rad[q][0] + gg * rad[q][1] + gb * rad[q][2]) + gacc + gdepth * ts;
-                if (g.d_weights) dw[q] += g.d_weights[ray * samples + s];
-            }
-        }
-        double run = carry * wave_exclusive_scan<true>(local, lane);
-        float T[PER];
-        double own = 0.0;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            T[q] = (float)run;
-            run *= (double)((1.0f - alpha[q]) + 1e-10f);
-            own += (double)(dw[q] * (alpha[q] * T[q]));
-        }
-        const double after = wave_exclusive_scan<false>(shfl_f64(own, 63 - lane), lane);    // the lanes above this one, as the one-pass kernel
-        double suffix = behind + shfl_f64(after, 63 - lane);
-#pragma unroll
-        for (int q = PER - 1; q >= 0; --q) {
-            const int s = base + lane * PER + q;
-            if (s < samples) {
-                const float w = alpha[q] * T[q];
-                const float keep = (1.0f - alpha[q]) + 1e-10f;
-                const float dalpha = dw[q] * T[q] - (float)suffix / keep;
-                suffix += (double)(dw[q] * w);
-                const float dsigma = raw[q] > 0.0f ? dalpha * dist[q] * decay[q] : 0.0f;
-                out[s] = f32x4{w * gr, w * gg, w * gb, dsigma};
-            }
-        }
-        behind = shfl_f64(suffix, 0);                         // lane 0 has walked down to the segment's first sample
+        composite_backward_segment<PER>(in, G, 0, lane, 1.0, 0.0, out);
     }
 }
 
 // ---- launchers ------------------------------------------------------------------------------------
-int launch_ray_bundle(const float* c2w, int height, int width, float focal, int64_t first, int64_t count, float* d_dirs,
-                      hipStream_t stream) {
-    if (count <= 0) return 0;
-    Pose p;
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) p.r[3 * a + b] = c2w[4 * a + b];
-    hipLaunchKernelGGL(ray_bundle_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, p, height, width,
-                       focal, first, count, d_dirs);
+// the pose and pixel grid of a RayGen (c2w: rows of 4 floats, 3 x 4 or 4 x 4); no NDC
+static void set_pose(RayGen* g, const float* c2w, int height, int width, float focal, int64_t first) {
+    memset(g, 0, sizeof(*g));
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) g->rot[3 * a + b] = c2w[4 * a + b];
+        g->origin[a] = c2w[4 * a + 3];
+    }
+    g->height = height; g->width = width; g->focal = focal;
+    g->enabled = 1; g->first = first;
+}
+
+// ndc_rays' python-float constants (nerf_helpers.py:288-303), computed in fp64 and rounded once, as torch does
+static void set_ndc_constants(RayGen* g, int height, int width, double focal, double near_) {
+    g->ndc_near = (float)near_;
+    g->c_w = (float)(-1.0 / (width / (2.0 * focal)));
+    g->c_h = (float)(-1.0 / (height / (2.0 * focal)));
+    g->two_near = (float)(2.0 * near_);
+    g->m_two_near = (float)(-2.0 * near_);
+}
+
+static int launch_view_rays(const RayGen& g, int64_t rays, float* d_origins, float* d_dirs, hipStream_t stream) {
+    if (rays <= 0) return 0;
+    hipLaunchKernelGGL(view_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, stream, g, rays, d_origins, d_dirs);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -569,6 +474,17 @@ int launch_coarse_intervals(const float* d_u, const float* d_near, const float* 
     return 0;
 }
 
+// KERNEL<PER, LONG>(...) on `rays` rays of `samples` samples, one wave per ray: one pass with the smallest PER of 1, 2, 3, 4, 8 that
+// holds the samples in 64 lanes, segments of 512 (PER = 8, LONG) beyond 512 samples
+#define NM_LAUNCH_COMPOSITE(KERNEL, rays, samples, stream, ...)                                                               \
+    do {                                                                                                                      \
+        const int per_ = ((samples) + 63) / 64;                                                                               \
+        auto* kernel_ = per_ == 1 ? KERNEL<1, false> : per_ == 2 ? KERNEL<2, false> : per_ == 3 ? KERNEL<3, false>            \
+                      : per_ == 4 ? KERNEL<4, false> : per_ <= 8 ? KERNEL<8, false> : KERNEL<8, true>;                        \
+        hipLaunchKernelGGL(kernel_, dim3((unsigned)(((rays) + 3) / 4)), dim3(256), 0, stream, __VA_ARGS__);                   \
+        NM_HIP_CHECK(hipGetLastError());                                                                                      \
+    } while (0)
+
 int launch_composite(const float* d_radiance, const float* d_t, const float* d_dirs, const float* d_noise, int64_t rays,
                      int samples, float thr, int white_bg, int training, const nm_bundle_out& out, hipStream_t stream,
                      const RayGen* gen_ptr = nullptr) {
@@ -576,26 +492,8 @@ int launch_composite(const float* d_radiance, const float* d_t, const float* d_d
     RayGen gen;
     if (gen_ptr) gen = *gen_ptr; else memset(&gen, 0, sizeof(gen));
     NM_REQUIRE(samples >= 1, "composite: samples per ray must be >= 1");
-    const dim3 grid((unsigned)((rays + 3) / 4)), block(256);
-    const int per = (samples + 63) / 64;
-    if (per > 8) {                        // more than 512 samples: segments of 512 (composite_long_kernel)
-        hipLaunchKernelGGL(composite_long_kernel, grid, block, 0, stream, d_radiance, d_t, d_dirs, d_noise, rays, samples, thr, white_bg,
-                           training, out, gen);
-        NM_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-#define NM_COMPOSITE(P)                                                                                      \
-    hipLaunchKernelGGL(composite_kernel<P>, grid, block, 0, stream, d_radiance, d_t, d_dirs, d_noise, rays, samples, \
-                       thr, white_bg, training, out, gen)
-    switch (per) {
-        case 1: NM_COMPOSITE(1); break;
-        case 2: NM_COMPOSITE(2); break;
-        case 3: NM_COMPOSITE(3); break;
-        case 4: NM_COMPOSITE(4); break;
-        default: NM_COMPOSITE(8); break;
-    }
-#undef NM_COMPOSITE
-    NM_HIP_CHECK(hipGetLastError());
+    NM_LAUNCH_COMPOSITE(composite_kernel, rays, samples, stream, d_radiance, d_t, d_dirs, d_noise, rays, samples, thr, white_bg, training, out,
+                        gen);
     return 0;
 }
 
@@ -625,7 +523,9 @@ int nm_ray_bundle(const float* h_c2w, int32_t height, int32_t width, float focal
     NM_REQUIRE(first >= 0 && count >= 0 && first + count <= (int64_t)height * width, "pixel range");
     if (h_origin)
         for (int a = 0; a < 3; ++a) h_origin[a] = h_c2w[4 * a + 3];
-    return launch_ray_bundle(h_c2w, height, width, focal, first, count, d_dirs, static_cast<hipStream_t>(stream));
+    RayGen g;
+    set_pose(&g, h_c2w, height, width, focal, first);
+    return launch_view_rays(g, count, nullptr, d_dirs, static_cast<hipStream_t>(stream));
 }
 
 int nm_coarse_intervals(const float* d_u, const float* d_near, const float* d_far, int bounds_per_ray, int lindisp,
@@ -674,25 +574,8 @@ int nm_composite_backward(const float* d_radiance, const float* d_t, const float
     NM_REQUIRE(d_radiance && d_t && d_dirs && grads && d_grad_radiance && rays >= 0, "bad argument");
     NM_REQUIRE(samples >= 1, "composite: samples per ray must be >= 1");
     if (rays == 0) return 0;
-    const dim3 grid((unsigned)((rays + 3) / 4)), block(256);
-    if (samples > 512) {
-        hipLaunchKernelGGL(composite_backward_long_kernel, grid, block, 0, static_cast<hipStream_t>(stream), d_radiance, d_t, d_dirs,
-                           d_noise, rays, samples, white_background, *grads, d_grad_radiance);
-        NM_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-#define NM_COMPOSITE_BWD(P)                                                                                                     \
-    hipLaunchKernelGGL(composite_backward_kernel<P>, grid, block, 0, static_cast<hipStream_t>(stream), d_radiance, d_t, d_dirs, \
-                       d_noise, rays, samples, white_background, *grads, d_grad_radiance)
-    switch ((samples + 63) / 64) {
-        case 1: NM_COMPOSITE_BWD(1); break;
-        case 2: NM_COMPOSITE_BWD(2); break;
-        case 3: NM_COMPOSITE_BWD(3); break;
-        case 4: NM_COMPOSITE_BWD(4); break;
-        default: NM_COMPOSITE_BWD(8); break;
-    }
-#undef NM_COMPOSITE_BWD
-    NM_HIP_CHECK(hipGetLastError());
+    NM_LAUNCH_COMPOSITE(composite_backward_kernel, rays, samples, static_cast<hipStream_t>(stream), d_radiance, d_t, d_dirs, d_noise, rays,
+                        samples, white_background, *grads, d_grad_radiance);
     return 0;
 }
 
@@ -772,19 +655,9 @@ int nm_render_rays(nm_mlp* coarse, nm_mlp* fine, const nm_render_cfg* cfg, const
 
 static int make_raygen(const nm_view* v, int64_t first, RayGen* g) {
     NM_REQUIRE(v && v->height > 0 && v->width > 0 && v->focal > 0.0, "bad view");
-    memset(g, 0, sizeof(*g));
-    for (int a = 0; a < 3; ++a) {
-        for (int b = 0; b < 3; ++b) g->rot[3 * a + b] = v->c2w[4 * a + b];
-        g->origin[a] = v->c2w[4 * a + 3];
-    }
-    g->height = v->height; g->width = v->width; g->focal = (float)v->focal;
-    g->enabled = 1; g->ndc = v->use_ndc ? 1 : 0; g->first = first;
-    // ndc_rays' python-float constants (nerf_helpers.py:288-303), computed in fp64 and rounded once, as torch does
-    g->ndc_near = (float)v->ndc_near;
-    g->c_w = (float)(-1.0 / (v->width / (2.0 * v->focal)));
-    g->c_h = (float)(-1.0 / (v->height / (2.0 * v->focal)));
-    g->two_near = (float)(2.0 * v->ndc_near);
-    g->m_two_near = (float)(-2.0 * v->ndc_near);
+    set_pose(g, v->c2w, v->height, v->width, (float)v->focal, first);
+    g->ndc = v->use_ndc ? 1 : 0;
+    set_ndc_constants(g, v->height, v->width, v->focal, v->ndc_near);
     return 0;
 }
 
@@ -807,11 +680,8 @@ int nm_view_rays(const nm_view* view, int64_t first_pixel, int64_t rays, float* 
     NM_REQUIRE(first_pixel >= 0 && rays >= 0 && first_pixel + rays <= (int64_t)view->height * view->width, "pixel range");
     RayGen g;
     int rc = make_raygen(view, first_pixel, &g);
-    if (rc || rays == 0) return rc;
-    hipLaunchKernelGGL(view_rays_kernel, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream_), g, rays, d_origins, d_dirs);
-    NM_HIP_CHECK(hipGetLastError());
-    return 0;
+    if (rc) return rc;
+    return launch_view_rays(g, rays, d_origins, d_dirs, static_cast<hipStream_t>(stream_));
 }
 
 int nm_ndc_rays(int32_t height, int32_t width, double focal, double near_, const float* d_origins, int origins_per_ray,
@@ -819,10 +689,11 @@ int nm_ndc_rays(int32_t height, int32_t width, double focal, double near_, const
     NM_REQUIRE(d_origins && d_dirs && d_out_origins && d_out_dirs && height > 0 && width > 0 && focal > 0.0 && n >= 0,
                "bad argument");
     if (n == 0) return 0;
+    RayGen g;
+    set_ndc_constants(&g, height, width, focal, near_);
     hipLaunchKernelGGL(ndc_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream_),
-                       d_origins, origins_per_ray, d_dirs, n, (float)near_, (float)(-1.0 / (width / (2.0 * focal))),
-                       (float)(-1.0 / (height / (2.0 * focal))), (float)(2.0 * near_), (float)(-2.0 * near_),
-                       d_out_origins, d_out_dirs);
+                       d_origins, origins_per_ray, d_dirs, n, g.ndc_near, g.c_w, g.c_h, g.two_near, g.m_two_near, d_out_origins,
+                       d_out_dirs);
     NM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -1,8 +1,8 @@
 """Inputs, references and tolerances of the training path's ray operators (nerfmeshes_amd/csrc/ray_ops.hip), shared by
 tests/test_ray_ops_inputs.py (no GPU) and tests/test_gpu_ray_ops.py.  Nothing here touches the GPU.
 
-Compositing (`composite_kernel<PER>` / `composite_long_kernel` in training mode and `composite_backward_kernel<1|2|3|4|8>` /
-`composite_backward_long_kernel`): 61 rays per case -- the last block of four waves has one live wave --, directions of any norm,
+Compositing (`composite_kernel<PER, LONG>` in training mode and `composite_backward_kernel<1|2|3|4|8, false>` / `<8, true>`, the
+long kernel): 61 rays per case -- the last block of four waves has one live wave --, directions of any norm,
 ray 0 with the zero direction, and five ray families of twelve rays each:
 
     random    sigma = 3 randn (what test_gpu_train.py uses)
@@ -55,7 +55,7 @@ RESTATEMENT_BOUND = 6.5
 
 
 def per_of(samples):
-    """The kernel instantiation a sample count reaches (ray_ops.hip: nm_composite_backward / launch_composite)."""
+    """The kernel instantiation a sample count reaches (ray_ops.hip: NM_LAUNCH_COMPOSITE)."""
     if samples > 512:
         return "long"
     per = (samples + 63) // 64
@@ -134,7 +134,7 @@ def oracle_backward(rad, t, dirs, noise, G, keys, white, dtype):
 
 
 def restated_backward(rad, t, dirs, noise, G, keys, white, total_minus_prefix=False, one_minus_alpha=False):
-    """The arithmetic of composite_backward_kernel and composite_backward_long_kernel on the CPU, written plainly: every
+    """The arithmetic of composite_backward_kernel (one pass and long) on the CPU, written plainly: every
     elementwise step in fp32, the transmittance an exclusive fp64 product rounded per element, the sum of dL/dw_j * w_j over the
     samples behind a sample accumulated in fp64 from the far end.  The host's expf stands in for the GPU's.
 
