@@ -54,6 +54,9 @@ extern "C" {
  * mesh and the vertex normals of the result (mesh_nerf --smooth-iters).  Additions only. */
 /* 6, later: + nm_mesh_rasterize (+ nm_mesh_raster_workspace_bytes), nm_mesh_interpolate: a deterministic software rasteriser of
  * the coloured mesh (mesh_render, mesh_nerf --render-views).  Additions only. */
+/* 6, later: + nm_mesh_texture_layout, _samples, _fill, _uv, _lookup, nm_export_obj_textured: a texture atlas of per-face
+ * charts baked from the network, and its fetch at the rasteriser's pixels (mesh_nerf --texture-res, mesh_render
+ * --appearance).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -956,6 +959,83 @@ int nm_mesh_rasterize(const nm_view* view, const float* d_verts, int64_t num_ver
 int nm_mesh_interpolate(const int32_t* d_face_id, const float* d_bary, int64_t num_pixels, const int32_t* d_faces, int64_t num_faces,
                         const float* d_attributes, int64_t num_vertices, int32_t channels, const float* d_background, float* d_out,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Texture atlas of a mesh (mesh_nerf --texture-res, mesh_render --appearance; DESIGN.md, "Texture atlas"): every face gets
+ * the same right-triangle chart on a barycentric lattice, two charts tile one cell, the cells tile the image.  Every index
+ * is a formula: no parametrisation, no packing, no compaction, and the bytes do not depend on the order of the workgroups.
+ * Every fp32 operation is rounded on its own, division and square root correctly rounded, so a numpy restatement
+ * (tests/mesh_texture.py) reproduces every output bit for bit.  THE RULE:
+ *
+ *   lattice    n in [1, 255] intervals per triangle side; T = (n + 1)(n + 2) / 2 samples per face: the lattice points (i, j)
+ *              with i, j >= 0 and i + j <= n, at index j (n + 1) - j (j - 1) / 2 + i within the face (rows of constant j, i
+ *              fastest); sample row of face f: f T + index.  Corner 0 of the face is lattice (0, 0), corner 1 is (n, 0),
+ *              corner 2 is (0, n): the weights are b1 = (float) i / (float) n, b2 = (float) j / (float) n,
+ *              b0 = (float)(n - i - j) / (float) n.
+ *   cell       Cw = n + 3 texels wide, Ch = n + 2 high.  Cell c holds face 2c ("lower") and face 2c + 1 ("upper").  Local
+ *              texel (a, b) belongs to the lower face when a + b <= n + 1, at lattice (a, b); otherwise to the upper face,
+ *              at lattice (n + 2 - a, n + 1 - b).  In either face a lattice point with i + j == n + 1 is on that face's
+ *              GUTTER diagonal.  2 T + 2 (n + 2) = Cw Ch: the two faces tile the cell and each owns its own gutter, which
+ *              is why the cell is one texel wider than high.
+ *   atlas      P = ceil(F / 2) cells; cols = the smallest integer >= 1 with cols Cw >= ceil(P / cols) Ch; rows =
+ *              ceil(P / cols); W = cols Cw, H = rows Ch, so H <= W.  Cell c starts at x0 = (c mod cols) Cw,
+ *              y0 = (c div cols) Ch; row 0 is the TOP row of the image.  Integer arithmetic only.  W > 16384 is refused.
+ *   gutter     for lattice (i, j) with i + j == n + 1, per channel in fp32: i, j >= 1: (c(i-1, j) + c(i, j-1)) - c(i-1, j-1);
+ *              i == 0: c(0, n); j == 0: c(n, 0).  A bilinear fetch inside a chart then equals linear interpolation on the
+ *              lattice triangle up to the hypotenuse, before quantisation.
+ *   empty      a texel of a face >= F (the upper face of the last cell when F is odd, the tail of the last row) is 0.
+ *   quantise   u8 = (uint8)(min(max(c, 0), 1) * 255 + 0.5), a NaN -> 0.
+ *   uv         per face corner, at the centre of the corner's texel (x, y): u = (float)(2x + 1) / (float)(2W),
+ *              v = (float)(2(H - y) - 1) / (float)(2H): v points up, the OBJ convention.
+ *   sample     position (b0 p0 + b1 p1) + b2 p2 per coordinate (nm_mesh_interpolate's order; a NaN is written as the
+ *              canonical 0x7fc00000).  Direction: m = the same blend of the corner normals, L = sqrt((mx mx + my my) + mz mz);
+ *              with L > 0 and finite, d = -(m / L).  Otherwise -- or without normals -- the sample is a FALLBACK sample:
+ *              e1 = p1 - p0, e2 = p2 - p0, g = e1 x e2 (gx = e1y e2z - e1z e2y, and cyclic), G = sqrt((gx gx + gy gy) + gz gz);
+ *              with G > 0 and finite, d = (g / G) * (float)(-flip), flip = +1 or -1 (marching cubes winds its triangles
+ *              against its normals: -1); otherwise d = (0, 0, -1).  A face with an index outside [0, V) is never
+ *              dereferenced: its rows are zeros, and its samples are counted under NM_MESH_TEXTURE_BAD_INDEX only.
+ *   lookup     per pixel with face_id f in [0, F): uv = (b0 uv0 + b1 uv1) + b2 uv2 per component with uvk the rows of
+ *              d_face_uv[f]; tx = u (float) Wt - 0.5, ty = (1 - v)(float) Ht - 0.5, each clamped: min(max(t, 0), side - 1)
+ *              (clamp to edge); ix0 = floor(tx), ix1 = min(ix0 + 1, Wt - 1), fx = tx - (float) ix0, likewise in y; texel
+ *              value (float) u8 / 255.0f; per channel top = c00 + fx (c10 - c00), bottom = c01 + fx (c11 - c01) with cXY the
+ *              texel (ixX, iyY), out = top + fy (bottom - top).  d_background where f is not in [0, F) or u or v is not finite.
+ *
+ * nm_mesh_texture_layout (host code; no HIP call): h_layout[NM_MESH_TEXTURE_LAYOUT] = W, H, cols, rows, T.
+ * nm_mesh_texture_samples: faces [first, first + count) -> d_positions, d_directions (count T, 3) fp32; d_normals (V,3) or
+ *   NULL; d_counts[2] int64 on the DEVICE: the fallback samples and the samples of faces with a bad index, of this window.
+ * nm_mesh_texture_fill: d_colors (F T, 3) fp32 -> d_atlas (H, W, 3) uint8.  nm_mesh_texture_uv -> d_face_uv (F, 3, 2) fp32.
+ * nm_mesh_texture_lookup: ANY d_face_uv (F,3,2) and ANY d_texture (Ht, Wt, 3) uint8 with sides in [1, 16384], at the pixels of
+ *   a nm_mesh_rasterize result -> d_out (pixels, 3) fp32.
+ * One thread per output element, nothing allocates and nothing waits for the host: every entry can be captured into a graph.
+ * F is in [0, 2^31 - 64), as is count T.  Argument errors -- a null array with a non-zero size, n outside [1, 255], a window
+ * outside [0, F], flip not +-1, sizes out of range, W > 16384 -- return 2 before any HIP call.
+ * nm_export_obj_textured (HOST arrays, as nm_export_obj, whose `v` and `vn` lines it writes byte for byte): `mtllib <mtllib>`,
+ *   the v lines, the vn lines, 3F lines `vt u v` from h_face_uv (F,3,2) (numbers printed by the same rule), `usemtl <material>`,
+ *   then `f a/t/a b/t/b c/t/c`, 1-based, t = 3f + k + 1.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_MESH_TEXTURE_MAX_RES 255
+#define NM_MESH_TEXTURE_MAX_SIDE 16384
+#define NM_MESH_TEXTURE_W 0
+#define NM_MESH_TEXTURE_H 1
+#define NM_MESH_TEXTURE_COLS 2
+#define NM_MESH_TEXTURE_ROWS 3
+#define NM_MESH_TEXTURE_T 4
+#define NM_MESH_TEXTURE_LAYOUT 5
+#define NM_MESH_TEXTURE_FALLBACK 0
+#define NM_MESH_TEXTURE_BAD_INDEX 1
+#define NM_MESH_TEXTURE_COUNTS 2
+int nm_mesh_texture_layout(int64_t num_faces, int32_t n, int64_t* h_layout);
+int nm_mesh_texture_samples(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
+                            const float* d_normals, int32_t n, int32_t flip, int64_t first, int64_t count, float* d_positions,
+                            float* d_directions, int64_t* d_counts, void* stream);
+int nm_mesh_texture_fill(const float* d_colors, int64_t num_faces, int32_t n, uint8_t* d_atlas, void* stream);
+int nm_mesh_texture_uv(int64_t num_faces, int32_t n, float* d_face_uv, void* stream);
+int nm_mesh_texture_lookup(const int32_t* d_face_id, const float* d_bary, int64_t num_pixels, const float* d_face_uv,
+                           int64_t num_faces, const uint8_t* d_texture, int32_t tex_height, int32_t tex_width,
+                           const float* d_background, float* d_out, void* stream);
+int nm_export_obj_textured(const float* h_vertices, int64_t num_vertices, const float* h_diffuse, int64_t num_diffuse,
+                           const float* h_normals, int64_t num_normals, const int32_t* h_triangles, int64_t num_triangles,
+                           const float* h_face_uv, const char* mtllib, const char* material, const char* path);
 
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex

@@ -219,6 +219,15 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nm_mesh_interpolate": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, C.c_int32, c_void_p,
                                       c_void_p, c_void_p]),
+    "nm_mesh_texture_layout": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "nm_mesh_texture_samples": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                          C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_texture_fill": (C.c_int, [c_void_p, C.c_int64, C.c_int32, c_void_p, c_void_p]),
+    "nm_mesh_texture_uv": (C.c_int, [C.c_int64, C.c_int32, c_void_p, c_void_p]),
+    "nm_mesh_texture_lookup": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int32, C.c_int32,
+                                         c_void_p, c_void_p, c_void_p]),
+    "nm_export_obj_textured": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64,
+                                         c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 

@@ -940,6 +940,100 @@ def mesh_interpolate(raster, faces, attributes, background):
     return out
 
 
+TEXTURE_MAX_RES = 255                    # NM_MESH_TEXTURE_MAX_RES
+TEXTURE_MAX_SIDE = 16384                 # NM_MESH_TEXTURE_MAX_SIDE
+
+
+def mesh_texture_layout(num_faces, n):
+    """The atlas of `num_faces` per-face charts at `n` lattice intervals per triangle side (nm_mesh_texture_layout: host code,
+    the rule in include/nerfmeshes_hip.h) -> dict(width, height, cols, rows, samples_per_face).  ValueError for no face, n
+    outside [1, 255] and an atlas wider than 16384 texels."""
+    lib = _lib.load()
+    num_faces, n = int(num_faces), int(n)
+    if num_faces <= 0:
+        raise ValueError(f"mesh texture: a mesh of {num_faces} faces has no atlas")
+    out = (C.c_int64 * 5)()
+    _mesh_check(lib, lib.nm_mesh_texture_layout(num_faces, n, out), "nm_mesh_texture_layout")
+    return dict(zip(("width", "height", "cols", "rows", "samples_per_face"), (int(x) for x in out)))
+
+
+def mesh_texture_samples(verts, faces, normals, n, first=0, count=None, flip=1):
+    """The surface samples behind the texels of faces [first, first + count) (nm_mesh_texture_samples): verts (V,3) f32, faces
+    (F,3) i32, normals (V,3) f32 or None, all on the GPU.  -> (positions (count*T, 3), directions (count*T, 3): minus the
+    interpolated unit normal, or minus flip times the face's geometric normal where there is none, fallback: how many samples
+    took that, bad: how many samples belong to faces with an index outside [0, V) -- their rows are zeros)."""
+    lib = _lib.load()
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = _dev32(verts, dev, "verts")
+    normals = _dev32(normals, dev, "normals") if normals is not None else None
+    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)):
+        raise ValueError("mesh_texture_samples: verts and normals must be (V,3)")
+    n, first = int(n), int(first)
+    if not 1 <= n <= TEXTURE_MAX_RES:
+        raise ValueError(f"mesh texture: the resolution n must be in [1, {TEXTURE_MAX_RES}], got {n}")
+    count = nf - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > nf:
+        raise ValueError(f"mesh_texture_samples: the window [{first}, {first + count}) is not inside [0, {nf}]")
+    rows = count * ((n + 1) * (n + 2) // 2)
+    positions = torch.empty(rows, 3, dtype=torch.float32, device=dev)
+    directions = torch.empty(rows, 3, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    rc = lib.nm_mesh_texture_samples(_ptr(verts), nv, _ptr(faces), nf, _ptr(normals), n, int(flip), first, count, _ptr(positions),
+                                     _ptr(directions), _ptr(counts), _stream())
+    _mesh_check(lib, rc, "nm_mesh_texture_samples")
+    fallback, bad = (int(x) for x in counts.tolist())
+    return positions, directions, fallback, bad
+
+
+def mesh_texture_fill(colors, num_faces, n):
+    """colors (F*T, 3) f32 on the GPU, in sample-row order -> the atlas (H, W, 3) uint8 (nm_mesh_texture_fill): every texel
+    copies its lattice point, extrapolates its chart's gutter or is 0, and is quantised."""
+    lib = _lib.load()
+    layout = mesh_texture_layout(num_faces, n)
+    colors = _dev32(colors, name="colors")
+    if colors.shape != (int(num_faces) * layout["samples_per_face"], 3):
+        raise ValueError(f"mesh_texture_fill: colors must be ({int(num_faces) * layout['samples_per_face']}, 3), got {tuple(colors.shape)}")
+    atlas = torch.empty(layout["height"], layout["width"], 3, dtype=torch.uint8, device=colors.device)
+    _mesh_check(lib, lib.nm_mesh_texture_fill(_ptr(colors), int(num_faces), int(n), _ptr(atlas), _stream()), "nm_mesh_texture_fill")
+    return atlas
+
+
+def mesh_texture_uv(num_faces, n, device="cuda"):
+    """-> (F,3,2) f32: the texture coordinates of every face corner in the atlas of mesh_texture_layout (nm_mesh_texture_uv)"""
+    lib = _lib.load()
+    mesh_texture_layout(num_faces, n)
+    uv = torch.empty(int(num_faces), 3, 2, dtype=torch.float32, device=device)
+    _mesh_check(lib, lib.nm_mesh_texture_uv(int(num_faces), int(n), _ptr(uv), _stream()), "nm_mesh_texture_uv")
+    return uv
+
+
+def mesh_texture_lookup(raster, face_uv, texture, background):
+    """The bilinear, clamp-to-edge fetch of a texture at every pixel of a mesh_rasterize result (nm_mesh_texture_lookup): raster =
+    (face_id, depth, bary, ...), face_uv (F,3,2) f32: ANY texture coordinates, v pointing up, texture (Ht,Wt,3) uint8: ANY
+    image, both on the GPU; background: three floats for the pixels nothing was drawn at or whose coordinates are not finite.
+    -> (H,W,3) f32."""
+    lib = _lib.load()
+    face_id, bary = raster[0], raster[2]
+    dev = face_id.device
+    face_uv = _dev32(face_uv, dev, "face_uv")
+    if face_uv.dim() != 3 or face_uv.shape[1:] != (3, 2):
+        raise ValueError(f"mesh_texture_lookup: face_uv must be (F,3,2), got {tuple(face_uv.shape)}")
+    if not isinstance(texture, torch.Tensor) or not texture.is_cuda:
+        raise _lib.HipLibraryError("texture must live in GPU memory; there is no CPU path")
+    if texture.dtype is not torch.uint8 or texture.dim() != 3 or texture.shape[2] != 3:
+        raise ValueError(f"mesh_texture_lookup: texture must be (Ht,Wt,3) uint8, got {tuple(texture.shape)} {texture.dtype}")
+    texture = texture.detach().to(dev).contiguous()
+    background = _dev32(torch.as_tensor(background, dtype=torch.float32).reshape(-1), dev, "background")
+    if background.numel() != 3:
+        raise ValueError(f"mesh_texture_lookup: {background.numel()} background values for 3 channels")
+    out = torch.empty(*face_id.shape, 3, dtype=torch.float32, device=dev)
+    rc = lib.nm_mesh_texture_lookup(_ptr(face_id), _ptr(bary), face_id.numel(), _ptr(face_uv), int(face_uv.shape[0]), _ptr(texture),
+                                    int(texture.shape[0]), int(texture.shape[1]), _ptr(background), _ptr(out), _stream())
+    _mesh_check(lib, rc, "nm_mesh_texture_lookup")
+    return out
+
+
 def _mesh_arrays(verts, faces, what):
     """(V,3) fp32 vertices and (F,3) int32 faces of one mesh on the GPU (host arrays are copied over), checked."""
     verts = _dev32(verts if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.as_tensor(verts).cuda(), name="verts")

@@ -23,7 +23,7 @@ import torch
 
 from . import hip_ops, models
 from .lightning_modules import PathParser
-from .nerf.nerf_helpers import batchify, export_obj
+from .nerf.nerf_helpers import batchify, export_obj, export_obj_textured
 
 
 def create_mesh(vertices, faces_idx):
@@ -359,7 +359,9 @@ def export_marching_cubes(model, args, cfg, device):
     unsimplified mesh, and every rank simplifies redundantly.
     `--smooth-iters N` smooths the full-resolution mesh (smooth_mesh) between the component filter and the clustering, which
     then averages smoothed positions and the recomputed normals; the cache keeps the unsmoothed mesh, and every rank smooths
-    redundantly."""
+    redundantly.
+    `--texture-res N` bakes a texture atlas after the per-vertex appearance (bake_texture), which stays: the `v` lines keep
+    their colours, so a viewer without textures still shows them; the OBJ gains `vt` lines, an .mtl and a .png."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
     normals_mode = getattr(args, "normals", "grid")
     if normals_mode == "network" and getattr(args, "route", "kernel") == "script":
@@ -398,6 +400,12 @@ def export_marching_cubes(model, args, cfg, device):
             raise ValueError("--render-views has no --route script: the reference's script has no such step")
         if render_views < 0 or not 1 <= int(args.render_size) <= 16384:
             raise ValueError("--render-views must be >= 0 and --render-size in [1, 16384]")
+    texture_res = int(getattr(args, "texture_res", 0))
+    if texture_res:
+        if getattr(args, "route", "kernel") == "script":
+            raise ValueError("--texture-res has no --route script: the reference's script has no such step")
+        if not 1 <= texture_res <= hip_ops.TEXTURE_MAX_RES:
+            raise ValueError(f"--texture-res must be in [0, {hip_ops.TEXTURE_MAX_RES}], got {texture_res}")
     from . import dist as nd
     cache_path = os.path.join(args.save_dir, args.cache_name)
     cached = os.path.exists(cache_path)
@@ -449,7 +457,6 @@ def export_marching_cubes(model, args, cfg, device):
     if getattr(args, "precision", "f32") != "f32":     # the geometry above is fp32 by contract; only the colours may use the mode
         model.set_precision(args.precision)
     targets, directions = vertices[lo:hi], -normals[lo:hi]
-    diffuse = []
     # --batch-size bounds the reference's per-call memory (default 1024); on a 288 GB device the per-call overhead
     # of a 1024-ray launch sequence dominates, so at least 65 536 vertices go into one call
     chunk = max(int(args.batch_size), 65536)
@@ -458,32 +465,88 @@ def export_marching_cubes(model, args, cfg, device):
         if world > 1:
             raise ValueError("--route script is the unmodified script's single-process call sequence: run it on one rank")
         chunk = int(args.batch_size)                       # the script's calls as they are (mesh_nerf.py:172-191), D2H per batch
-    keep = (lambda t: t.cpu()) if script else (lambda t: t)
-    if args.no_view_dependence:
-        print("Diffuse map query directly  without specific-views...")
-        for pos, dirs in batchify(targets, directions, batch_size=chunk, device=device, progress=False):
-            diffuse.append(keep(model.sample_points(pos, dirs)[..., :3]))
-    else:
-        print("Diffuse map query with view dependence...")
-        ray_bounds = torch.tensor([0.0, args.view_disparity_max_bound], dtype=directions.dtype)
-        ray_origins = targets - args.view_disparity * directions
-        for o, d in batchify(ray_origins, directions, batch_size=chunk, device=device, progress=False):
-            diffuse.append(keep(model.query((o, d, ray_bounds)).rgb_map))
+    diffuse = query_appearance(model, args, targets, directions, device, chunk, to_host=script)
     diffuse = torch.cat(diffuse, dim=0) if diffuse else torch.empty(0, 3, dtype=torch.float32, device=device)
     diffuse = nd.all_gather_rows(diffuse.contiguous(), counts).cpu().numpy()
+    texture = bake_texture(model, vertices, triangles, normals, args, device, chunk) if texture_res else None
     if getattr(args, "precision", "f32") != "f32":
         model.set_precision("f32")
-    if rank == 0:
-        export_obj(vertices.cpu(), triangles.cpu(), diffuse, normals.cpu(), os.path.join(args.save_dir, args.mesh_name))
+    path = os.path.join(args.save_dir, args.mesh_name)
+    if rank == 0 and texture is None:
+        export_obj(vertices.cpu(), triangles.cpu(), diffuse, normals.cpu(), path)
+    elif rank == 0:
+        export_obj_textured(vertices.cpu(), triangles.cpu(), diffuse, normals.cpu(), texture[0], texture[1], path)
     if render_views:
-        render_report(model, vertices, triangles, diffuse, args, cfg, device)
+        render_report(model, vertices, triangles, diffuse, args, cfg, device, texture=texture)
     return vertices, triangles, normals, diffuse
 
 
-def render_report(model, vertices, triangles, diffuse, args, cfg, device):
+def query_appearance(model, args, targets, directions, device, chunk, to_host=False, announce=True):
+    """The colour the network gives each of `targets` (N,3) seen along `directions` (N,3), in calls of `chunk` points: the
+    colour branch at the point itself under --no-view-dependence, else a full render of the short ray that starts
+    --view-disparity in front of the point.  Vertices and texels both come through here.  -> the list of the calls' (n,3)
+    results (to_host: each copied to the host as soon as it is there, the script route's D2H per batch)."""
+    keep = (lambda t: t.cpu()) if to_host else (lambda t: t)
+    colours = []
+    if args.no_view_dependence:
+        if announce:
+            print("Diffuse map query directly  without specific-views...")
+        for pos, dirs in batchify(targets, directions, batch_size=chunk, device=device, progress=False):
+            colours.append(keep(model.sample_points(pos, dirs)[..., :3]))
+    else:
+        if announce:
+            print("Diffuse map query with view dependence...")
+        ray_bounds = torch.tensor([0.0, args.view_disparity_max_bound], dtype=directions.dtype)
+        ray_origins = targets - args.view_disparity * directions
+        for o, d in batchify(ray_origins, directions, batch_size=chunk, device=device, progress=False):
+            colours.append(keep(model.query((o, d, ray_bounds)).rgb_map))
+    return colours
+
+
+TEXTURE_WINDOW_SAMPLES = 1 << 22        # samples generated and queried at a time: 48 MB of positions, as much of directions
+
+
+def bake_texture(model, vertices, triangles, normals, args, device, chunk):
+    """`--texture-res N`: the atlas of per-face charts ("Texture atlas") baked from the network.  The surface
+    samples behind the texels are generated (hip_ops.mesh_texture_samples) and queried (query_appearance, the vertices' own
+    query) in windows of whole faces, so the positions of all samples are never resident at once; the (F*T, 3) colours stay on
+    the device.  Under torch.distributed every rank takes a contiguous face range and one all-gather assembles the colours;
+    every rank then fills the atlas redundantly.  -> (face_uv (F,3,2) f32, atlas (H,W,3) uint8), both on the device."""
+    from . import dist as nd
+    rank, world = nd.world()
+    n = int(args.texture_res)
+    faces = triangles.to(device=device, dtype=torch.int32).contiguous()
+    num_faces = int(faces.shape[0])
+    layout = hip_ops.mesh_texture_layout(num_faces, n)                # ValueError: no face, or an atlas wider than 16384
+    per_face = layout["samples_per_face"]
+    vertices, normals = vertices.to(device), normals.to(device=device, dtype=torch.float32)
+    ranges = [nd.split_range(num_faces, r, world) for r in range(world)]
+    lo, hi = ranges[rank]
+    step = max(1, TEXTURE_WINDOW_SAMPLES // per_face)
+    colours = torch.empty((hi - lo) * per_face, 3, dtype=torch.float32, device=device)
+    fallback = bad = 0
+    for first in range(lo, hi, step):
+        count = min(step, hi - first)
+        positions, directions, fb, bd = hip_ops.mesh_texture_samples(vertices, faces, normals, n, first, count, flip=SMOOTH_FLIP)
+        fallback, bad = fallback + fb, bad + bd
+        parts = query_appearance(model, args, positions, directions, device, chunk, announce=False)
+        colours[(first - lo) * per_face:(first - lo + count) * per_face] = torch.cat(parts, dim=0)
+    colours = nd.all_gather_rows(colours, [(b - a) * per_face for a, b in ranges])
+    tally = nd.all_gather_rows(torch.tensor([[fallback, bad]], dtype=torch.int64, device=device), [1] * world).sum(0).tolist()
+    atlas = hip_ops.mesh_texture_fill(colours, num_faces, n)
+    face_uv = hip_ops.mesh_texture_uv(num_faces, n, device=device)
+    print(f"Texture atlas: {layout['width']} x {layout['height']} texels ({layout['cols']} x {layout['rows']} cells of {n + 3} x "
+          f"{n + 2}) for {num_faces} faces at --texture-res {n}: {num_faces * per_face} samples, {int(tally[0])} with the face's "
+          f"own normal (no usable vertex normal), {int(tally[1])} on faces with a bad index")
+    return face_uv, atlas
+
+
+def render_report(model, vertices, triangles, diffuse, args, cfg, device, texture=None):
     """`--render-views N`: the exported mesh drawn from N orbit poses at --render-size (mesh_render.evaluate) against the
     network's own render of each pose -- PSNR, depth difference, silhouette IoU --, printed; rank 0 writes
-    <save-dir>/<mesh-name stem>.render.json.  Under torch.distributed the views are dealt out over the ranks."""
+    <save-dir>/<mesh-name stem>.render.json.  Under torch.distributed the views are dealt out over the ranks.  With
+    `--texture-res` the numbers describe the textured mesh, and the per-vertex colours' PSNR of the same views (one
+    rasterisation, one network render) stands beside them."""
     from . import dist as nd
     from . import mesh_render, synthetic
     if not (hasattr(model, "can_query_view") and model.can_query_view()):
@@ -494,7 +557,10 @@ def render_report(model, vertices, triangles, diffuse, args, cfg, device):
     background = (1.0,) * 3 if cfg.dataset.white_background else (0.0,) * 3
     report = mesh_render.evaluate(vertices, triangles.to(torch.int32), torch.as_tensor(diffuse), views, cfg.dataset.near / 4,
                                   background, model=model, bounds=bounds, chunksize=cfg.nerf.validation.chunksize,
-                                  compare_nerf=True, device=device)
+                                  compare_nerf=True, device=device, texture=texture, vertex_too=texture is not None)
+    if texture is not None:
+        report["mesh"] = dict(appearance="texture", atlas=dict(width=int(texture[1].shape[1]), height=int(texture[1].shape[0])),
+                              texture_res=int(args.texture_res))
     for line in mesh_render.format_report(report):
         print(line)
     if nd.world()[0] == 0:
@@ -576,6 +642,10 @@ def build_parser():
                         "against the network's own render of each pose: PSNR, depth difference, silhouette IoU; writes "
                         "<save-dir>/<mesh-name stem>.render.json (0 = off)")
     p.add_argument("--render-size", type=int, default=800, help="(addition) side in pixels of the --render-views images")
+    p.add_argument("--texture-res", type=_non_negative, default=0,
+                   help="(addition) bake a texture atlas from the network: every face gets a chart of this many lattice "
+                        "intervals per triangle side, (N+1)(N+2)/2 samples queried like the vertices; writes <stem>.obj with "
+                        "vt lines, <stem>.mtl and <stem>.png, and --render-views scores the textured mesh (0 = off)")
     p.add_argument("--gather", choices=("triangles", "grid"), default="triangles",
                    help="(addition, multi-GPU) what travels between the ranks: the emitted triangles of per-slab marching "
                         "cubes (default) or the density grid")

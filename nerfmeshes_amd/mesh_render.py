@@ -6,7 +6,8 @@
 
 A deterministic software rasteriser (hip_ops.mesh_rasterize: exact integer coverage, a 64-bit minimum per pixel; the rule is in
 include/nerfmeshes_hip.h) finds the face every pixel sees, hip_ops.mesh_interpolate blends the per-vertex colours of the OBJ
-that `mesh_nerf` wrote.  The pixel grid is get_ray_bundle's, so pixel (j, i) of the mesh image and of the network's render look
+that `mesh_nerf` wrote -- or, for an OBJ with a texture (`mesh_nerf --texture-res`, or any other: `--appearance`),
+hip_ops.mesh_texture_lookup fetches the image at the interpolated texture coordinates.  The pixel grid is get_ray_bundle's, so pixel (j, i) of the mesh image and of the network's render look
 along the same ray.  The rasteriser's depth is measured along the camera's axis; the network's depth_map along the unit ray:
 `ray_lengths` converts.  With a dataset the PSNR uses eval_nerf's bookkeeping (chunks of cfg.nerf.validation.chunksize, the
 float batch count), so it compares with the PSNR eval_nerf prints for the network.  `--compare-nerf` renders every pose with
@@ -34,17 +35,35 @@ def ray_lengths(height, width, focal, device):
     return torch.sqrt(i[None, :] ** 2 + j[:, None] ** 2 + 1.0).to(torch.float32)
 
 
-def render_mesh(verts, faces, colors, pose, height, width, focal, near, background, normals=None, cull_back=False):
+def device_texture(texture, device):
+    """(face_uv (F,3,2), image (Ht,Wt,3) uint8) -> both on the device, as hip_ops.mesh_texture_lookup takes them"""
+    face_uv, image = texture
+    return (torch.as_tensor(face_uv, dtype=torch.float32).to(device).contiguous(),
+            torch.as_tensor(image, dtype=torch.uint8).to(device).contiguous())
+
+
+def render_mesh(verts, faces, colors, pose, height, width, focal, near, background, normals=None, cull_back=False, texture=None,
+                vertex_too=False):
     """One view of a coloured mesh -> dict(rgb (H,W,3), depth (H,W): along the camera's axis, 0 where nothing was drawn,
     mask (H,W) bool, face_id (H,W) int32, counts: the rasteriser's; normals (H,W,3): interpolated, not normalised, zero in
     the background -- only when `normals` came).  verts (V,3), faces (F,3), colors (V,3) on the GPU (host arrays are copied);
-    background: three floats."""
+    background: three floats.  texture = (face_uv (F,3,2), image (Ht,Wt,3) uint8): rgb is the bilinear fetch of the image at
+    the interpolated coordinates (hip_ops.mesh_texture_lookup) instead of the blend of `colors`, which vertex_too adds as
+    rgb_vertex from the same rasterisation."""
     verts, faces, _, _ = hip_ops._mesh_arrays(verts, faces, "render_mesh")
     view = hip_ops.make_view(pose, height, width, focal)
     raster = hip_ops.mesh_rasterize(verts, faces, view, near, cull_back=cull_back)
     colors = torch.as_tensor(colors, dtype=torch.float32).to(verts.device)
-    out = dict(rgb=hip_ops.mesh_interpolate(raster, faces, colors, background), depth=raster[1], mask=raster[0] >= 0,
-               face_id=raster[0], counts=raster[3])
+    if texture is None:
+        rgb = hip_ops.mesh_interpolate(raster, faces, colors, background)
+    else:
+        face_uv, image = device_texture(texture, verts.device)
+        if face_uv.shape[0] != faces.shape[0]:
+            raise ValueError(f"render_mesh: texture coordinates of {face_uv.shape[0]} faces for a mesh of {faces.shape[0]}")
+        rgb = hip_ops.mesh_texture_lookup(raster, face_uv, image, background)
+    out = dict(rgb=rgb, depth=raster[1], mask=raster[0] >= 0, face_id=raster[0], counts=raster[3])
+    if texture is not None and vertex_too:
+        out["rgb_vertex"] = hip_ops.mesh_interpolate(raster, faces, colors, background)
     if normals is not None:
         out["normals"] = hip_ops.mesh_interpolate(raster, faces, torch.as_tensor(normals, dtype=torch.float32).to(verts.device),
                                                   (0.0, 0.0, 0.0))
@@ -89,33 +108,55 @@ def _imwrite(path, image):
     write(path, image)
 
 
+def read_image(path):
+    """an image file -> (H,W,3) uint8 on the host, row 0 on top"""
+    from PIL import Image
+    with Image.open(path) as im:
+        return torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8))
+
+
 def _to_u8(rgb):
     return (rgb.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
 
 
+VERTEX_ROW = ("psnr_target_vertex", "psnr_nerf_vertex")
+
+
 def evaluate(verts, faces, colors, views, near, background, model=None, bounds=None, chunksize=None, compare_nerf=False,
-             cull_back=False, save_dir=None, save_images=False, save_depth=False, device="cuda"):
+             cull_back=False, save_dir=None, save_images=False, save_depth=False, device="cuda", texture=None, vertex_too=False):
     """The report over an iterable of views `(pose, height, width, focal, targets | None)`: rank r draws views r, r + world,
-    ...; the rows are gathered, so every rank returns the single-rank report.  targets: (H*W, 3) on any device."""
+    ...; the rows are gathered, so every rank returns the single-rank report.  targets: (H*W, 3) on any device.
+    texture = (face_uv, image): the mesh is drawn with it (render_mesh) and every number describes the textured mesh;
+    vertex_too then adds VERTEX_ROW -- the PSNR of the per-vertex colours from the same rasterisation against the same target and
+    the same network render -- to every view and to the means."""
     from . import dist as nd
     rank, world = nd.world()
     verts, faces, _, _ = hip_ops._mesh_arrays(verts, faces, "mesh_render")
     colors = torch.as_tensor(colors, dtype=torch.float32).to(verts.device)
+    if texture is not None:
+        texture = device_texture(texture, verts.device)
+    vertex_too = bool(vertex_too and texture is not None)
+    columns = ROW + (VERTEX_ROW if vertex_too else ())
     rows, total = [], 0
     for nr, (pose, height, width, focal, targets) in enumerate(views):
         total += 1
         if nr % world != rank:
             continue
-        out = render_mesh(verts, faces, colors, pose, height, width, focal, near, background, cull_back=cull_back)
+        out = render_mesh(verts, faces, colors, pose, height, width, focal, near, background, cull_back=cull_back, texture=texture,
+                          vertex_too=vertex_too)
         chunk = chunksize or height * width
-        row = dict.fromkeys(ROW, NAN)
+        row = dict.fromkeys(columns, NAN)
         row.update({k: float(v) for k, v in out["counts"].items()})
         if targets is not None:
             row["psnr_target"] = psnr(chunked_mse(out["rgb"].reshape(-1, 3), targets.to(verts.device).reshape(-1, 3), chunk))
         if compare_nerf:
-            row["psnr_nerf"], row["depth_mean"], row["depth_median"], row["depth_pixels"], row["iou"], _, _ = compare_with_nerf(
+            row["psnr_nerf"], row["depth_mean"], row["depth_median"], row["depth_pixels"], row["iou"], net_rgb, _ = compare_with_nerf(
                 model, out, pose, height, width, focal, bounds, chunk)
-        rows.append([row[k] for k in ROW])
+            if vertex_too:
+                row["psnr_nerf_vertex"] = psnr(torch.nn.functional.mse_loss(out["rgb_vertex"].reshape(-1, 3), net_rgb))
+        if vertex_too and targets is not None:
+            row["psnr_target_vertex"] = psnr(chunked_mse(out["rgb_vertex"].reshape(-1, 3), targets.to(verts.device).reshape(-1, 3), chunk))
+        rows.append([row[k] for k in columns])
         if save_dir and save_images:
             os.makedirs(os.path.join(save_dir, "mesh_images"), exist_ok=True)
             _imwrite(os.path.join(save_dir, "mesh_images", f"{nr:04d}.png"), _to_u8(out["rgb"]))
@@ -124,24 +165,24 @@ def evaluate(verts, faces, colors, views, near, background, model=None, bounds=N
             far = out["depth"].max().clamp_min(1e-12)
             shade = torch.where(out["mask"], 1.0 - out["depth"] / far, torch.zeros_like(out["depth"]))
             _imwrite(os.path.join(save_dir, "mesh_depth", f"{nr:04d}.png"), _to_u8(shade))
-    mine = torch.tensor(rows, dtype=torch.float64, device=verts.device).reshape(-1, len(ROW))
+    mine = torch.tensor(rows, dtype=torch.float64, device=verts.device).reshape(-1, len(columns))
     if world > 1:
         counts = nd.round_robin_counts(total, world)
         flat = nd.all_gather_rows(mine, counts)
         starts = [sum(counts[:r]) for r in range(world)]
         mine = torch.stack([flat[starts[i % world] + i // world] for i in range(total)]) if total else flat
-    return build_report(mine.cpu().numpy(), near)
+    return build_report(mine.cpu().numpy(), near, columns)
 
 
-def build_report(table, near):
-    """per-view rows (views, len(ROW)) fp64 -> the report: per-view dicts, means over the views that have the number, the
+def build_report(table, near, columns=ROW):
+    """per-view rows (views, len(columns)) fp64 -> the report: per-view dicts, means over the views that have the number, the
     reject counts summed"""
     integer = set(hip_ops.RASTER_COUNTS) | {"depth_pixels"}
     views = []
     for r in table:
-        views.append({k: (int(v) if k in integer and not np.isnan(v) else (None if np.isnan(v) else float(v))) for k, v in zip(ROW, r)})
+        views.append({k: (int(v) if k in integer and not np.isnan(v) else (None if np.isnan(v) else float(v))) for k, v in zip(columns, r)})
     mean = {}
-    for k in ("psnr_target", "psnr_nerf", "depth_mean", "depth_median", "iou"):
+    for k in ("psnr_target", "psnr_nerf", "depth_mean", "depth_median", "iou") + tuple(k for k in VERTEX_ROW if k in columns):
         have = [v[k] for v in views if v[k] is not None]
         mean[k] = float(np.mean(have)) if have else None
     mse = [10.0 ** (-v["psnr_target"] / 10.0) for v in views if v["psnr_target"] is not None]
@@ -162,6 +203,8 @@ def format_report(report):
                          f"{v['depth_mean'] if v['depth_mean'] is not None else NAN:.6f} median "
                          f"{v['depth_median'] if v['depth_median'] is not None else NAN:.6f} over {v['depth_pixels']} px, "
                          f"IoU {v['iou']:.4f}")
+        if v.get("psnr_nerf_vertex") is not None:
+            parts.append(f"per-vertex colours: PSNR to the network {v['psnr_nerf_vertex']:.4f}")
         lines.append(", ".join(parts))
     mean = ", ".join(f"{k} {v:.6f}" for k, v in report["mean"].items() if v is not None)
     lines.append(f"Mesh render: {len(report['views'])} views" + (f", mean {mean}" if mean else ""))
@@ -228,6 +271,9 @@ def build_parser():
                    help="render every pose with the network too: PSNR, depth difference and IoU of the mesh against it")
     p.add_argument("--near", type=float, default=None, help="default: cfg.dataset.near / 4, 0.05 without a config")
     p.add_argument("--cull", choices=("none", "back"), default="none")
+    p.add_argument("--appearance", choices=("auto", "vertex", "texture"), default="auto",
+                   help="what colours the mesh: the OBJ's texture (its vt lines and the map_Kd image of its mtllib), its "
+                        "per-vertex colours, or auto: the texture when the OBJ has one")
     p.add_argument("--save-dir", type=str, default=".")
     p.add_argument("--save-images", action="store_true", default=False)
     p.add_argument("--save-depth", action="store_true", default=False)
@@ -244,12 +290,18 @@ def main(argv=None):
     if not args.log_checkpoint and args.views <= 0:
         raise SystemExit("without --log-checkpoint there is no dataset: give --views N")
     from . import dist as nd
-    from .nerf.nerf_helpers import load_obj_attributes
+    from .nerf.nerf_helpers import load_obj_textured
     rank, world, device = nd.init_from_env()
     try:
-        verts, faces, colors, _ = load_obj_attributes(args.mesh)
+        verts, faces, colors, _, face_uv, image_path = load_obj_textured(args.mesh)
         if colors is None:
             colors = torch.full_like(verts, 0.7)
+        if args.appearance == "texture" and face_uv is None:
+            raise SystemExit(f"--appearance texture: {args.mesh} has no texture (vt indices on every face corner and an mtllib "
+                             "with a readable map_Kd image beside it)")
+        texture = None
+        if face_uv is not None and args.appearance != "vertex":
+            texture = (face_uv, read_image(image_path))
         cfg = model = bounds = chunksize = None
         if args.log_checkpoint:
             pp = PathParser()
@@ -270,8 +322,12 @@ def main(argv=None):
         with torch.no_grad():
             report = evaluate(verts, faces, colors, views, near, (1.0,) * 3 if white else (0.0,) * 3, model=model, bounds=bounds,
                               chunksize=chunksize, compare_nerf=args.compare_nerf, cull_back=args.cull == "back",
-                              save_dir=args.save_dir, save_images=args.save_images, save_depth=args.save_depth, device=device)
-        report["mesh"] = dict(path=args.mesh, vertices=int(verts.shape[0]), faces=int(faces.shape[0]))
+                              save_dir=args.save_dir, save_images=args.save_images, save_depth=args.save_depth, device=device,
+                              texture=texture)
+        report["mesh"] = dict(path=args.mesh, vertices=int(verts.shape[0]), faces=int(faces.shape[0]),
+                              appearance="vertex" if texture is None else "texture")
+        if texture is not None:
+            report["mesh"]["atlas"] = dict(path=image_path, width=int(texture[1].shape[1]), height=int(texture[1].shape[0]))
         for line in format_report(report):
             print(line)
         if args.out and rank == 0:

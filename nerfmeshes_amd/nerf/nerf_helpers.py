@@ -213,3 +213,100 @@ def load_obj_attributes(path):
     as_rows = lambda rows: torch.from_numpy(np.asarray(rows, dtype=np.float64).astype(np.float32).reshape(-1, 3))  # noqa: E731
     return (verts, faces, as_rows(colors) if count and len(colors) == count else None,
             as_rows(normals) if count and len(normals) == count else None)
+
+
+MATERIAL_NAME = "material_0"
+
+
+def write_mtl(path, image_name, material=MATERIAL_NAME):
+    """the one-material library of a textured OBJ: white diffuse, the image as its diffuse map"""
+    with open(path, "w") as fh:
+        fh.write(f"newmtl {material}\nKa 0 0 0\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {image_name}\n")
+
+
+def export_obj_textured(vertices, triangles, diffuse, normals, face_uv, atlas, filename):
+    """`export_obj` with a texture (addition; nm_export_obj_textured): <stem>.obj with `mtllib <stem>.mtl`, the same `v x y z
+    [r g b]` and `vn` lines, 3F `vt u v` lines from face_uv (F,3,2), `usemtl` and `f a/t/a b/t/b c/t/c`; <stem>.mtl naming
+    <stem>.png; <stem>.png: the atlas (H,W,3) uint8, row 0 on top."""
+    import ctypes as C
+    from .. import _lib
+    from ..eval_nerf import _imwrite
+
+    def host(x, dtype, width=3):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        return np.ascontiguousarray(np.asarray(x), dtype=dtype).reshape(-1, width)
+
+    v, c, n, t = host(vertices, np.float32), host(diffuse, np.float32), host(normals, np.float32), host(triangles, np.int32)
+    uv = host(face_uv, np.float32, 2)
+    if len(uv) != 3 * len(t):
+        raise ValueError(f"export_obj_textured: {len(uv)} texture coordinates for {len(t)} faces")
+    image = atlas.detach().cpu().numpy() if isinstance(atlas, torch.Tensor) else np.asarray(atlas)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError(f"export_obj_textured: the atlas must be (H,W,3) uint8, got {image.shape} {image.dtype}")
+    stem = os.path.splitext(filename)[0]
+    name = os.path.basename(stem)
+    print("Writing to obj...")
+    ptr = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+    lib = _lib.load()
+    rc = lib.nm_export_obj_textured(ptr(v), len(v), ptr(c), len(c), ptr(n), len(n), ptr(t), len(t), ptr(uv),
+                                    os.fsencode(name + ".mtl"), MATERIAL_NAME.encode(), os.fsencode(filename))
+    if rc == 2:
+        raise ValueError((lib.nm_last_error() or b"nm_export_obj_textured: bad argument").decode())
+    _lib.check(rc, "nm_export_obj_textured")
+    write_mtl(stem + ".mtl", name + ".png")
+    _imwrite(stem + ".png", np.ascontiguousarray(image))
+    print(f"Finished writing to {filename} with {len(v)} vertices")
+
+
+def _read_map_kd(obj_path, library):
+    """the first `map_Kd` image of the material library named beside the OBJ, as a path, or None"""
+    mtl = os.path.join(os.path.dirname(obj_path), library)
+    try:
+        with open(mtl, "r", errors="replace") as fh:
+            for line in fh:
+                parts = line.split()
+                if parts and parts[0] == "map_Kd" and len(parts) >= 2:
+                    image = os.path.join(os.path.dirname(mtl), parts[-1])
+                    return image if os.path.isfile(image) and os.access(image, os.R_OK) else None
+    except OSError:
+        return None
+    return None
+
+
+def load_obj_textured(path):
+    """`load_obj_attributes` plus the texture -> (verts, faces, colors, normals, face_uv, image_path): face_uv (F,3,2) f32 from
+    the `vt` lines through the `f a/t/n` entries (fan triangulation carries the vt indices along; negative ones count back),
+    image_path: the `map_Kd` file of the `mtllib` beside the OBJ.  The last two are None unless EVERY face corner has a vt
+    index in range and the library and its image can be read; the first four are load_obj_attributes' own."""
+    verts, faces, colors, normals = load_obj_attributes(path)
+    coords, corners, library, complete = [], [], None, True
+    with open(path, "r", errors="replace") as fh:
+        for line in fh:
+            if line.startswith(("vt ", "vt\t")):
+                parts = line.split()
+                try:
+                    coords.append((float(parts[1]), float(parts[2])))
+                except (IndexError, ValueError):
+                    coords.append((float("nan"), float("nan")))
+                    complete = False
+            elif line.startswith(("f ", "f\t")):
+                entry_uv = []
+                for entry in line.split()[1:]:
+                    fields = entry.split("/")
+                    try:
+                        t = int(fields[1]) if len(fields) >= 2 and fields[1] else 0
+                    except ValueError:
+                        t = 0
+                    entry_uv.append(t - 1 if t > 0 else (len(coords) + t if t < 0 else -1))
+                for k in range(1, len(entry_uv) - 1):
+                    corners.append((entry_uv[0], entry_uv[k], entry_uv[k + 1]))
+            elif line.startswith(("mtllib ", "mtllib\t")) and library is None:
+                library = line.split(None, 1)[1].strip()
+    index = np.asarray(corners, dtype=np.int64).reshape(-1, 3)
+    image = _read_map_kd(path, library) if library else None
+    if (not complete or image is None or len(index) != faces.shape[0] or not len(index) or not len(coords)
+            or index.min() < 0 or index.max() >= len(coords)):
+        return verts, faces, colors, normals, None, None
+    table = np.asarray(coords, dtype=np.float64).astype(np.float32).reshape(-1, 2)
+    return verts, faces, colors, normals, torch.from_numpy(np.ascontiguousarray(table[index])), image

@@ -1,0 +1,360 @@
+"""GPU: the texture atlas (nm_mesh_texture_samples / _fill / _uv / _lookup, mesh_nerf --texture-res, mesh_render
+--appearance).  Every index is a formula and every fp32 operation is rounded on its own, so every comparison with the numpy
+restatement (tests/mesh_texture.py) is exact -- dtype, shape and bytes: single faces, full and half-empty cells, a ragged last
+row, the sheet, the sphere, a mesh of bad indices and vertices, zero and NaN normals and none at all, windows of faces, run
+after run; the fetch on the baked atlases and on arbitrary coordinates and images; then the exporter and mesh_render end to
+end, 2 ranks against 1."""
+import contextlib
+import io
+import json
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from nerfmeshes_amd import synthetic as S
+from tests import mesh_metrics as MM
+from tests import mesh_texture as MT
+from tests.test_mesh_raster import SPHERE_VIEWS, reject_mesh, sheet
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F32 = np.float32
+
+
+@pytest.fixture(scope="module")
+def ops():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a MI355X")
+    from nerfmeshes_amd import hip_ops
+    return hip_ops
+
+
+def _dev(a, dtype=None):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _same(got, want, tag):
+    assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), f"{tag} differ"
+
+
+def _normals(verts, seed):
+    """unit-ish normals with zero rows, NaN rows and an infinite one: the fallback and its count"""
+    rng = np.random.default_rng(seed)
+    normals = rng.standard_normal((len(verts), 3)).astype(F32)
+    if len(verts) >= 4:
+        normals[rng.choice(len(verts), max(1, len(verts) // 6), replace=False)] = 0
+        normals[rng.choice(len(verts), max(1, len(verts) // 8), replace=False), rng.integers(0, 3)] = np.nan
+        normals[rng.integers(0, len(verts)), 0] = np.inf
+    return normals
+
+
+def _colours(rows, seed):
+    """colours below 0, above 1, NaN and infinite among the ordinary ones: the quantiser's edges"""
+    rng = np.random.default_rng(seed)
+    colours = rng.uniform(-0.1, 1.1, (rows, 3)).astype(F32)
+    colours[rng.integers(0, rows, max(1, rows // 50))] = [np.nan, np.inf, -np.inf]
+    colours[rng.integers(0, rows, max(1, rows // 50))] = rng.integers(0, 256, 3).astype(F32) / F32(255)
+    return colours
+
+
+def meshes():
+    tri = np.array([[-0.8, -0.7, 0.1], [0.9, -0.5, -0.2], [0.1, 0.85, 0.3]], F32)
+    quad = np.array([[-1, -1, 0], [1, -1, 0.5], [1, 1, 0], [-1, 1, -0.5]], F32)
+    sv, sf, _ = sheet()
+    rv, rf, _ = reject_mesh()
+    return {"one_triangle": (tri, np.array([[0, 1, 2]], np.int32)),
+            "two_faces": (quad, np.array([[0, 1, 2], [0, 2, 3]], np.int32)),
+            "three_faces": (quad, np.array([[0, 1, 2], [0, 2, 3], [3, 1, 0]], np.int32)),
+            "five_faces": (sv, sf[:5]),
+            "sheet": (sv, sf),
+            "sphere": MM.uv_sphere(64, 32),
+            "reject_mesh": (rv, rf)}
+
+
+MESHES = meshes()
+
+
+def _check_bake(ops, verts, faces, normals, n, tag, flip=1):
+    """samples, fill and uv of one mesh against the restatement -> the restated (positions, directions, fallback, bad)"""
+    dv, df = _dev(verts), _dev(faces)
+    dn = _dev(normals) if normals is not None else None
+    want = MT.samples(verts, faces, normals, n, flip=flip)
+    got = ops.mesh_texture_samples(dv, df, dn, n, flip=flip)
+    _same(_np(got[0]), want[0], f"{tag}: positions")
+    _same(_np(got[1]), want[1], f"{tag}: directions")
+    assert got[2:] == want[2:], f"{tag}: fallback / bad counts {got[2:]} != {want[2:]}"
+    colours = _colours(len(want[0]), len(faces) * 1000 + n)
+    _same(_np(ops.mesh_texture_fill(_dev(colours), len(faces), n)), MT.fill(colours, len(faces), n), f"{tag}: atlas")
+    _same(_np(ops.mesh_texture_uv(len(faces), n)), MT.face_uv(len(faces), n), f"{tag}: uv")
+    return want
+
+
+@pytest.mark.parametrize("n", [1, 2, 5, 8])
+@pytest.mark.parametrize("name", list(MESHES))
+def test_samples_fill_and_uv_are_the_restatement(ops, name, n):
+    verts, faces = MESHES[name]
+    with_normals = _check_bake(ops, verts, faces, _normals(verts, n), n, f"{name} n={n} normals", flip=-1)
+    without = _check_bake(ops, verts, faces, None, n, f"{name} n={n} no normals")
+    per_face = (n + 1) * (n + 2) // 2
+    good = ((faces >= 0) & (faces < len(verts))).all(1).sum()
+    assert without[2] == good * per_face and without[3] == (len(faces) - good) * per_face
+    if name in ("sheet", "sphere"):
+        assert 0 < with_normals[2] < good * per_face, "some samples fall back, some do not"
+    if name == "reject_mesh":
+        assert without[3] == 2 * per_face and np.isnan(without[0]).any(), "bad indices are counted, NaN vertices come through"
+    if name == "five_faces":
+        lay = MT.layout(5, n)
+        assert lay["cols"] * lay["rows"] > 3, "three cells in a grid of more: the last row is ragged and its last cell half empty"
+
+
+def test_the_finest_lattice_on_two_faces(ops):
+    verts, faces = MESHES["two_faces"]
+    want = _check_bake(ops, verts, faces, _normals(verts, 255), 255, "n=255")
+    assert len(want[0]) == 2 * 32896 and MT.layout(2, 255)["width"] == 258
+
+
+def test_windows_concatenate_to_the_whole_run_after_run(ops):
+    verts, faces = MESHES["sphere"]
+    normals, n = _normals(verts, 3), 5
+    dv, df, dn = _dev(verts), _dev(faces), _dev(normals)
+    whole = ops.mesh_texture_samples(dv, df, dn, n, flip=-1)
+    again = ops.mesh_texture_samples(dv, df, dn, n, 0, len(faces), flip=-1)
+    assert _np(whole[0]).tobytes() == _np(again[0]).tobytes() and _np(whole[1]).tobytes() == _np(again[1]).tobytes() and whole[2:] == again[2:]
+    nf = len(faces)
+    for windows in (((0, 1), (1, nf - 1)), ((0, nf - 1), (nf - 1, 1)), ((0, 700), (700, 0), (700, 2001), (2701, nf - 2701))):
+        parts = [ops.mesh_texture_samples(dv, df, dn, n, first, count, flip=-1) for first, count in windows]
+        for (first, count), part in zip(windows, parts):
+            want = MT.samples(verts, faces, normals, n, first, count, flip=-1)
+            _same(_np(part[0]), want[0], f"window {first}+{count}: positions")
+            _same(_np(part[1]), want[1], f"window {first}+{count}: directions")
+            assert part[2:] == want[2:]
+        assert torch.equal(torch.cat([p[0] for p in parts]).view(torch.int32), whole[0].view(torch.int32))
+        assert torch.equal(torch.cat([p[1] for p in parts]).view(torch.int32), whole[1].view(torch.int32))
+        assert sum(p[2] for p in parts) == whole[2] and sum(p[3] for p in parts) == whole[3]
+    empty = ops.mesh_texture_samples(dv, df, dn, n, nf, 0)
+    assert empty[0].shape == (0, 3) and empty[2:] == (0, 0)
+    with pytest.raises(ValueError):
+        ops.mesh_texture_samples(dv, df, dn, n, 1, nf)
+    colours = _dev(_colours(len(faces) * 21, 9))
+    atlases = [ops.mesh_texture_fill(colours, len(faces), n) for _ in range(3)]
+    assert torch.equal(atlases[0], atlases[1]) and torch.equal(atlases[0], atlases[2])
+
+
+def _baked(verts, faces, n, seed):
+    """a restated atlas of random colours (nothing smooth: every texel matters) and its coordinates"""
+    rng = np.random.default_rng(seed)
+    colours = rng.random((len(faces) * (n + 1) * (n + 2) // 2, 3), dtype=F32)
+    return MT.face_uv(len(faces), n), MT.fill(colours, len(faces), n)
+
+
+BACKGROUND = (0.25, 0.5, 0.75)
+
+
+def test_lookup_on_the_baked_atlases(ops):
+    verts, faces = MESHES["sphere"]
+    dv, df = _dev(verts), _dev(faces)
+    uv, atlas = _baked(verts, faces, 4, 1)
+    for angles, height, width, focal in SPHERE_VIEWS:
+        raster = ops.mesh_rasterize(dv, df, ops.make_view(S.pose_spherical(*angles), height, width, focal), 0.1)
+        got = ops.mesh_texture_lookup(raster, _dev(uv), _dev(atlas), BACKGROUND)
+        _same(_np(got), MT.lookup(_np(raster[0]), _np(raster[2]), uv, atlas, BACKGROUND), f"sphere {angles}")
+        assert raster[3]["covered"] > 500 and (_np(got)[_np(raster[0]) < 0] == np.array(BACKGROUND, F32)).all()
+    verts, faces, pose = sheet()
+    for n in (1, 8):
+        uv, atlas = _baked(verts, faces, n, n)
+        raster = ops.mesh_rasterize(_dev(verts), _dev(faces), ops.make_view(pose, 48, 48, 60.0), 0.1)
+        got = ops.mesh_texture_lookup(raster, _dev(uv), _dev(atlas), BACKGROUND)
+        _same(_np(got), MT.lookup(_np(raster[0]), _np(raster[2]), uv, atlas, BACKGROUND), f"sheet n={n}")
+        assert raster[3]["covered"] == 1600
+
+
+@pytest.mark.parametrize("th, tw", [(1, 1), (2, 3), (64, 64)])
+def test_lookup_on_arbitrary_coordinates_and_images(ops, th, tw):
+    rng = np.random.default_rng(th * 100 + tw)
+    texture = rng.integers(0, 256, (th, tw, 3)).astype(np.uint8)
+    num_faces = 40
+    uv = rng.uniform(-0.5, 1.5, (num_faces, 3, 2)).astype(F32)
+    # faces whose corners sit exactly on texel centres and on texel borders
+    centres = (rng.integers(0, tw, (8, 3)) + 0.5) / tw, 1.0 - (rng.integers(0, th, (8, 3)) + 0.5) / th
+    borders = rng.integers(0, tw + 1, (8, 3)) / tw, 1.0 - rng.integers(0, th + 1, (8, 3)) / th
+    uv[:8] = np.stack(centres, -1).astype(F32)
+    uv[8:16] = np.stack(borders, -1).astype(F32)
+    uv[16, 1, 0], uv[17, 0, 1], uv[18, 2, 0], uv[19, 1, 1] = np.nan, np.inf, -np.inf, np.nan
+    uv[20] = [[3e38, 3e38], [-3e38, 3e38], [3e38, -3e38]]            # finite, but u Wt overflows: clamped, not background
+    pixels = 4096
+    face_id = rng.integers(0, num_faces, pixels).astype(np.int32)
+    face_id[rng.choice(pixels, 200, replace=False)] = rng.choice([-1, num_faces, num_faces + 7, -2 ** 31, 2 ** 31 - 1], 200)
+    bary = rng.dirichlet((1, 1, 1), pixels).astype(F32)
+    corner = rng.choice(pixels, 600, replace=False)
+    bary[corner] = np.eye(3, dtype=F32)[rng.integers(0, 3, 600)]     # exactly a corner: exactly a centre or a border
+    face_id, bary = face_id.reshape(64, 64), bary.reshape(64, 64, 3)
+    got = ops.mesh_texture_lookup((_dev(face_id), None, _dev(bary)), _dev(uv), _dev(texture), BACKGROUND)
+    want = MT.lookup(face_id, bary, uv, texture, BACKGROUND)
+    _same(_np(got), want, f"texture {th}x{tw}")
+    outside = (face_id < 0) | (face_id >= num_faces)
+    assert (want[outside] == np.array(BACKGROUND, F32)).all() and (want[face_id == 16] == np.array(BACKGROUND, F32)).any()
+    again = ops.mesh_texture_lookup((_dev(face_id), None, _dev(bary)), _dev(uv), _dev(texture), BACKGROUND)
+    assert torch.equal(got.view(torch.int32), again.view(torch.int32))
+
+
+def test_render_mesh_draws_the_texture_and_keeps_the_vertex_path(ops):
+    from nerfmeshes_amd import mesh_render
+    verts, faces, pose = sheet()
+    uv, atlas = _baked(verts, faces, 4, 11)
+    colors = np.random.default_rng(5).random((len(verts), 3), dtype=F32)
+    plain = mesh_render.render_mesh(verts, faces, colors, pose, 48, 48, 60.0, 0.1, BACKGROUND)
+    both = mesh_render.render_mesh(verts, faces, colors, pose, 48, 48, 60.0, 0.1, BACKGROUND, texture=(uv, atlas), vertex_too=True)
+    assert _np(both["rgb_vertex"]).tobytes() == _np(plain["rgb"]).tobytes() and "rgb_vertex" not in plain
+    _same(_np(both["rgb"]), MT.lookup(_np(both["face_id"]), _np(ops.mesh_rasterize(
+        _dev(verts), _dev(faces), ops.make_view(pose, 48, 48, 60.0), 0.1)[2]), uv, atlas, BACKGROUND), "render_mesh with a texture")
+    with pytest.raises(ValueError):
+        mesh_render.render_mesh(verts, faces, colors, pose, 48, 48, 60.0, 0.1, BACKGROUND, texture=(uv[:5], atlas))
+
+
+@pytest.fixture(scope="module")
+def scene():
+    from nerfmeshes_amd import models
+    hp = S.hparams(chunksize=3000)
+    torch.manual_seed(0)
+    model = models.NeRFModel(hp)
+    sd = model.state_dict()
+    for prefix in ("model_coarse.", "model_fine."):
+        for k, v in S.make_scene_weights().items():
+            sd[prefix + k] = torch.from_numpy(v)
+    model.load_state_dict(sd)
+    return model.eval().to("cuda")
+
+
+COMMON = ["--view-disparity-max-bound", "1.0", "--batch-size", "4096", "--res", "48", "--iso-level", "32", "--limit", "1.2",
+          "--simplify-cell", "2"]
+SIZE = 80
+
+
+def _run(model, tmp, tag, *extra):
+    from nerfmeshes_amd import mesh_nerf
+    d = tmp / tag
+    d.mkdir(exist_ok=True)
+    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), *COMMON, *extra])
+    text = io.StringIO()
+    with torch.no_grad(), contextlib.redirect_stdout(text):
+        out = mesh_nerf.export_marching_cubes(model, args, model.cfg, "cuda")
+    return out, d, text.getvalue()
+
+
+@pytest.fixture(scope="module")
+def exported(scene, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("texture")
+    views = ["--render-views", "2", "--render-size", str(SIZE)]
+    return {"plain": _run(scene, tmp, "plain", *views), "zero": _run(scene, tmp, "zero", "--texture-res", "0", *views),
+            "texture": _run(scene, tmp, "texture", "--texture-res", "4", *views)}
+
+
+def test_the_exporter_writes_a_textured_obj_and_scores_it(ops, scene, exported):
+    from nerfmeshes_amd.nerf.nerf_helpers import load_obj_textured
+    (v, f, n, c), d, text = exported["texture"]
+    for name in ("mesh.obj", "mesh.mtl", "mesh.png", "mesh.render.json"):
+        assert os.path.getsize(d / name) > 0, name
+    rv, rf, rc, rn, uv, image = load_obj_textured(str(d / "mesh.obj"))
+    assert rv.numpy().tobytes() == _np(v).tobytes() and rf.numpy().tobytes() == _np(f.to(torch.int32)).tobytes()
+    assert rc.numpy().tobytes() == np.asarray(c, F32).tobytes() and image == str(d / "mesh.png")
+    num_faces = int(f.shape[0])
+    _same(uv.numpy(), MT.face_uv(num_faces, 4), "the OBJ's vt lines")
+    from nerfmeshes_amd import mesh_render
+    atlas = mesh_render.read_image(image).numpy()
+    lay = MT.layout(num_faces, 4)
+    assert atlas.shape == (lay["height"], lay["width"], 3) and f"Texture atlas: {lay['width']} x {lay['height']} texels" in text
+    assert f"{num_faces * 15} samples" in text
+    # the image is the fill of the network's colours at the samples, queried as the vertices are
+    from nerfmeshes_amd import mesh_nerf
+    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), *COMMON, "--texture-res", "4"])
+    positions, directions, fallback, bad = ops.mesh_texture_samples(v, f.to(torch.int32), n, 4, flip=mesh_nerf.SMOOTH_FLIP)
+    assert bad == 0 and f"{fallback} with the face's own normal" in text
+    with torch.no_grad():
+        colours = torch.cat(mesh_nerf.query_appearance(scene, args, positions, directions, "cuda", 65536, announce=False))
+    assert _np(ops.mesh_texture_fill(colours, num_faces, 4)).tobytes() == atlas.tobytes(), "the PNG is the baked atlas"
+    assert atlas.std() > 1, "an image, not a constant"
+    report = json.load(open(d / "mesh.render.json"))
+    assert report["mesh"] == dict(appearance="texture", atlas=dict(width=lay["width"], height=lay["height"]), texture_res=4)
+    for row in report["views"]:
+        print(f"PSNR to the network: textured {row['psnr_nerf']:.4f}, per vertex {row['psnr_nerf_vertex']:.4f}")
+        assert set(row) == set(mesh_render.ROW) | set(mesh_render.VERTEX_ROW) and row["covered"] > 300
+    assert report["mean"]["psnr_nerf"] >= report["mean"]["psnr_nerf_vertex"], "the texture does not lose to the vertex colours"
+    # the per-vertex numbers beside it are the plain run's own
+    plain = json.load(open(exported["plain"][1] / "mesh.render.json"))
+    assert [r["psnr_nerf_vertex"] for r in report["views"]] == [r["psnr_nerf"] for r in plain["views"]]
+    assert "mesh" not in plain and set(plain["views"][0]) == set(mesh_render.ROW)
+
+
+def test_texture_res_0_changes_nothing(exported):
+    (_, _, _, _), plain_dir, plain_text = exported["plain"]
+    (_, _, _, _), zero_dir, zero_text = exported["zero"]
+    assert open(zero_dir / "mesh.obj", "rb").read() == open(plain_dir / "mesh.obj", "rb").read()
+    assert open(zero_dir / "mesh.render.json", "rb").read() == open(plain_dir / "mesh.render.json", "rb").read()
+    assert zero_text.replace(str(zero_dir), "") == plain_text.replace(str(plain_dir), "") and "Texture" not in zero_text
+    assert sorted(os.listdir(zero_dir)) == sorted(os.listdir(plain_dir)) == ["mesh.obj", "mesh.render.json"]
+    textured = open(exported["texture"][1] / "mesh.obj").read().split("\n")
+    base = open(plain_dir / "mesh.obj").read().split("\n")
+    assert [l for l in textured if l.startswith(("v ", "vn "))] == [l for l in base if l.startswith(("v ", "vn "))]
+
+
+def test_mesh_render_on_the_written_files_reproduces_the_report(ops, scene, exported, tmp_path, monkeypatch):
+    """mesh_render.main on the three files, the checkpoint loading replaced by the scene in memory: the same uint8 atlas
+    through the same coordinates -> the report's textured numbers exactly; --appearance vertex -> the per-vertex ones"""
+    from nerfmeshes_amd import mesh_render, models
+    _, d, _ = exported["texture"]
+    want = json.load(open(d / "mesh.render.json"))
+
+    class Parser:
+        checkpoint_path = "memory"
+
+        def parse(self, *a):
+            return scene.cfg, None
+
+    monkeypatch.setattr(mesh_render, "PathParser", Parser)
+    monkeypatch.setattr(getattr(models, scene.cfg.experiment.model), "load_from_checkpoint", classmethod(lambda cls, path: scene))
+    common = ["--mesh", str(d / "mesh.obj"), "--log-checkpoint", "memory", "--views", "2", "--img-size", str(SIZE), "--compare-nerf"]
+    got = mesh_render.main(common + ["--out", str(tmp_path / "auto.json")])
+    saved = json.load(open(tmp_path / "auto.json"))
+    assert saved["mesh"]["appearance"] == "texture" and saved["mesh"]["atlas"]["width"] == want["mesh"]["atlas"]["width"]
+    assert saved["views"] == [{k: row[k] for k in mesh_render.ROW} for row in want["views"]], "the textured numbers, exactly"
+    assert saved["mean"] == {k: v for k, v in want["mean"].items() if k not in mesh_render.VERTEX_ROW} and got["counts"] == want["counts"]
+    assert mesh_render.main(common + ["--appearance", "texture"])["views"] == json.loads(json.dumps(got["views"]))
+    vertex = mesh_render.main(common + ["--appearance", "vertex"])
+    assert vertex["mesh"]["appearance"] == "vertex" and "atlas" not in vertex["mesh"]
+    assert [r["psnr_nerf"] for r in vertex["views"]] == [r["psnr_nerf_vertex"] for r in want["views"]]
+    with pytest.raises(SystemExit, match="has no texture"):
+        mesh_render.main(["--mesh", str(exported["plain"][1] / "mesh.obj"), "--views", "1", "--appearance", "texture"])
+    plain = mesh_render.main(["--mesh", str(exported["plain"][1] / "mesh.obj"), "--views", "1", "--img-size", "40"])
+    assert plain["mesh"]["appearance"] == "vertex"
+
+
+def _env():
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
+    return env
+
+
+def test_two_ranks_sharing_one_gpu_equal_one_rank():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a MI355X")
+    world = 2
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
+           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "texture_dist_worker.py")]
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
+    assert f"TEXTURE_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
