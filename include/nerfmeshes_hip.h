@@ -57,6 +57,8 @@ extern "C" {
 /* 6, later: + nm_mesh_texture_layout, _samples, _fill, _uv, _lookup, nm_export_obj_textured: a texture atlas of per-face
  * charts baked from the network, and its fetch at the rasteriser's pixels (mesh_nerf --texture-res, mesh_render
  * --appearance).  Additions only. */
+/* 6, later: + nm_mesh_visibility_views (+ _workspace_bytes), _select, _compact: the faces no camera of a set sees are dropped
+ * (mesh_nerf --cull-hidden-views).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -959,6 +961,56 @@ int nm_mesh_rasterize(const nm_view* view, const float* d_verts, int64_t num_ver
 int nm_mesh_interpolate(const int32_t* d_face_id, const float* d_bary, int64_t num_pixels, const int32_t* d_faces, int64_t num_faces,
                         const float* d_attributes, int64_t num_vertices, int32_t channels, const float* d_background, float* d_out,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Hidden faces of a mesh (mesh_nerf --cull-hidden-views; DESIGN.md, "Hidden faces"): the faces that no camera of a set sees
+ * are dropped.  Built on the rasteriser above: integer work only, the same bytes whatever order the workgroups ran in, and a
+ * numpy restatement (tests/mesh_visibility.py) reproduces every array and every count bit for bit.  THE RULE:
+ *
+ *   inputs     d_verts (V,3) fp32, d_faces (F,3) int32; M views under the constraints of nm_mesh_rasterize (non-NDC, sides in
+ *              [1, 16384], focal finite and > 0); near, large_threshold as there; rings >= 0.
+ *   seen       the views are taken in the order given.  Each runs the rasteriser's vertex stage and its two face paths exactly
+ *              as nm_mesh_rasterize does without NM_MESH_RASTER_CULL_BACK: both windings drawn, the same reject reasons.  Face f
+ *              is SEEN when it is the winner -- the low 32 bits of the pixel's word -- of at least one pixel of at least one
+ *              view.  new_faces[k] = the faces whose bit view k set first: the views run in stream order, exactly one atomic OR
+ *              per bit observes it clear, and a bit read as set is never counted (bits only rise, as the pixels' words only
+ *              fall).
+ *   rings      `rings` times: (1) the vertex bit of every corner of every kept face is set; (2) every face with valid indices
+ *              and at least one marked corner becomes kept.  Step 2 reads only what step 1 finished writing.  This keeps the
+ *              faces smaller than a pixel, which win no pixel centre, next to faces that did.  rings = 0 keeps the winners.
+ *   bad faces  a face with an index outside [0, V) is never dereferenced and never kept; it is counted.
+ *   output     the kept faces in their original order; a vertex is kept iff a kept face uses it; renumbering as numpy's
+ *              new = cumsum(keep_v) - 1; out = new[faces[keep_f]] (csrc/compact.h: no atomic queue); the kept rows of every
+ *              per-vertex input that is not NULL; optionally the kept faces' original indices.
+ *
+ * nm_mesh_visibility_views: `views` is a HOST array of num_views >= 0 nm_view.  Per view: the words cleared, the vertex stage,
+ *   the two face paths, then one thread per pixel marks the winner (a lane whose left neighbour holds the same face leaves the
+ *   atomic to it; the count is taken per wave by ballot).  clear != 0 zeroes the seen bits first; with clear == 0 a call
+ *   accumulates onto the bits of the calls before it (the first call on a workspace must clear).  d_new_faces (num_views,)
+ *   int64 on the DEVICE; d_reject_counts (num_views, NM_MESH_RASTER_COUNTS) int64 on the device, or NULL: every view's
+ *   nm_mesh_rasterize counts.  Allocates nothing and never waits for the host.
+ * nm_mesh_visibility_select: the rings, the final vertex bits and the prefix sums, then the one host synchronisation: the
+ *   numbers of vertices and faces kept, of faces seen and of bad faces.  It starts from the seen bits and leaves them intact: it
+ *   may be called again with another `rings` (at most NM_MESH_VISIBILITY_MAX_RINGS).
+ * nm_mesh_visibility_compact: with that workspace, d_out_verts / d_out_normals (vertices_kept,3) for the inputs that are not
+ *   NULL, d_out_faces (faces_kept,3), d_out_face_index (faces_kept,) int32 or NULL.  No host synchronisation.
+ * V and F are in [0, 2^31 - 64).  The workspace (nm_mesh_visibility_workspace_bytes, 0 for sizes out of range; 256-byte aligned)
+ * holds a header, the seen, face and vertex bits (one 64-bit word per 64 elements), their popcount prefix sums and the
+ * rasteriser's workspace for max_height max_width pixels, the product no view may exceed; it must stay untouched between the
+ * calls.  Argument errors return 2 before any HIP call, in the rasteriser's words where the condition is the rasteriser's.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_MESH_VISIBILITY_MAX_RINGS 1024
+int64_t nm_mesh_visibility_workspace_bytes(int64_t num_vertices, int64_t num_faces, int32_t max_height, int32_t max_width);
+int nm_mesh_visibility_views(const nm_view* views, int64_t num_views, const float* d_verts, int64_t num_vertices,
+                             const int32_t* d_faces, int64_t num_faces, float near, int32_t large_threshold, int32_t clear,
+                             void* d_workspace, int64_t* d_new_faces, int64_t* d_reject_counts, void* stream);
+int nm_mesh_visibility_select(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t rings, void* d_workspace,
+                              int64_t* h_vertices_kept, int64_t* h_faces_kept, int64_t* h_faces_seen, int64_t* h_bad_faces,
+                              void* stream);
+int nm_mesh_visibility_compact(const void* d_workspace, const int32_t* d_faces, int64_t num_faces, int64_t num_vertices,
+                               const float* d_verts, const float* d_normals, int64_t vertices_kept, int64_t faces_kept,
+                               float* d_out_verts, int32_t* d_out_faces, float* d_out_normals, int32_t* d_out_face_index,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Texture atlas of a mesh (mesh_nerf --texture-res, mesh_render --appearance; DESIGN.md, "Texture atlas"): every face gets

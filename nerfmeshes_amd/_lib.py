@@ -219,6 +219,13 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nm_mesh_interpolate": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, C.c_int32, c_void_p,
                                       c_void_p, c_void_p]),
+    "nm_mesh_visibility_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "nm_mesh_visibility_views": (C.c_int, [C.POINTER(View), C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, C.c_float, C.c_int32,
+                                           C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_visibility_select": (C.c_int, [c_void_p, C.c_int64, C.c_int64, C.c_int32, c_void_p, C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), c_void_p]),
+    "nm_mesh_visibility_compact": (C.c_int, [c_void_p, c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, C.c_int64, C.c_int64,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nm_mesh_texture_layout": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "nm_mesh_texture_samples": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                           C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),

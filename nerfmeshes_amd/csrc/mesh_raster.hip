@@ -29,6 +29,14 @@
 // by ballot).  A pixel's word is read before it is written and the atomicMin issued only where the word read is above the
 // lane's own: the words only ever fall, so a stale read costs an atomic and never changes the result.  Nothing allocates and
 // nothing synchronises with the host: both entries can be captured into a graph.
+//
+// Hidden faces (mesh_nerf --cull-hidden-views; DESIGN.md, "Hidden faces"; the rule in include/nerfmeshes_hip.h, restated in
+// tests/mesh_visibility.py): nm_mesh_visibility_views runs the three passes above per view, without mr_resolve, and
+// mv_mark_pixels (one thread per pixel) raises the seen bit of every pixel's winner; _select grows the seen set `rings` times
+// over shared vertices (mv_mark_corners: the corners of the kept faces; mv_grow: the faces with a marked corner, one ballot word
+// per wave) and takes the prefix sums of compact.h; _compact writes the kept rows in their order.  The bits only rise, as the
+// pixels' words only fall: a bit read as set costs no atomic, exactly one atomic per bit finds it clear, and that one is
+// counted -- new_faces[k] does not depend on the order of the workgroups because the views run in stream order.
 #include "compact.h"
 #include "nm_internal.h"
 
@@ -278,6 +286,118 @@ __global__ __launch_bounds__(256) void mr_interpolate(const int32_t* __restrict_
     }
 }
 
+// ---- hidden faces (nm_mesh_visibility_*) ------------------------------------------------------
+struct MvHeader {
+    unsigned long long bad_faces;      // faces with a vertex index outside [0, nv): never dereferenced, never kept
+    unsigned long long faces_seen;     // set bits of the seen words
+    unsigned long long totals[2];      // vertices kept, faces kept
+    unsigned long long pad[4];
+    unsigned long long counts[24];     // where a view's raster counts go when the caller does not want them
+};
+static_assert(sizeof(MvHeader) == 256 && NM_MESH_RASTER_COUNTS <= 24, "workspace layout");
+
+__device__ __forceinline__ bool mv_raise(unsigned long long* words, int64_t i) {
+    // sets bit i -> true when THIS call found it clear.  Bits only rise: a bit read as set stays set and costs no atomic; a stale
+    // read of a clear bit costs the atomic, whose answer is the truth -- exactly one caller per bit gets `true`.
+    const unsigned long long bit = 1ull << (i & 63);
+    if (__hip_atomic_load(words + (i >> 6), MR_RELAXED_AGENT) & bit) return false;
+    return !(__hip_atomic_fetch_or(words + (i >> 6), bit, MR_RELAXED_AGENT) & bit);
+}
+
+// one thread per pixel, whole waves (the votes): the winner's seen bit, the faces this view saw first, the covered pixels
+__global__ __launch_bounds__(256) void mv_mark_pixels(const unsigned long long* __restrict__ zbuf, int64_t pixels, int64_t nf,
+                                                      unsigned long long* seen, unsigned long long* new_faces,
+                                                      unsigned long long* counts) {
+    const int64_t pixel = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long word = pixel < pixels ? zbuf[pixel] : MR_EMPTY;
+    const bool covered = word != MR_EMPTY && (int64_t)(word & 0xffffffffull) < nf;
+    const int f = covered ? (int)(word & 0xffffffffull) : -1;
+    const int left = __shfl_up(f, 1, 64);                            // a run of pixels on one face: its first lane speaks for it
+    const bool first = covered && !(lane > 0 && left == f) && mv_raise(seen, f);
+    const unsigned long long firsts = __ballot(first), votes = __ballot(covered);
+    if (lane == 0 && firsts) atomicAdd(new_faces, (unsigned long long)__popcll(firsts));
+    if (lane == 0 && votes) atomicAdd(counts + NM_MESH_RASTER_COVERED, (unsigned long long)__popcll(votes));
+}
+
+// kept = seen (a face with a bad index is never drawn, so never seen); the header's two counts
+__global__ __launch_bounds__(256) void mv_begin(const int32_t* __restrict__ faces, int64_t nf, int nv,
+                                                const unsigned long long* __restrict__ seen, unsigned long long* __restrict__ fwords,
+                                                MvHeader* hdr) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int v[3];
+    const bool valid = f < nf && load_face(faces, f, nv, v);
+    const bool keep = valid && bit_test(seen, f);
+    const unsigned long long word = __ballot(keep), bad = __ballot(f < nf && !valid);
+    if ((threadIdx.x & 63) == 0 && (f >> 6) < (nf + 63) / 64) {
+        fwords[f >> 6] = word;
+        if (word) atomicAdd(&hdr->faces_seen, (unsigned long long)__popcll(word));
+        if (bad) atomicAdd(&hdr->bad_faces, (unsigned long long)__popcll(bad));
+    }
+}
+
+// the vertex bit of every corner of every kept face
+__global__ __launch_bounds__(256) void mv_mark_corners(const int32_t* __restrict__ faces, int64_t nf, int nv,
+                                                       const unsigned long long* __restrict__ fwords, unsigned long long* vwords) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int v[3];
+    if (f >= nf || !bit_test(fwords, f) || !load_face(faces, f, nv, v)) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mv_raise(vwords, v[k]);
+}
+
+// a face with valid indices and a marked corner becomes kept; the vertex bits are the launch in front's, complete
+__global__ __launch_bounds__(256) void mv_grow(const int32_t* __restrict__ faces, int64_t nf, int nv,
+                                               const unsigned long long* __restrict__ vwords, unsigned long long* __restrict__ fwords) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int v[3];
+    const bool keep = f < nf && load_face(faces, f, nv, v) && (bit_test(vwords, v[0]) || bit_test(vwords, v[1]) || bit_test(vwords, v[2]));
+    const unsigned long long word = __ballot(keep);
+    if ((threadIdx.x & 63) == 0 && (f >> 6) < (nf + 63) / 64) fwords[f >> 6] = word;
+}
+
+// workgroup 0 the vertex words, workgroup 1 the face words (compact.h)
+__global__ __launch_bounds__(SCAN_THREADS) void mv_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
+                                                        uint32_t* __restrict__ vprefix,
+                                                        const unsigned long long* __restrict__ fwords, int64_t nfw,
+                                                        uint32_t* __restrict__ fprefix, MvHeader* hdr) {
+    const bool f = blockIdx.x != 0;
+    const uint32_t kept = popcount_prefix_sums(f ? fwords : vwords, f ? nfw : nvw, f ? fprefix : vprefix);
+    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = kept;
+}
+
+__global__ __launch_bounds__(256) void mv_compact_vertices(const float* __restrict__ verts, const float* __restrict__ normals, int nv,
+                                                           int64_t capacity, const unsigned long long* __restrict__ words,
+                                                           const uint32_t* __restrict__ prefix, float* __restrict__ out_verts,
+                                                           float* __restrict__ out_normals) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv || !bit_test(words, v)) return;
+    const int64_t dst = bit_rank(words, prefix, v);
+    if (dst >= capacity) return;                                     // never past the caller's arrays
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (verts) out_verts[3 * dst + k] = verts[3 * v + k];
+        if (normals) out_normals[3 * dst + k] = normals[3 * v + k];
+    }
+}
+
+__global__ __launch_bounds__(256) void mv_compact_faces(const int32_t* __restrict__ faces, int64_t nf, int nv, int64_t capacity,
+                                                        const unsigned long long* __restrict__ fwords,
+                                                        const uint32_t* __restrict__ fprefix,
+                                                        const unsigned long long* __restrict__ vwords,
+                                                        const uint32_t* __restrict__ vprefix, int32_t* __restrict__ out_faces,
+                                                        int32_t* __restrict__ out_face_index) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (f >= nf || !bit_test(fwords, f)) return;
+    int v[3];
+    if (!load_face(faces, f, nv, v)) return;                         // such a face never has its bit set
+    const int64_t dst = bit_rank(fwords, fprefix, f);
+    if (dst >= capacity) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)bit_rank(vwords, vprefix, v[k]);
+    if (out_face_index) out_face_index[dst] = (int32_t)f;
+}
+
 struct MrWorkspace {
     unsigned long long* zbuf;
     MrHeader* hdr;
@@ -297,7 +417,90 @@ static MrWorkspace mr_carve(const void* ws, int64_t nv, int64_t nf, int64_t heig
     return w;
 }
 
+// Everything whose size V and F decide comes first and the visibility words last: nm_mesh_visibility_select and _compact find
+// their members without knowing the image sizes the workspace was made for.
+struct MvWorkspace {
+    MvHeader* hdr;
+    unsigned long long* seen;
+    unsigned long long* fwords;
+    uint32_t* fprefix;
+    unsigned long long* vwords;
+    uint32_t* vprefix;
+    MrWorkspace raster;
+    int64_t nvw, nfw, bytes;
+};
+
+static MvWorkspace mv_carve(const void* ws, int64_t nv, int64_t nf, int64_t pixels) {
+    Carver c(ws, 256);
+    MvWorkspace w;
+    w.nvw = (nv + 63) / 64;
+    w.nfw = (nf + 63) / 64;
+    w.hdr = c.take<MvHeader>(1);
+    w.seen = c.take<unsigned long long>(w.nfw);
+    w.fwords = c.take<unsigned long long>(w.nfw);
+    w.fprefix = c.take<uint32_t>(w.nfw);
+    w.vwords = c.take<unsigned long long>(w.nvw);
+    w.vprefix = c.take<uint32_t>(w.nvw);
+    w.raster.hdr = c.take<MrHeader>(1);
+    w.raster.vtx = c.take<MrVertex>(nv);
+    w.raster.queue = c.take<int32_t>(nf);
+    w.raster.zbuf = c.take<unsigned long long>(pixels);
+    w.bytes = w.raster.bytes = c.offset;
+    return w;
+}
+
 static bool mr_side_ok(int64_t n) { return n >= 1 && n <= MR_MAX_SIDE; }
+
+// What nm_mesh_rasterize and the nm_mesh_visibility_* entries ask of a view and of a mesh, in one place: 0 or 2
+static int mr_check_view(const nm_view* view) {
+    NM_REQUIRE(view->use_ndc == 0, "mesh raster: an NDC view has no pinhole projection to rasterise with");
+    NM_REQUIRE(mr_side_ok(view->height) && mr_side_ok(view->width), "mesh raster: height and width must be in [1, 16384]");
+    NM_REQUIRE(view->focal > 0.0 && view->focal - view->focal == 0.0, "mesh raster: focal must be finite and > 0");
+    return 0;
+}
+
+static int mr_check_mesh(int64_t num_vertices, int64_t num_faces) {
+    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces), "mesh raster: vertex and face counts must be in [0, 2^31 - 64)");
+    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh raster: faces without vertices");
+    return 0;
+}
+
+static int mr_check_limits(float near, int32_t large_threshold) {
+    NM_REQUIRE(near > 0.0f && near - near == 0.0f, "mesh raster: near must be finite and > 0");        // a NaN fails the comparison
+    NM_REQUIRE(large_threshold >= 0, "mesh raster: large_threshold must be >= 0");
+    return 0;
+}
+
+// The passes both entries share: the words, the queue and the counts cleared, the vertex stage and the two face paths.  After
+// it w.zbuf holds every pixel's winner and counts[] everything but NM_MESH_RASTER_COVERED.
+static int mr_draw(const nm_view* view, const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
+                   float near, int cull, int32_t large_threshold, const MrWorkspace& w, unsigned long long* counts, hipStream_t s) {
+    const int height = view->height, width = view->width, nv = (int)num_vertices;
+    MrCamera cam;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) cam.rot[3 * r + c] = (double)view->c2w[4 * r + c];
+        cam.origin[r] = (double)view->c2w[4 * r + 3];
+    }
+    cam.focal = view->focal;
+    cam.half_w = (double)width * 0.5;
+    cam.half_h = (double)height * 0.5;
+    cam.height = height;
+    cam.width = width;
+    NM_HIP_CHECK(hipMemsetAsync(w.zbuf, 0xff, sizeof(unsigned long long) * (size_t)height * (size_t)width, s));
+    NM_HIP_CHECK(hipMemsetAsync(w.hdr, 0, sizeof(MrHeader), s));
+    NM_HIP_CHECK(hipMemsetAsync(counts, 0, sizeof(int64_t) * NM_MESH_RASTER_COUNTS, s));
+    if (num_faces) {
+        hipLaunchKernelGGL(mr_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, nv, cam, w.vtx);
+        NM_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(mr_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, w.vtx, near, cull, height,
+                           width, (long long)large_threshold, w.zbuf, w.queue, w.hdr, counts);
+        NM_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(mr_large, dim3(MR_LARGE_GRID), dim3(256), 0, s, d_faces, nv, w.vtx, near, cull, height, width, w.zbuf,
+                           w.queue, w.hdr, counts);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}
 
 }  // namespace nm
 
@@ -314,48 +517,116 @@ int nm_mesh_rasterize(const nm_view* view, const float* d_verts, int64_t num_ver
                       float near, int32_t flags, int32_t large_threshold, void* d_workspace, int32_t* d_face_id, float* d_depth,
                       float* d_bary, int64_t* d_counts, void* stream) {
     NM_REQUIRE(view != nullptr, "bad argument");
-    NM_REQUIRE(view->use_ndc == 0, "mesh raster: an NDC view has no pinhole projection to rasterise with");
-    NM_REQUIRE(mr_side_ok(view->height) && mr_side_ok(view->width), "mesh raster: height and width must be in [1, 16384]");
-    NM_REQUIRE(view->focal > 0.0 && view->focal - view->focal == 0.0, "mesh raster: focal must be finite and > 0");
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces), "mesh raster: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh raster: faces without vertices");
-    NM_REQUIRE(near > 0.0f && near - near == 0.0f, "mesh raster: near must be finite and > 0");        // a NaN fails the comparison
+    if (mr_check_view(view) || mr_check_mesh(num_vertices, num_faces) || mr_check_limits(near, large_threshold)) return 2;
     NM_REQUIRE((flags & ~NM_MESH_RASTER_CULL_BACK) == 0, "mesh raster: unknown flags");
-    NM_REQUIRE(large_threshold >= 0, "mesh raster: large_threshold must be >= 0");
     NM_REQUIRE(d_workspace && d_face_id && d_depth && d_bary && d_counts && (num_vertices == 0 || d_verts) &&
                (num_faces == 0 || d_faces), "bad argument");
-    const int height = view->height, width = view->width, nv = (int)num_vertices;
+    const int height = view->height, width = view->width;
     const int64_t pixels = (int64_t)height * width;
     const MrWorkspace w = mr_carve(d_workspace, num_vertices, num_faces, height, width);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    MrCamera cam;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) cam.rot[3 * r + c] = (double)view->c2w[4 * r + c];
-        cam.origin[r] = (double)view->c2w[4 * r + 3];
-    }
-    cam.focal = view->focal;
-    cam.half_w = (double)width * 0.5;
-    cam.half_h = (double)height * 0.5;
-    cam.height = height;
-    cam.width = width;
     const int cull = flags & NM_MESH_RASTER_CULL_BACK;
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(d_counts);
-    NM_HIP_CHECK(hipMemsetAsync(w.zbuf, 0xff, sizeof(unsigned long long) * (size_t)pixels, s));
-    NM_HIP_CHECK(hipMemsetAsync(w.hdr, 0, sizeof(MrHeader), s));
-    NM_HIP_CHECK(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * NM_MESH_RASTER_COUNTS, s));
-    if (num_faces) {
-        hipLaunchKernelGGL(mr_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, nv, cam, w.vtx);
-        NM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(mr_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, w.vtx, near, cull, height,
-                           width, (long long)large_threshold, w.zbuf, w.queue, w.hdr, counts);
-        NM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(mr_large, dim3(MR_LARGE_GRID), dim3(256), 0, s, d_faces, nv, w.vtx, near, cull, height, width, w.zbuf,
-                           w.queue, w.hdr, counts);
+    if (const int rc = mr_draw(view, d_verts, num_vertices, d_faces, num_faces, near, cull, large_threshold, w, counts, s)) return rc;
+    hipLaunchKernelGGL(mr_resolve, dim3(launch_grid(pixels)), dim3(256), 0, s, d_faces, num_faces, (int)num_vertices, w.vtx, near, cull,
+                       height, width, w.zbuf, d_face_id, d_depth, d_bary, counts);
+    NM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int64_t nm_mesh_visibility_workspace_bytes(int64_t num_vertices, int64_t num_faces, int32_t max_height, int32_t max_width) {
+    if (!mesh_size_ok(num_vertices) || !mesh_size_ok(num_faces) || !mr_side_ok(max_height) || !mr_side_ok(max_width)) return 0;
+    return mv_carve(nullptr, num_vertices, num_faces, (int64_t)max_height * max_width).bytes;
+}
+
+int nm_mesh_visibility_views(const nm_view* views, int64_t num_views, const float* d_verts, int64_t num_vertices,
+                             const int32_t* d_faces, int64_t num_faces, float near, int32_t large_threshold, int32_t clear,
+                             void* d_workspace, int64_t* d_new_faces, int64_t* d_reject_counts, void* stream) {
+    NM_REQUIRE(num_views >= 0, "mesh visibility: num_views must be >= 0");
+    NM_REQUIRE(num_views == 0 || (views && d_new_faces), "bad argument");
+    for (int64_t k = 0; k < num_views; ++k)
+        if (mr_check_view(views + k)) return 2;
+    if (mr_check_mesh(num_vertices, num_faces) || mr_check_limits(near, large_threshold)) return 2;
+    NM_REQUIRE(d_workspace && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces), "bad argument");
+    const MvWorkspace w = mv_carve(d_workspace, num_vertices, num_faces, 0);      // the visibility words come last
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (clear && w.nfw) NM_HIP_CHECK(hipMemsetAsync(w.seen, 0, sizeof(unsigned long long) * (size_t)w.nfw, s));
+    if (num_views) NM_HIP_CHECK(hipMemsetAsync(d_new_faces, 0, sizeof(int64_t) * (size_t)num_views, s));
+    for (int64_t k = 0; k < num_views; ++k) {
+        unsigned long long* counts = d_reject_counts ? reinterpret_cast<unsigned long long*>(d_reject_counts) + k * NM_MESH_RASTER_COUNTS
+                                                     : w.hdr->counts;
+        if (const int rc = mr_draw(views + k, d_verts, num_vertices, d_faces, num_faces, near, 0, large_threshold, w.raster, counts, s))
+            return rc;
+        if (!num_faces) continue;
+        const int64_t pixels = (int64_t)views[k].height * views[k].width;
+        hipLaunchKernelGGL(mv_mark_pixels, dim3(launch_grid(pixels)), dim3(256), 0, s, w.raster.zbuf, pixels, num_faces, w.seen,
+                           reinterpret_cast<unsigned long long*>(d_new_faces) + k, counts);
         NM_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(mr_resolve, dim3(launch_grid(pixels)), dim3(256), 0, s, d_faces, num_faces, nv, w.vtx, near, cull, height,
-                       width, w.zbuf, d_face_id, d_depth, d_bary, counts);
+    return 0;
+}
+
+int nm_mesh_visibility_select(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t rings, void* d_workspace,
+                              int64_t* h_vertices_kept, int64_t* h_faces_kept, int64_t* h_faces_seen, int64_t* h_bad_faces,
+                              void* stream) {
+    if (mr_check_mesh(num_vertices, num_faces)) return 2;
+    NM_REQUIRE(rings >= 0 && rings <= NM_MESH_VISIBILITY_MAX_RINGS, "mesh visibility: rings must be in [0, 1024]");
+    NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces) && h_vertices_kept && h_faces_kept && h_faces_seen && h_bad_faces,
+               "bad argument");
+    const MvWorkspace w = mv_carve(d_workspace, num_vertices, num_faces, 0);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = (int)num_vertices;
+    const unsigned fgrid = launch_grid(num_faces);
+    NM_HIP_CHECK(hipMemsetAsync(w.hdr, 0, sizeof(MvHeader), s));
+    if (num_faces) {
+        hipLaunchKernelGGL(mv_begin, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.seen, w.fwords, w.hdr);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    for (int r = 0; r <= rings && num_faces; ++r) {                  // the last round only leaves the final vertex bits
+        NM_HIP_CHECK(hipMemsetAsync(w.vwords, 0, sizeof(unsigned long long) * (size_t)w.nvw, s));
+        hipLaunchKernelGGL(mv_mark_corners, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.fwords, w.vwords);
+        NM_HIP_CHECK(hipGetLastError());
+        if (r == rings) break;
+        hipLaunchKernelGGL(mv_grow, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.vwords, w.fwords);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    if (!num_faces && w.nvw) NM_HIP_CHECK(hipMemsetAsync(w.vwords, 0, sizeof(unsigned long long) * (size_t)w.nvw, s));
+    hipLaunchKernelGGL(mv_scan, dim3(2), dim3(SCAN_THREADS), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
     NM_HIP_CHECK(hipGetLastError());
+    MvHeader h;
+    NM_HIP_CHECK(hipMemcpyAsync(&h, w.hdr, sizeof(MvHeader), hipMemcpyDeviceToHost, s));
+    NM_HIP_CHECK(hipStreamSynchronize(s));
+    *h_vertices_kept = (int64_t)h.totals[0];
+    *h_faces_kept = (int64_t)h.totals[1];
+    *h_faces_seen = (int64_t)h.faces_seen;
+    *h_bad_faces = (int64_t)h.bad_faces;
+    return 0;
+}
+
+int nm_mesh_visibility_compact(const void* d_workspace, const int32_t* d_faces, int64_t num_faces, int64_t num_vertices,
+                               const float* d_verts, const float* d_normals, int64_t vertices_kept, int64_t faces_kept,
+                               float* d_out_verts, int32_t* d_out_faces, float* d_out_normals, int32_t* d_out_face_index,
+                               void* stream) {
+    if (mr_check_mesh(num_vertices, num_faces)) return 2;
+    NM_REQUIRE(vertices_kept >= 0 && vertices_kept <= num_vertices && faces_kept >= 0 && faces_kept <= num_faces,
+               "mesh visibility: the kept counts must lie within the mesh's");
+    NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces), "bad argument");
+    NM_REQUIRE(vertices_kept == 0 || ((!d_verts || d_out_verts) && (!d_normals || d_out_normals)),
+               "mesh visibility: an input array without its output");
+    NM_REQUIRE(faces_kept == 0 || d_out_faces, "mesh visibility: null face output");
+    const MvWorkspace w = mv_carve(d_workspace, num_vertices, num_faces, 0);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = (int)num_vertices;
+    if (vertices_kept && (d_verts || d_normals)) {
+        hipLaunchKernelGGL(mv_compact_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, vertices_kept,
+                           w.vwords, w.vprefix, d_out_verts, d_out_normals);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    if (faces_kept) {
+        hipLaunchKernelGGL(mv_compact_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, faces_kept, w.fwords,
+                           w.fprefix, w.vwords, w.vprefix, d_out_faces, d_out_face_index);
+        NM_HIP_CHECK(hipGetLastError());
+    }
     return 0;
 }
 

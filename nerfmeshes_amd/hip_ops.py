@@ -940,6 +940,54 @@ def mesh_interpolate(raster, faces, attributes, background):
     return out
 
 
+VISIBILITY_MAX_RINGS = 1024              # NM_MESH_VISIBILITY_MAX_RINGS
+
+
+def mesh_cull_hidden(verts, faces, normals, views, near, rings=1, large_threshold=None):
+    """Drops the faces no camera of `views` sees (nm_mesh_visibility_views + _select + _compact; the rule in
+    include/nerfmeshes_hip.h): a face stays when it wins a pixel of the rasteriser in at least one view -- both windings drawn,
+    a face with a corner nearer than `near` not at all --, or is within `rings` rounds of sharing a vertex with one that does.
+    verts (V,3) f32, faces (F,3) i32, normals (V,3) f32 or None on the GPU; views: non-NDC hip_ops.make_view results.
+    -> (verts, faces, normals, face_index, info): the kept rows in their original order, faces renumbered (numpy: new =
+    cumsum(keep_v) - 1; new[faces[keep_f]]), normals None where None came in, face_index (faces_kept,) int32: the kept faces'
+    original indices; info = dict(faces, faces_seen, faces_kept, vertices, vertices_kept, bad_faces, new_faces: per view the
+    faces it saw first).  Nothing left gives empty (0,3) arrays.  One read-back of the counts, one of new_faces."""
+    lib = _lib.load()
+    rings = int(rings)
+    if not 0 <= rings <= VISIBILITY_MAX_RINGS:
+        raise ValueError(f"mesh_cull_hidden: rings must be in [0, {VISIBILITY_MAX_RINGS}], got {rings}")
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = _dev32(verts, dev, "verts")
+    normals = _dev32(normals, dev, "normals") if normals is not None else None
+    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)):
+        raise ValueError("mesh_cull_hidden: the per-vertex arrays disagree on the vertex count")
+    views = list(views)
+    array = (_lib.View * max(len(views), 1))(*views)
+    height, width = (max(int(v.height) for v in views), max(int(v.width) for v in views)) if views else (1, 1)
+    threshold = RASTER_LARGE_THRESHOLD if large_threshold is None else int(large_threshold)
+    ws = _mesh_workspace(int(lib.nm_mesh_visibility_workspace_bytes(nv, nf, height, width)), "mesh visibility", nv, nf, dev)
+    new_faces = torch.empty(len(views), dtype=torch.int64, device=dev)
+    rc = lib.nm_mesh_visibility_views(array, len(views), _ptr(verts), nv, _ptr(faces), nf, float(near), threshold, 1, _ptr(ws),
+                                      _ptr(new_faces), None, _stream())
+    _mesh_check(lib, rc, "nm_mesh_visibility_views")
+    kv, kf, seen, bad = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    rc = lib.nm_mesh_visibility_select(_ptr(faces), nf, nv, rings, _ptr(ws), C.byref(kv), C.byref(kf), C.byref(seen), C.byref(bad),
+                                       _stream())
+    _mesh_check(lib, rc, "nm_mesh_visibility_select")
+    out_verts = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
+    out_normals = torch.empty(kv.value, 3, dtype=torch.float32, device=dev) if normals is not None else None
+    out_faces = torch.empty(kf.value, 3, dtype=torch.int32, device=dev)
+    face_index = torch.empty(kf.value, dtype=torch.int32, device=dev)
+    if kv.value:
+        check(lib.nm_mesh_visibility_compact(_ptr(ws), _ptr(faces), nf, nv, _ptr(verts), _ptr(normals), kv.value, kf.value,
+                                             _ptr(out_verts), _ptr(out_faces), _ptr(out_normals), _ptr(face_index), _stream()),
+              "nm_mesh_visibility_compact")
+    info = dict(faces=nf, faces_seen=seen.value, faces_kept=kf.value, vertices=nv, vertices_kept=kv.value, bad_faces=bad.value,
+                new_faces=[int(x) for x in new_faces.tolist()])
+    return out_verts, out_faces, out_normals, face_index, info
+
+
 TEXTURE_MAX_RES = 255                    # NM_MESH_TEXTURE_MAX_RES
 TEXTURE_MAX_SIDE = 16384                 # NM_MESH_TEXTURE_MAX_SIDE
 

@@ -17,6 +17,8 @@ reference checkout: what a maintainer gets who changes nothing (tests/test_gpu_s
 one recorded from the reference's script; bench.py times its inner loop as `mesh.grid_query.at_reference_batch_1024`).
 """
 import argparse
+import json
+import math
 import os
 
 import torch
@@ -290,6 +292,50 @@ def filter_components(vertices, triangles, normals, min_faces, keep_largest):
     return vertices, triangles, normals
 
 
+CULL_MAX_SIZE = 16384       # the rasteriser's largest image side
+
+
+def cull_size(res):
+    """`--cull-size 0`: the smallest multiple of 256 that gives a voxel of a res^3 grid at least 2 pixels when the grid's box
+    fills 95 % of the image, at most the rasteriser's 16384 (1792 at --res 480)"""
+    return min(int(math.ceil(2.0 * math.sqrt(3.0) * res / 0.95 / 256.0)) * 256, CULL_MAX_SIZE)
+
+
+def cull_hidden(vertices, triangles, normals, args):
+    """`--cull-hidden-views N` on the device (hip_ops.mesh_cull_hidden): the mesh is rasterised from N cameras all around it
+    (mesh_render.sphere_views at --cull-radius bounding radii, --cull-size pixels square) and only the faces that win a pixel
+    somewhere stay, with --cull-rings rounds of their vertex neighbours -- the faces too small to win a pixel centre.  Kept
+    vertices and triangles stay in their order.  Rank 0 writes <save-dir>/<mesh-name stem>.visibility.json.  ValueError when
+    nothing is left."""
+    from . import dist as nd
+    from . import mesh_render
+    count, rings, radius = int(args.cull_hidden_views), int(args.cull_rings), float(args.cull_radius)
+    res = max(_nums(args.res))
+    size = int(args.cull_size) or cull_size(res)
+    centre, distance, focal, near = mesh_render.frame_views(vertices, radius, size)
+    views = [hip_ops.make_view(pose, h, w, f) for pose, h, w, f, _ in mesh_render.sphere_views(count, centre, distance, size, focal)]
+    vertices, triangles, normals, _, info = hip_ops.mesh_cull_hidden(vertices, triangles.to(torch.int32), normals, views, near,
+                                                                     rings=rings)
+    # the bounding sphere, 2 distance / --cull-radius across, spans 0.95 size pixels
+    per_voxel = 0.95 * size * (2.0 * args.limit / res) / (2.0 * distance / radius)
+    if info["faces_kept"] == 0:
+        raise ValueError(f"--cull-hidden-views {count} leaves nothing of {info['faces']} faces: no view of {size}^2 pixels sees one")
+    print(f"Hidden-face filter: kept {info['faces_kept']} of {info['faces']} faces ({info['faces_seen']} seen), "
+          f"{info['vertices_kept']} of {info['vertices']} vertices, {count} views of {size}\u00b2, {per_voxel:.2f} px/voxel")
+    if per_voxel < 1.0:
+        print(f"Warning: {per_voxel:.2f} pixels per voxel: faces smaller than a pixel are kept only through --cull-rings; raise "
+              "--cull-size")
+    if nd.world()[0] == 0:
+        path = os.path.join(args.save_dir, os.path.splitext(args.mesh_name)[0] + ".visibility.json")
+        report = dict(info, views=count, size=size, rings=rings, radius=radius, focal=focal, near=near, centre=[float(x) for x in centre],
+                      distance=distance, pixels_per_voxel=per_voxel)
+        with open(path, "w") as fh:
+            json.dump(report, fh, indent=1)
+            fh.write("\n")
+        print(f"Hidden-face report saved to {path}")
+    return vertices, triangles, normals
+
+
 SMOOTH_FLIP = -1            # marching cubes winds its triangles against its normals (tests/test_mesh_smooth.py pins it)
 
 
@@ -360,6 +406,9 @@ def export_marching_cubes(model, args, cfg, device):
     `--smooth-iters N` smooths the full-resolution mesh (smooth_mesh) between the component filter and the clustering, which
     then averages smoothed positions and the recomputed normals; the cache keeps the unsmoothed mesh, and every rank smooths
     redundantly.
+    `--cull-hidden-views N` drops the faces that none of N cameras around the mesh sees (cull_hidden) right after the component
+    filter, on the full-resolution geometry: the smoothing, the clustering, the appearance rays and the texture bake then work on
+    less; the cache keeps the unculled mesh, and every rank culls redundantly.
     `--texture-res N` bakes a texture atlas after the per-vertex appearance (bake_texture), which stays: the `v` lines keep
     their colours, so a viewer without textures still shows them; the OBJ gains `vt` lines, an .mtl and a .png."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
@@ -388,6 +437,16 @@ def export_marching_cubes(model, args, cfg, device):
                 and -1.0 <= args.smooth_mu <= 0.0):
             raise ValueError(f"--smooth-iters must be in [0, {hip_ops.SMOOTH_MAX_ITERATIONS}], --smooth-lambda in (0, 1] and "
                              "--smooth-mu in [-1, 0]")
+    cull_views = int(getattr(args, "cull_hidden_views", 0))
+    if cull_views or any(getattr(args, name, default) != default for name, default in
+                         (("cull_size", 0), ("cull_rings", 1), ("cull_radius", 3.0))):
+        if getattr(args, "route", "kernel") == "script":
+            raise ValueError("--cull-hidden-views / --cull-size / --cull-rings / --cull-radius have no --route script: the "
+                             "reference's script has no such step")
+        if not (cull_views >= 0 and 0 <= int(args.cull_size) <= CULL_MAX_SIZE and 0 <= int(args.cull_rings) <= hip_ops.VISIBILITY_MAX_RINGS
+                and 1.0 < float(args.cull_radius) < float("inf")):
+            raise ValueError(f"--cull-hidden-views must be >= 0, --cull-size in [0, {CULL_MAX_SIZE}], --cull-rings in "
+                             f"[0, {hip_ops.VISIBILITY_MAX_RINGS}] and --cull-radius finite and > 1")
     target_mesh = getattr(args, "target_mesh", None)
     if target_mesh:
         if getattr(args, "route", "kernel") == "script":
@@ -416,6 +475,8 @@ def export_marching_cubes(model, args, cfg, device):
         vertices, triangles, normals = (torch.as_tensor(t).to(device) for t in (vertices, triangles, normals))
         if min_faces or keep_largest:
             vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
+        if cull_views:
+            vertices, triangles, normals = cull_hidden(vertices, triangles, normals, args)
         if smooth_iters:
             vertices, triangles, normals = smooth_mesh(vertices, triangles, normals, args)
         if simplify_cell:
@@ -426,6 +487,8 @@ def export_marching_cubes(model, args, cfg, device):
         unfiltered = vertices, triangles, normals          # what the cache keeps, so that the filter can be tuned on it
         if min_faces or keep_largest:                      # first: a filter that leaves nothing raises before anything is written
             vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
+        if cull_views:                                     # likewise, on the full-resolution geometry: the later stages work on less
+            vertices, triangles, normals = cull_hidden(vertices, triangles, normals, args)
         if smooth_iters:
             vertices, triangles, normals = smooth_mesh(vertices, triangles, normals, args)
         if simplify_cell:                                  # likewise: no triangle left raises here
@@ -621,6 +684,20 @@ def build_parser():
                    help="(addition) simplify the mesh by vertex clustering: the vertices in one cell of a grid of this many voxels "
                         "per edge become their mean, degenerate and duplicate triangles go; after the component filter, before "
                         "the normals and the appearance query (0 = off)")
+    p.add_argument("--cull-hidden-views", type=_non_negative, default=0,
+                   help="(addition) drop the faces no outside camera sees: rasterise the mesh on the GPU from this many cameras "
+                        "spread evenly over a sphere around it and keep the faces that win a pixel in at least one view; after "
+                        "the component filter, before --smooth-iters, --simplify-cell and the appearance query; writes "
+                        "<save-dir>/<mesh-name stem>.visibility.json (0 = off)")
+    p.add_argument("--cull-size", type=_non_negative, default=0,
+                   help="(addition) side in pixels of the --cull-hidden-views images; 0 (default): the smallest multiple of 256 "
+                        "that gives every voxel at least 2 pixels, at most 16384")
+    p.add_argument("--cull-rings", type=_non_negative, default=1,
+                   help="(addition) rounds in which the faces that share a vertex with a kept face are kept too: the faces too "
+                        "small to win a pixel centre next to visible ones (0: exactly the faces that won a pixel)")
+    p.add_argument("--cull-radius", type=float, default=3.0,
+                   help="(addition) distance of the --cull-hidden-views cameras from the centre of the mesh's bounding box, in "
+                        "bounding radii; finite and > 1")
     p.add_argument("--smooth-iters", type=_non_negative, default=0,
                    help="(addition) smooth the mesh with this many iterations of Taubin's lambda | mu filter on the GPU: after "
                         "the component filter, before --simplify-cell, the normals and the appearance query; the vertex normals "

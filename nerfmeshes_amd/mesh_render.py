@@ -225,6 +225,52 @@ def orbit_views(count, height, width, focal, radius=4.0, phi=-30.0):
         yield pose, height, width, focal, None
 
 
+def sphere_poses(count, centre, radius):
+    """(count, 3, 4) fp32 camera-to-world matrices on a Fibonacci lattice of the sphere (centre, radius), every camera looking
+    at the centre: z_k = 1 - (2k + 1) / count, a_k = k pi (3 - sqrt 5), d_k = (sqrt(1 - z^2) cos a, sqrt(1 - z^2) sin a, z); the
+    eye is centre + radius d_k, the camera's backward axis d_k, right = unit(up x d_k), up' = d_k x right with up = (0, 0, 1),
+    or (0, 1, 0) when |z_k| > 0.999.  fp64 on the host, cast to fp32 once."""
+    centre = np.asarray(centre, np.float64).reshape(3)
+    poses = np.zeros((int(count), 3, 4), np.float64)
+    for k in range(int(count)):
+        z = 1.0 - (2 * k + 1) / np.float64(count)
+        a = k * (np.pi * (3.0 - np.sqrt(5.0)))
+        s = np.sqrt(1.0 - z * z)
+        d = np.array([s * np.cos(a), s * np.sin(a), z], np.float64)
+        up = np.array([0.0, 1.0, 0.0] if abs(z) > 0.999 else [0.0, 0.0, 1.0], np.float64)
+        right = np.cross(up, d)
+        right /= np.sqrt((right * right).sum())
+        poses[k, :, 0], poses[k, :, 1], poses[k, :, 2] = right, np.cross(d, right), d
+        poses[k, :, 3] = centre + np.float64(radius) * d
+    return poses.astype(np.float32)
+
+
+def sphere_views(count, centre, radius, size, focal):
+    """`count` square views of side `size` from all around (sphere_poses), in `orbit_views`' form"""
+    for pose in sphere_poses(count, centre, radius):
+        yield pose, size, size, focal, None
+
+
+def frame_views(verts, cull_radius, size):
+    """The framing of sphere_views for a mesh, done once: with lo and hi the fp32 extremes of the vertices, centre = (lo + hi) /
+    2 in fp64, rb = half the box diagonal, radius = cull_radius rb, focal = 0.5 size sqrt(radius^2 - rb^2) / rb 0.95 and near =
+    (float)((radius - rb) / 2): the bounding sphere fills 95 % of the image and no face can fail the near test.
+    -> (centre (3,) fp64, radius, focal, near).  ValueError for no vertex, a vertex that is not finite, or a box without extent."""
+    verts = torch.as_tensor(verts)
+    if not 1.0 < float(cull_radius) < float("inf"):
+        raise ValueError(f"frame_views: the radius must be finite and > 1 bounding radii, got {cull_radius}")
+    if verts.shape[0] == 0:
+        raise ValueError("frame_views: no vertex to frame")
+    lo = verts.to(torch.float32).min(dim=0).values.cpu().numpy().astype(np.float64)
+    hi = verts.to(torch.float32).max(dim=0).values.cpu().numpy().astype(np.float64)
+    rb = 0.5 * np.sqrt(((hi - lo) ** 2).sum())
+    if not (np.isfinite(rb) and rb > 0):
+        raise ValueError(f"frame_views: the vertices' box [{lo}, {hi}] is not finite or has no extent")
+    radius = np.float64(cull_radius) * rb
+    focal = 0.5 * size * np.sqrt(radius * radius - rb * rb) / rb * 0.95
+    return (lo + hi) / 2, float(radius), float(focal), float(np.float32((radius - rb) / 2))
+
+
 def pose_from_rays(origins, directions, height, width, focal):
     """The (3,4) camera-to-world that get_ray_bundle made these rays from: a dataset (or its ray cache) keeps the rays of
     an image, not its pose.  directions (H*W,3) = R @ unit(x, y, -1): R^T is the least-squares solution over a grid of
