@@ -16,9 +16,9 @@
 //                       (count descending, label ascending) as K rounds of a 64-bit max-reduction over the key
 //                       count << 32 | (2^32 - 1 - label): round r takes the largest key below round r-1's.  The keep bits of
 //                       vertices and faces leave each wave as one ballot word.
-//   4. cc_scan / cc_compact_*   the ordered compaction of compact.h over both sets of words: the output order is the input
-//                       order, whatever order the workgroups ran in, and a kept vertex's new index is its rank among the set
-//                       bits, which is numpy's cumsum(keep) - 1.
+//   4. subset_scan / subset_compact_*   the ordered compaction of compact.h over both sets of words (mesh_subset.hip): the
+//                       output order is the input order, whatever order the workgroups ran in, and a kept vertex's new index
+//                       is its rank among the set bits, which is numpy's cumsum(keep) - 1.
 // The only host round trip is the one that returns the output sizes (nm_mesh_components_select).
 #include "compact.h"
 #include "nm_internal.h"
@@ -34,7 +34,7 @@ struct CcHeader {
     unsigned long long pad2[4];
 };
 
-__device__ __forceinline__ int cc_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int cc_load(int* p) { return __hip_atomic_load(p, NM_RELAXED_AGENT); }
 
 // Root of v, halving the path on the way.  parent[x] <= x always and values only decrease, so v strictly decreases in every
 // iteration: at most v of them, and the two `>=` exits end the walk even on memory that is not a forest.
@@ -44,7 +44,7 @@ __device__ __forceinline__ int cc_find(int* parent, int v) {
         if (p >= v) return v;
         const int g = cc_load(parent + p);
         if (g >= p) return p;
-        __hip_atomic_fetch_min(parent + v, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // g is an ancestor of v and smaller
+        __hip_atomic_fetch_min(parent + v, g, NM_RELAXED_AGENT);   // g is an ancestor of v and smaller
         v = g;
     }
 }
@@ -58,9 +58,7 @@ __device__ __forceinline__ void cc_union(int* parent, int a, int b) {
         if (a == b) return;
         const int hi = a > b ? a : b, lo = a > b ? b : a;
         int expected = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &expected, lo, __ATOMIC_RELAXED, NM_RELAXED_AGENT)) return;
         if (expected >= hi) return;                                  // cannot happen on a forest; never spin
         a = expected;
         b = lo;
@@ -168,9 +166,9 @@ __global__ __launch_bounds__(256) void cc_mask_vertices(const int* __restrict__ 
     const int root = valid ? labels[v] : 0;
     const bool keep = valid && cc_keeps(counts, nv, root, min_faces, threshold);
     const bool is_root = valid && root == (int)v;
-    const unsigned long long word = __ballot(keep), seen = __ballot(is_root), kept = __ballot(is_root && keep);
-    if ((threadIdx.x & 63) == 0 && (v >> 6) < ((int64_t)nv + 63) / 64) {
-        words[v >> 6] = word;
+    store_keep_word(words, v, nv, keep);
+    const unsigned long long seen = __ballot(is_root), kept = __ballot(is_root && keep);
+    if ((threadIdx.x & 63) == 0) {                                   // a wave beyond the last word has no root to count
         if (seen) atomicAdd(&hdr->totals[2], (unsigned long long)__popcll(seen));
         if (kept) atomicAdd(&hdr->totals[3], (unsigned long long)__popcll(kept));
     }
@@ -184,80 +182,24 @@ __global__ __launch_bounds__(256) void cc_mask_faces(const int32_t* __restrict__
     const unsigned long long threshold = keep_largest ? best[keep_largest - 1] : 0ull;
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int v[3];
-    const bool keep = f < nf && load_face(faces, f, nv, v) && cc_keeps(counts, nv, labels[v[0]], min_faces, threshold);
-    const unsigned long long word = __ballot(keep);
-    if ((threadIdx.x & 63) == 0 && (f >> 6) < (nf + 63) / 64) words[f >> 6] = word;
-}
-
-// workgroup 0 the vertex words, workgroup 1 the face words (compact.h)
-__global__ __launch_bounds__(SCAN_THREADS) void cc_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
-                                                        uint32_t* __restrict__ vprefix,
-                                                        const unsigned long long* __restrict__ fwords, int64_t nfw,
-                                                        uint32_t* __restrict__ fprefix, CcHeader* hdr) {
-    const bool f = blockIdx.x != 0;
-    const uint32_t kept = popcount_prefix_sums(f ? fwords : vwords, f ? nfw : nvw, f ? fprefix : vprefix);
-    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = kept;
-}
-
-struct CcRows {
-    const float* verts;  const float* normals;  const float* values;  const long long* keys;
-    float* out_verts;    float* out_normals;    float* out_values;    long long* out_keys;
-};
-
-__global__ __launch_bounds__(256) void cc_compact_vertices(CcRows a, int nv, int64_t capacity,
-                                                           const unsigned long long* __restrict__ words,
-                                                           const uint32_t* __restrict__ prefix) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv || !bit_test(words, v)) return;
-    const int64_t dst = bit_rank(words, prefix, v);
-    if (dst >= capacity) return;                                     // never past the caller's arrays
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (a.verts) a.out_verts[3 * dst + k] = a.verts[3 * v + k];
-        if (a.normals) a.out_normals[3 * dst + k] = a.normals[3 * v + k];
-    }
-    if (a.values) a.out_values[dst] = a.values[v];
-    if (a.keys) a.out_keys[dst] = a.keys[v];
-}
-
-__global__ __launch_bounds__(256) void cc_compact_faces(const int32_t* __restrict__ faces, int64_t nf, int nv, int64_t capacity,
-                                                        const unsigned long long* __restrict__ fwords,
-                                                        const uint32_t* __restrict__ fprefix,
-                                                        const unsigned long long* __restrict__ vwords,
-                                                        const uint32_t* __restrict__ vprefix, int32_t* __restrict__ out_faces) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || !bit_test(fwords, f)) return;
-    int v[3];
-    if (!load_face(faces, f, nv, v)) return;                         // such a face never has its bit set
-    const int64_t dst = bit_rank(fwords, fprefix, f);
-    if (dst >= capacity) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)bit_rank(vwords, vprefix, v[k]);
+    store_keep_word(words, f, nf, f < nf && load_face(faces, f, nv, v) && cc_keeps(counts, nv, labels[v[0]], min_faces, threshold));
 }
 
 struct CcWorkspace {
     CcHeader* hdr;
     int* parent;
     unsigned long long* best;
-    unsigned long long* vwords;
-    uint32_t* vprefix;
-    unsigned long long* fwords;
-    uint32_t* fprefix;
-    int64_t nvw, nfw, bytes;
+    SubsetBits bits;
+    int64_t bytes;
 };
 
 static CcWorkspace cc_carve(const void* ws, int64_t nv, int64_t nf) {
     Carver c(ws, 256);
     CcWorkspace w;
-    w.nvw = (nv + 63) / 64;
-    w.nfw = (nf + 63) / 64;
     w.hdr = c.take<CcHeader>(1);
     w.parent = c.take<int>(nv);
     w.best = c.take<unsigned long long>(CC_KMAX + 1);
-    w.vwords = c.take<unsigned long long>(w.nvw);
-    w.vprefix = c.take<uint32_t>(w.nvw);
-    w.fwords = c.take<unsigned long long>(w.nfw);
-    w.fprefix = c.take<uint32_t>(w.nfw);
+    w.bits = take_subset_bits(c, nv, nf);
     w.bytes = c.offset;
     return w;
 }
@@ -275,9 +217,7 @@ int64_t nm_mesh_components_workspace_bytes(int64_t num_vertices, int64_t num_fac
 
 int nm_mesh_components(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t* d_labels,
                        int32_t* d_face_counts, void* d_workspace, void* stream) {
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
-               "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh components: faces without vertices");
+    if (require_mesh("mesh components", num_vertices, num_faces)) return 2;
     NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces) && (num_vertices == 0 || (d_labels && d_face_counts)), "bad argument");
     const CcWorkspace w = cc_carve(d_workspace, num_vertices, num_faces);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -304,9 +244,7 @@ int nm_mesh_components_select(const int32_t* d_faces, int64_t num_faces, int64_t
                               const int32_t* d_face_counts, int64_t min_faces, int32_t keep_largest, void* d_workspace,
                               int64_t* h_vertices_kept, int64_t* h_faces_kept, int64_t* h_components,
                               int64_t* h_components_kept, void* stream) {
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
-               "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh components: faces without vertices");
+    if (require_mesh("mesh components", num_vertices, num_faces)) return 2;
     NM_REQUIRE(min_faces >= 0, "mesh components: min_faces must be >= 0");
     NM_REQUIRE(keep_largest >= 0 && keep_largest <= CC_KMAX, "mesh components: keep_largest must be in [0, 1024]");
     NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces) && (num_vertices == 0 || (d_labels && d_face_counts)) &&
@@ -321,13 +259,12 @@ int nm_mesh_components_select(const int32_t* d_faces, int64_t num_faces, int64_t
     NM_HIP_CHECK(hipGetLastError());
     if (nv)
         hipLaunchKernelGGL(cc_mask_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_labels, d_face_counts, nv,
-                           (long long)min_faces, (int)keep_largest, w.best, w.vwords, w.hdr);
+                           (long long)min_faces, (int)keep_largest, w.best, w.bits.vwords, w.hdr);
     if (num_faces)
         hipLaunchKernelGGL(cc_mask_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, d_labels,
-                           d_face_counts, (long long)min_faces, (int)keep_largest, w.best, w.fwords);
+                           d_face_counts, (long long)min_faces, (int)keep_largest, w.best, w.bits.fwords);
     NM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(cc_scan, dim3(2), dim3(SCAN_THREADS), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
-    NM_HIP_CHECK(hipGetLastError());
+    if (const int rc = subset_scan(w.bits, w.hdr->totals, s)) return rc;
     CcHeader h;
     NM_HIP_CHECK(hipMemcpyAsync(&h, w.hdr, sizeof(CcHeader), hipMemcpyDeviceToHost, s));
     NM_HIP_CHECK(hipStreamSynchronize(s));
@@ -346,31 +283,17 @@ int nm_mesh_components_compact(const void* d_workspace, const int32_t* d_faces, 
                                const float* d_verts, const float* d_normals, const float* d_values, const int64_t* d_keys,
                                int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
                                float* d_out_normals, float* d_out_values, int64_t* d_out_keys, void* stream) {
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
-               "mesh components: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh components: faces without vertices");
-    NM_REQUIRE(vertices_kept >= 0 && vertices_kept <= num_vertices && faces_kept >= 0 && faces_kept <= num_faces,
-               "mesh components: the kept counts must lie within the mesh's");
-    NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces), "bad argument");
-    NM_REQUIRE(vertices_kept == 0 || ((!d_verts || d_out_verts) && (!d_normals || d_out_normals) && (!d_values || d_out_values) &&
-                                      (!d_keys || d_out_keys)), "mesh components: an input array without its output");
-    NM_REQUIRE(faces_kept == 0 || d_out_faces, "mesh components: null face output");
+    if (require_mesh("mesh components", num_vertices, num_faces)) return 2;
+    NM_REQUIRE_COMPACT_OUTPUTS("mesh components", d_workspace && (num_faces == 0 || d_faces),
+                               (!d_verts || d_out_verts) && (!d_normals || d_out_normals) && (!d_values || d_out_values) &&
+                                   (!d_keys || d_out_keys));
     const CcWorkspace w = cc_carve(d_workspace, num_vertices, num_faces);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
-    if (vertices_kept && (d_verts || d_normals || d_values || d_keys)) {
-        const CcRows rows{d_verts, d_normals, d_values, reinterpret_cast<const long long*>(d_keys),
+    const SubsetRows rows{d_verts, d_normals, d_values, reinterpret_cast<const long long*>(d_keys),
                           d_out_verts, d_out_normals, d_out_values, reinterpret_cast<long long*>(d_out_keys)};
-        hipLaunchKernelGGL(cc_compact_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, rows, nv, vertices_kept, w.vwords,
-                           w.vprefix);
-        NM_HIP_CHECK(hipGetLastError());
-    }
-    if (faces_kept) {
-        hipLaunchKernelGGL(cc_compact_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, faces_kept,
-                           w.fwords, w.fprefix, w.vwords, w.vprefix, d_out_faces);
-        NM_HIP_CHECK(hipGetLastError());
-    }
-    return 0;
+    if (const int rc = subset_compact_vertices(rows, nv, vertices_kept, w.bits, s)) return rc;
+    return subset_compact_faces(d_faces, num_faces, nv, faces_kept, w.bits, nullptr, d_out_faces, nullptr, s);
 }
 
 }  // extern "C"

@@ -292,9 +292,7 @@ int64_t nm_mesh_face_weights_workspace_bytes(void) { return 256; }
 
 int nm_mesh_face_weights(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces, float* d_areas,
                          uint64_t* d_cdf, void* d_workspace, void* stream) {
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces),
-               "mesh face weights: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh face weights: faces without vertices");
+    if (require_mesh("mesh face weights", num_vertices, num_faces)) return 2;
     NM_REQUIRE(d_workspace && (num_faces == 0 || (d_faces && d_verts && d_cdf)), "bad argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     MmHeader* hdr = static_cast<MmHeader*>(d_workspace);

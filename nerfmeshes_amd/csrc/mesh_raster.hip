@@ -34,7 +34,7 @@
 // tests/mesh_visibility.py): nm_mesh_visibility_views runs the three passes above per view, without mr_resolve, and
 // mv_mark_pixels (one thread per pixel) raises the seen bit of every pixel's winner; _select grows the seen set `rings` times
 // over shared vertices (mv_mark_corners: the corners of the kept faces; mv_grow: the faces with a marked corner, one ballot word
-// per wave) and takes the prefix sums of compact.h; _compact writes the kept rows in their order.  The bits only rise, as the
+// per wave) and takes the prefix sums of compact.h (subset_scan); _compact writes the kept rows in their order (subset_compact_*).  The bits only rise, as the
 // pixels' words only fall: a bit read as set costs no atomic, exactly one atomic per bit finds it clear, and that one is
 // counted -- new_faces[k] does not depend on the order of the workgroups because the views run in stream order.
 #include "compact.h"
@@ -58,8 +58,6 @@ struct MrCamera {
     int32_t height, width;
 };
 
-#define MR_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
 __global__ __launch_bounds__(256) void mr_vertices(const float* __restrict__ verts, int nv, const MrCamera cam,
                                                    MrVertex* __restrict__ out) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(256) void mr_vertices(const float* __restrict__ ver
     const double xc = (xa + xb) + xd, yc = (ya + yb) + yd, zc = (za + zb) + zd;
     const float w = (float)(-zc);
     MrVertex r;
-    const bool finite = (px - px == 0.0f) && (py - py == 0.0f) && (pz - pz == 0.0f) && (w - w == 0.0f);
+    const bool finite = is_finite(px) && is_finite(py) && is_finite(pz) && is_finite(w);
     r.w = finite ? w : __uint_as_float(0x7fc00000u);
     const double wd = (double)w;
     const double ux = (xc / wd) * cam.focal, uy = -(yc / wd) * cam.focal;
@@ -102,7 +100,7 @@ __device__ __forceinline__ int mr_setup(const int32_t* __restrict__ faces, int64
     MrVertex p[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) p[k] = vtx[c[k]];
-    if (!(p[0].w - p[0].w == 0.0f) || !(p[1].w - p[1].w == 0.0f) || !(p[2].w - p[2].w == 0.0f)) return MR_NOT_FINITE;
+    if (!is_finite(p[0].w) || !is_finite(p[1].w) || !is_finite(p[2].w)) return MR_NOT_FINITE;
     if (p[0].w < near || p[1].w < near || p[2].w < near) return MR_NEAR;
     if (p[0].x == MR_OUT_OF_RANGE || p[1].x == MR_OUT_OF_RANGE || p[2].x == MR_OUT_OF_RANGE) return MR_RANGE_REJECT;
     const long long x0 = p[0].x, y0 = p[0].y, x1 = p[1].x, y1 = p[1].y, x2 = p[2].x, y2 = p[2].y;
@@ -150,12 +148,12 @@ __device__ __forceinline__ bool mr_pixel(const MrSetup& s, int i, int j, float& 
     depth = (float)(1.0 / q);
 #pragma unroll
     for (int k = 0; k < 3; ++k) bary[k] = (float)(t[k] / q);
-    return (depth - depth == 0.0f) && depth > 0.0f;
+    return is_finite(depth) && depth > 0.0f;
 }
 
 __device__ __forceinline__ void mr_write(unsigned long long* zbuf, int64_t pixel, float depth, int64_t f) {
     const unsigned long long word = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)f;
-    if (__hip_atomic_load(zbuf + pixel, MR_RELAXED_AGENT) > word) __hip_atomic_fetch_min(zbuf + pixel, word, MR_RELAXED_AGENT);
+    if (__hip_atomic_load(zbuf + pixel, NM_RELAXED_AGENT) > word) __hip_atomic_fetch_min(zbuf + pixel, word, NM_RELAXED_AGENT);
 }
 
 // a whole wave's covered (face, pixel) pairs in one integer atomic
@@ -182,7 +180,7 @@ __global__ __launch_bounds__(256) void mr_faces(const int32_t* __restrict__ face
     if (larges) {                                // one atomic per wave; the order inside the queue does not matter
         unsigned base = 0;
         const int leader = __ffsll((long long)larges) - 1;
-        if (lane == leader) base = __hip_atomic_fetch_add(&hdr->queued, (unsigned)__popcll(larges), MR_RELAXED_AGENT);
+        if (lane == leader) base = __hip_atomic_fetch_add(&hdr->queued, (unsigned)__popcll(larges), NM_RELAXED_AGENT);
         base = __shfl(base, leader, 64);
         if (large) queue[base + __popcll(larges & ((1ull << lane) - 1ull))] = (int32_t)f;     // at most nf entries: one per face
     }
@@ -216,7 +214,7 @@ __global__ __launch_bounds__(256) void mr_large(const int32_t* __restrict__ face
     if (((unsigned)blockIdx.x * 256u + threadIdx.x) / 64u >= queued) return;
     for (;;) {
         unsigned at = 0;
-        if (lane == 0) at = __hip_atomic_fetch_add(&hdr->claimed, 1u, MR_RELAXED_AGENT);
+        if (lane == 0) at = __hip_atomic_fetch_add(&hdr->claimed, 1u, NM_RELAXED_AGENT);
         at = __shfl(at, 0, 64);
         if (at >= queued) break;
         const int64_t f = queue[at];
@@ -300,8 +298,8 @@ __device__ __forceinline__ bool mv_raise(unsigned long long* words, int64_t i) {
     // sets bit i -> true when THIS call found it clear.  Bits only rise: a bit read as set stays set and costs no atomic; a stale
     // read of a clear bit costs the atomic, whose answer is the truth -- exactly one caller per bit gets `true`.
     const unsigned long long bit = 1ull << (i & 63);
-    if (__hip_atomic_load(words + (i >> 6), MR_RELAXED_AGENT) & bit) return false;
-    return !(__hip_atomic_fetch_or(words + (i >> 6), bit, MR_RELAXED_AGENT) & bit);
+    if (__hip_atomic_load(words + (i >> 6), NM_RELAXED_AGENT) & bit) return false;
+    return !(__hip_atomic_fetch_or(words + (i >> 6), bit, NM_RELAXED_AGENT) & bit);
 }
 
 // one thread per pixel, whole waves (the votes): the winner's seen bit, the faces this view saw first, the covered pixels
@@ -328,9 +326,8 @@ __global__ __launch_bounds__(256) void mv_begin(const int32_t* __restrict__ face
     int v[3];
     const bool valid = f < nf && load_face(faces, f, nv, v);
     const bool keep = valid && bit_test(seen, f);
-    const unsigned long long word = __ballot(keep), bad = __ballot(f < nf && !valid);
-    if ((threadIdx.x & 63) == 0 && (f >> 6) < (nf + 63) / 64) {
-        fwords[f >> 6] = word;
+    const unsigned long long word = store_keep_word(fwords, f, nf, keep), bad = __ballot(f < nf && !valid);
+    if ((threadIdx.x & 63) == 0) {                                   // a wave beyond the last word has no face to count
         if (word) atomicAdd(&hdr->faces_seen, (unsigned long long)__popcll(word));
         if (bad) atomicAdd(&hdr->bad_faces, (unsigned long long)__popcll(bad));
     }
@@ -351,51 +348,8 @@ __global__ __launch_bounds__(256) void mv_grow(const int32_t* __restrict__ faces
                                                const unsigned long long* __restrict__ vwords, unsigned long long* __restrict__ fwords) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     int v[3];
-    const bool keep = f < nf && load_face(faces, f, nv, v) && (bit_test(vwords, v[0]) || bit_test(vwords, v[1]) || bit_test(vwords, v[2]));
-    const unsigned long long word = __ballot(keep);
-    if ((threadIdx.x & 63) == 0 && (f >> 6) < (nf + 63) / 64) fwords[f >> 6] = word;
-}
-
-// workgroup 0 the vertex words, workgroup 1 the face words (compact.h)
-__global__ __launch_bounds__(SCAN_THREADS) void mv_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
-                                                        uint32_t* __restrict__ vprefix,
-                                                        const unsigned long long* __restrict__ fwords, int64_t nfw,
-                                                        uint32_t* __restrict__ fprefix, MvHeader* hdr) {
-    const bool f = blockIdx.x != 0;
-    const uint32_t kept = popcount_prefix_sums(f ? fwords : vwords, f ? nfw : nvw, f ? fprefix : vprefix);
-    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = kept;
-}
-
-__global__ __launch_bounds__(256) void mv_compact_vertices(const float* __restrict__ verts, const float* __restrict__ normals, int nv,
-                                                           int64_t capacity, const unsigned long long* __restrict__ words,
-                                                           const uint32_t* __restrict__ prefix, float* __restrict__ out_verts,
-                                                           float* __restrict__ out_normals) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv || !bit_test(words, v)) return;
-    const int64_t dst = bit_rank(words, prefix, v);
-    if (dst >= capacity) return;                                     // never past the caller's arrays
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (verts) out_verts[3 * dst + k] = verts[3 * v + k];
-        if (normals) out_normals[3 * dst + k] = normals[3 * v + k];
-    }
-}
-
-__global__ __launch_bounds__(256) void mv_compact_faces(const int32_t* __restrict__ faces, int64_t nf, int nv, int64_t capacity,
-                                                        const unsigned long long* __restrict__ fwords,
-                                                        const uint32_t* __restrict__ fprefix,
-                                                        const unsigned long long* __restrict__ vwords,
-                                                        const uint32_t* __restrict__ vprefix, int32_t* __restrict__ out_faces,
-                                                        int32_t* __restrict__ out_face_index) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || !bit_test(fwords, f)) return;
-    int v[3];
-    if (!load_face(faces, f, nv, v)) return;                         // such a face never has its bit set
-    const int64_t dst = bit_rank(fwords, fprefix, f);
-    if (dst >= capacity) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)bit_rank(vwords, vprefix, v[k]);
-    if (out_face_index) out_face_index[dst] = (int32_t)f;
+    store_keep_word(fwords, f, nf,
+                    f < nf && load_face(faces, f, nv, v) && (bit_test(vwords, v[0]) || bit_test(vwords, v[1]) || bit_test(vwords, v[2])));
 }
 
 struct MrWorkspace {
@@ -422,25 +376,17 @@ static MrWorkspace mr_carve(const void* ws, int64_t nv, int64_t nf, int64_t heig
 struct MvWorkspace {
     MvHeader* hdr;
     unsigned long long* seen;
-    unsigned long long* fwords;
-    uint32_t* fprefix;
-    unsigned long long* vwords;
-    uint32_t* vprefix;
+    SubsetBits bits;                             // the face pair in front
     MrWorkspace raster;
-    int64_t nvw, nfw, bytes;
+    int64_t bytes;
 };
 
 static MvWorkspace mv_carve(const void* ws, int64_t nv, int64_t nf, int64_t pixels) {
     Carver c(ws, 256);
     MvWorkspace w;
-    w.nvw = (nv + 63) / 64;
-    w.nfw = (nf + 63) / 64;
     w.hdr = c.take<MvHeader>(1);
-    w.seen = c.take<unsigned long long>(w.nfw);
-    w.fwords = c.take<unsigned long long>(w.nfw);
-    w.fprefix = c.take<uint32_t>(w.nfw);
-    w.vwords = c.take<unsigned long long>(w.nvw);
-    w.vprefix = c.take<uint32_t>(w.nvw);
+    w.seen = c.take<unsigned long long>((nf + 63) / 64);
+    w.bits = take_subset_bits(c, nv, nf, true);
     w.raster.hdr = c.take<MrHeader>(1);
     w.raster.vtx = c.take<MrVertex>(nv);
     w.raster.queue = c.take<int32_t>(nf);
@@ -451,17 +397,11 @@ static MvWorkspace mv_carve(const void* ws, int64_t nv, int64_t nf, int64_t pixe
 
 static bool mr_side_ok(int64_t n) { return n >= 1 && n <= MR_MAX_SIDE; }
 
-// What nm_mesh_rasterize and the nm_mesh_visibility_* entries ask of a view and of a mesh, in one place: 0 or 2
+// What nm_mesh_rasterize and the nm_mesh_visibility_* entries ask of a view, in one place: 0 or 2
 static int mr_check_view(const nm_view* view) {
     NM_REQUIRE(view->use_ndc == 0, "mesh raster: an NDC view has no pinhole projection to rasterise with");
     NM_REQUIRE(mr_side_ok(view->height) && mr_side_ok(view->width), "mesh raster: height and width must be in [1, 16384]");
     NM_REQUIRE(view->focal > 0.0 && view->focal - view->focal == 0.0, "mesh raster: focal must be finite and > 0");
-    return 0;
-}
-
-static int mr_check_mesh(int64_t num_vertices, int64_t num_faces) {
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces), "mesh raster: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh raster: faces without vertices");
     return 0;
 }
 
@@ -517,7 +457,7 @@ int nm_mesh_rasterize(const nm_view* view, const float* d_verts, int64_t num_ver
                       float near, int32_t flags, int32_t large_threshold, void* d_workspace, int32_t* d_face_id, float* d_depth,
                       float* d_bary, int64_t* d_counts, void* stream) {
     NM_REQUIRE(view != nullptr, "bad argument");
-    if (mr_check_view(view) || mr_check_mesh(num_vertices, num_faces) || mr_check_limits(near, large_threshold)) return 2;
+    if (mr_check_view(view) || require_mesh("mesh raster", num_vertices, num_faces) || mr_check_limits(near, large_threshold)) return 2;
     NM_REQUIRE((flags & ~NM_MESH_RASTER_CULL_BACK) == 0, "mesh raster: unknown flags");
     NM_REQUIRE(d_workspace && d_face_id && d_depth && d_bary && d_counts && (num_vertices == 0 || d_verts) &&
                (num_faces == 0 || d_faces), "bad argument");
@@ -546,11 +486,11 @@ int nm_mesh_visibility_views(const nm_view* views, int64_t num_views, const floa
     NM_REQUIRE(num_views == 0 || (views && d_new_faces), "bad argument");
     for (int64_t k = 0; k < num_views; ++k)
         if (mr_check_view(views + k)) return 2;
-    if (mr_check_mesh(num_vertices, num_faces) || mr_check_limits(near, large_threshold)) return 2;
+    if (require_mesh("mesh raster", num_vertices, num_faces) || mr_check_limits(near, large_threshold)) return 2;
     NM_REQUIRE(d_workspace && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces), "bad argument");
     const MvWorkspace w = mv_carve(d_workspace, num_vertices, num_faces, 0);      // the visibility words come last
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (clear && w.nfw) NM_HIP_CHECK(hipMemsetAsync(w.seen, 0, sizeof(unsigned long long) * (size_t)w.nfw, s));
+    if (clear && w.bits.nfw) NM_HIP_CHECK(hipMemsetAsync(w.seen, 0, sizeof(unsigned long long) * (size_t)w.bits.nfw, s));
     if (num_views) NM_HIP_CHECK(hipMemsetAsync(d_new_faces, 0, sizeof(int64_t) * (size_t)num_views, s));
     for (int64_t k = 0; k < num_views; ++k) {
         unsigned long long* counts = d_reject_counts ? reinterpret_cast<unsigned long long*>(d_reject_counts) + k * NM_MESH_RASTER_COUNTS
@@ -569,7 +509,7 @@ int nm_mesh_visibility_views(const nm_view* views, int64_t num_views, const floa
 int nm_mesh_visibility_select(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t rings, void* d_workspace,
                               int64_t* h_vertices_kept, int64_t* h_faces_kept, int64_t* h_faces_seen, int64_t* h_bad_faces,
                               void* stream) {
-    if (mr_check_mesh(num_vertices, num_faces)) return 2;
+    if (require_mesh("mesh raster", num_vertices, num_faces)) return 2;
     NM_REQUIRE(rings >= 0 && rings <= NM_MESH_VISIBILITY_MAX_RINGS, "mesh visibility: rings must be in [0, 1024]");
     NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces) && h_vertices_kept && h_faces_kept && h_faces_seen && h_bad_faces,
                "bad argument");
@@ -577,22 +517,22 @@ int nm_mesh_visibility_select(const int32_t* d_faces, int64_t num_faces, int64_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
     const unsigned fgrid = launch_grid(num_faces);
+    const SubsetBits& b = w.bits;
     NM_HIP_CHECK(hipMemsetAsync(w.hdr, 0, sizeof(MvHeader), s));
     if (num_faces) {
-        hipLaunchKernelGGL(mv_begin, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.seen, w.fwords, w.hdr);
+        hipLaunchKernelGGL(mv_begin, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.seen, b.fwords, w.hdr);
         NM_HIP_CHECK(hipGetLastError());
     }
     for (int r = 0; r <= rings && num_faces; ++r) {                  // the last round only leaves the final vertex bits
-        NM_HIP_CHECK(hipMemsetAsync(w.vwords, 0, sizeof(unsigned long long) * (size_t)w.nvw, s));
-        hipLaunchKernelGGL(mv_mark_corners, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.fwords, w.vwords);
+        NM_HIP_CHECK(hipMemsetAsync(b.vwords, 0, sizeof(unsigned long long) * (size_t)b.nvw, s));
+        hipLaunchKernelGGL(mv_mark_corners, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, b.fwords, b.vwords);
         NM_HIP_CHECK(hipGetLastError());
         if (r == rings) break;
-        hipLaunchKernelGGL(mv_grow, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.vwords, w.fwords);
+        hipLaunchKernelGGL(mv_grow, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, b.vwords, b.fwords);
         NM_HIP_CHECK(hipGetLastError());
     }
-    if (!num_faces && w.nvw) NM_HIP_CHECK(hipMemsetAsync(w.vwords, 0, sizeof(unsigned long long) * (size_t)w.nvw, s));
-    hipLaunchKernelGGL(mv_scan, dim3(2), dim3(SCAN_THREADS), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
-    NM_HIP_CHECK(hipGetLastError());
+    if (!num_faces && b.nvw) NM_HIP_CHECK(hipMemsetAsync(b.vwords, 0, sizeof(unsigned long long) * (size_t)b.nvw, s));
+    if (const int rc = subset_scan(b, w.hdr->totals, s)) return rc;
     MvHeader h;
     NM_HIP_CHECK(hipMemcpyAsync(&h, w.hdr, sizeof(MvHeader), hipMemcpyDeviceToHost, s));
     NM_HIP_CHECK(hipStreamSynchronize(s));
@@ -607,27 +547,15 @@ int nm_mesh_visibility_compact(const void* d_workspace, const int32_t* d_faces, 
                                const float* d_verts, const float* d_normals, int64_t vertices_kept, int64_t faces_kept,
                                float* d_out_verts, int32_t* d_out_faces, float* d_out_normals, int32_t* d_out_face_index,
                                void* stream) {
-    if (mr_check_mesh(num_vertices, num_faces)) return 2;
-    NM_REQUIRE(vertices_kept >= 0 && vertices_kept <= num_vertices && faces_kept >= 0 && faces_kept <= num_faces,
-               "mesh visibility: the kept counts must lie within the mesh's");
-    NM_REQUIRE(d_workspace && (num_faces == 0 || d_faces), "bad argument");
-    NM_REQUIRE(vertices_kept == 0 || ((!d_verts || d_out_verts) && (!d_normals || d_out_normals)),
-               "mesh visibility: an input array without its output");
-    NM_REQUIRE(faces_kept == 0 || d_out_faces, "mesh visibility: null face output");
+    if (require_mesh("mesh raster", num_vertices, num_faces)) return 2;
+    NM_REQUIRE_COMPACT_OUTPUTS("mesh visibility", d_workspace && (num_faces == 0 || d_faces),
+                               (!d_verts || d_out_verts) && (!d_normals || d_out_normals));
     const MvWorkspace w = mv_carve(d_workspace, num_vertices, num_faces, 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
-    if (vertices_kept && (d_verts || d_normals)) {
-        hipLaunchKernelGGL(mv_compact_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, vertices_kept,
-                           w.vwords, w.vprefix, d_out_verts, d_out_normals);
-        NM_HIP_CHECK(hipGetLastError());
-    }
-    if (faces_kept) {
-        hipLaunchKernelGGL(mv_compact_faces, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_faces, num_faces, nv, faces_kept, w.fwords,
-                           w.fprefix, w.vwords, w.vprefix, d_out_faces, d_out_face_index);
-        NM_HIP_CHECK(hipGetLastError());
-    }
-    return 0;
+    const SubsetRows rows{d_verts, d_normals, nullptr, nullptr, d_out_verts, d_out_normals, nullptr, nullptr};
+    if (const int rc = subset_compact_vertices(rows, nv, vertices_kept, w.bits, s)) return rc;
+    return subset_compact_faces(d_faces, num_faces, nv, faces_kept, w.bits, nullptr, d_out_faces, d_out_face_index, s);
 }
 
 int nm_mesh_interpolate(const int32_t* d_face_id, const float* d_bary, int64_t num_pixels, const int32_t* d_faces, int64_t num_faces,
@@ -635,8 +563,7 @@ int nm_mesh_interpolate(const int32_t* d_face_id, const float* d_bary, int64_t n
                         void* stream) {
     NM_REQUIRE(channels >= 1 && channels <= NM_MESH_INTERPOLATE_MAX_CHANNELS, "mesh interpolate: channels must be in [1, 16]");
     NM_REQUIRE(num_pixels >= 0 && num_pixels <= (int64_t)MR_MAX_SIDE * MR_MAX_SIDE, "mesh interpolate: pixels must be in [0, 2^28]");
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces), "mesh raster: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh raster: faces without vertices");
+    if (require_mesh("mesh raster", num_vertices, num_faces)) return 2;
     NM_REQUIRE(d_background && (num_pixels == 0 || (d_face_id && d_bary && d_out)) && (num_faces == 0 || d_faces) &&
                (num_vertices == 0 || d_attributes), "bad argument");
     if (num_pixels == 0) return 0;

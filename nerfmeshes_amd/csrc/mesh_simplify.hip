@@ -34,9 +34,10 @@
 //                       no key to store and no bound on V.  Same rules: agent-scope atomics only, bounded walks, no waiting.
 //   4. ms_mark          a face stays when it is the index its slot ended with: of duplicates the smallest.  Keep bits leave
 //                       each wave as one ballot word; the representatives of kept faces' corners get their bit by atomicOr.
-//   5. ms_scan / ms_emit_*   the ordered compaction of compact.h over both sets of words: kept faces in input order with
-//                       their corners in their own order; kept clusters by ascending representative (numpy: new =
-//                       cumsum(used) - 1), which is marching cubes' scan order.  A cluster of ONE member emits that member's
+//   5. subset_scan / ms_emit_vertices / subset_compact_faces   the ordered compaction of compact.h over both sets of words
+//                       (the faces through rep[]: mesh_subset.hip): kept faces in input order with their corners in their own
+//                       order; kept clusters by ascending representative (numpy: new = cumsum(used) - 1), which is marching
+//                       cubes' scan order.  A cluster of ONE member emits that member's
 //                       rows bit for bit; a larger one
 //                         p = (float)((double) lo + (double) cell * ((double) S / ((double) n * 2^30)))
 //                         normal = s / sqrt((sx sx + sy sy) + sz sz) with s = (float) S per component, or the representative's
@@ -47,7 +48,6 @@
 
 namespace nm {
 
-constexpr unsigned long long MS_EMPTY = ~0ull;
 constexpr float MS_CELLS = 2097152.0f;           // 2^21 cells per axis
 constexpr double MS_QUANTUM = 1073741824.0;      // 2^30 quanta per cell edge / per unit of a normal component
 constexpr double MS_QMAX = 2147483648.0;         // 2^31: the largest |q|
@@ -71,8 +71,6 @@ struct MsHeader {
 
 struct MsGrid { float o[3]; float cell; };
 
-#define MS_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
 // cell of a vertex -> false: bad
 __device__ __forceinline__ bool ms_cell(const MsGrid& g, const float (&x)[3], float (&c)[3], unsigned long long& key) {
     bool ok = true;
@@ -92,23 +90,11 @@ __device__ __forceinline__ long long ms_quantise(float t) {
     return (long long)rint(s);
 }
 
-// The slot of `key`, claimed if no vertex of that cell came before.  At most V keys live in >= 2 V slots, so an empty slot
-// always ends the walk; `cap` iterations bound it all the same (-> cap: not placed).
-__device__ __forceinline__ uint64_t ms_find_or_insert(MsSlot* table, uint64_t cap, unsigned long long key) {
-    uint64_t s = mix64(key) & (cap - 1);
-    for (uint64_t i = 0; i < cap; ++i, s = (s + 1) & (cap - 1)) {
-        unsigned long long k = __hip_atomic_load(&table[s].key, MS_RELAXED_AGENT);
-        if (k == MS_EMPTY && __hip_atomic_compare_exchange_strong(&table[s].key, &k, key, __ATOMIC_RELAXED, MS_RELAXED_AGENT)) return s;
-        if (k == key) return s;                  // found, or the thread that beat us to the slot brought the same cell
-    }
-    return cap;
-}
-
 __global__ __launch_bounds__(256) void ms_init(MsSlot* __restrict__ table, uint64_t cap, int* __restrict__ ftab, uint64_t fcap,
                                                unsigned long long* __restrict__ vwords, int64_t nvw, MsHeader* hdr) {
     const uint64_t stride = (uint64_t)gridDim.x * 256, first = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     MsSlot empty;
-    empty.key = MS_EMPTY;
+    empty.key = EMPTY_KEY;
 #pragma unroll
     for (int k = 0; k < 3; ++k) empty.psum[k] = empty.nsum[k] = 0;
     empty.rep = 0x7fffffff;
@@ -120,7 +106,7 @@ __global__ __launch_bounds__(256) void ms_init(MsSlot* __restrict__ table, uint6
 }
 
 __device__ __forceinline__ void ms_add(long long* p, long long q) {
-    if (q) __hip_atomic_fetch_add(p, q, MS_RELAXED_AGENT);
+    if (q) __hip_atomic_fetch_add(p, q, NM_RELAXED_AGENT);
 }
 
 // One thread per vertex, whole waves (the aggregation votes).  slot_of[v] = v's slot; rep[v] = -1 marks a bad vertex.
@@ -141,7 +127,8 @@ __global__ __launch_bounds__(256) void ms_insert(const float* __restrict__ verts
         unsigned long long key;
         todo = ms_cell(g, x, c, key);
         if (todo) {
-            s = ms_find_or_insert(table, cap, key);
+            bool claimed;                        // whoever claims the slot: at most V cells live in >= 2 V slots
+            s = find_or_insert(table, cap, key, claimed);
             todo = s < cap;
         }
         slot_of[v] = todo ? (uint32_t)s : 0u;
@@ -171,8 +158,8 @@ __global__ __launch_bounds__(256) void ms_insert(const float* __restrict__ verts
     if (!AGGREGATE) {
         if (todo) {
             MsSlot* slot = table + s;
-            __hip_atomic_fetch_min(&slot->rep, (int)v, MS_RELAXED_AGENT);
-            __hip_atomic_fetch_add(&slot->count, 1u, MS_RELAXED_AGENT);
+            __hip_atomic_fetch_min(&slot->rep, (int)v, NM_RELAXED_AGENT);
+            __hip_atomic_fetch_add(&slot->count, 1u, NM_RELAXED_AGENT);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 ms_add(slot->psum + k, q[k]);
@@ -201,8 +188,8 @@ __global__ __launch_bounds__(256) void ms_insert(const float* __restrict__ verts
         }
         if (lane == leader) {                                        // the group's lowest lane: its smallest vertex index
             MsSlot* slot = table + want;
-            __hip_atomic_fetch_min(&slot->rep, (int)v, MS_RELAXED_AGENT);
-            __hip_atomic_fetch_add(&slot->count, members, MS_RELAXED_AGENT);
+            __hip_atomic_fetch_min(&slot->rep, (int)v, NM_RELAXED_AGENT);
+            __hip_atomic_fetch_add(&slot->count, members, NM_RELAXED_AGENT);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 ms_add(slot->psum + k, r[k]);
@@ -257,8 +244,8 @@ __global__ __launch_bounds__(256) void ms_insert_faces(const int32_t* __restrict
     uint64_t s = mix64(mix64(((unsigned long long)(unsigned)t[0] << 32) | (unsigned)t[1]) ^ (unsigned long long)(unsigned)t[2]) & (fcap - 1);
     uint32_t placed = 0u;                                            // a walk that ran out (it cannot: <= F triples in >= 2 F slots)
     for (uint64_t i = 0; i < fcap; ++i, s = (s + 1) & (fcap - 1)) {  // leaves slot 0 unowned by f: the face counts as a duplicate
-        int o = __hip_atomic_load(ftab + s, MS_RELAXED_AGENT);
-        if (o == -1 && __hip_atomic_compare_exchange_strong(ftab + s, &o, (int)f, __ATOMIC_RELAXED, MS_RELAXED_AGENT)) {
+        int o = __hip_atomic_load(ftab + s, NM_RELAXED_AGENT);
+        if (o == -1 && __hip_atomic_compare_exchange_strong(ftab + s, &o, (int)f, __ATOMIC_RELAXED, NM_RELAXED_AGENT)) {
             placed = (uint32_t)s;
             break;
         }
@@ -266,7 +253,7 @@ __global__ __launch_bounds__(256) void ms_insert_faces(const int32_t* __restrict
         if ((int64_t)o < 0 || (int64_t)o >= nf || !ms_corners(faces, o, nv, rep, ro)) continue;
         ms_canonical(ro, to);
         if (to[0] == t[0] && to[1] == t[1] && to[2] == t[2]) {
-            __hip_atomic_fetch_min(ftab + s, (int)f, MS_RELAXED_AGENT);
+            __hip_atomic_fetch_min(ftab + s, (int)f, NM_RELAXED_AGENT);
             placed = (uint32_t)s;
             break;
         }
@@ -285,27 +272,17 @@ __global__ __launch_bounds__(256) void ms_mark(const int32_t* __restrict__ faces
     const bool flat = ok && ms_degenerate(r);
     const bool live = ok && !flat;
     const bool keep = live && ftab[fslot[f]] == (int)f;
-    const unsigned long long word = __ballot(keep), bad = __ballot(in && !ok), deg = __ballot(flat), dup = __ballot(live && !keep);
+    store_keep_word(fwords, f, nf, keep);
+    const unsigned long long bad = __ballot(in && !ok), deg = __ballot(flat), dup = __ballot(live && !keep);
     if (keep) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) atomicOr(vwords + (r[k] >> 6), 1ull << (r[k] & 63));
     }
-    if ((threadIdx.x & 63) == 0 && (f >> 6) < (nf + 63) / 64) {
-        fwords[f >> 6] = word;
+    if ((threadIdx.x & 63) == 0) {                                   // a wave beyond the last word has no face to count
         if (bad) atomicAdd(&hdr->bad_faces, (unsigned long long)__popcll(bad));
         if (deg) atomicAdd(&hdr->degenerate, (unsigned long long)__popcll(deg));
         if (dup) atomicAdd(&hdr->duplicate, (unsigned long long)__popcll(dup));
     }
-}
-
-// workgroup 0 the vertex words, workgroup 1 the face words (compact.h)
-__global__ __launch_bounds__(SCAN_THREADS) void ms_scan(const unsigned long long* __restrict__ vwords, int64_t nvw,
-                                                        uint32_t* __restrict__ vprefix,
-                                                        const unsigned long long* __restrict__ fwords, int64_t nfw,
-                                                        uint32_t* __restrict__ fprefix, MsHeader* hdr) {
-    const bool f = blockIdx.x != 0;
-    const uint32_t kept = popcount_prefix_sums(f ? fwords : vwords, f ? nfw : nvw, f ? fprefix : vprefix);
-    if (threadIdx.x == 0) hdr->totals[blockIdx.x] = kept;
 }
 
 __global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict__ verts, const float* __restrict__ normals, int nv,
@@ -357,22 +334,6 @@ __global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict_
     out_normals[3 * dst + 2] = sz / len;
 }
 
-__global__ __launch_bounds__(256) void ms_emit_faces(const int32_t* __restrict__ faces, int64_t nf, int nv,
-                                                     const int* __restrict__ rep, const unsigned long long* __restrict__ fwords,
-                                                     const uint32_t* __restrict__ fprefix,
-                                                     const unsigned long long* __restrict__ vwords,
-                                                     const uint32_t* __restrict__ vprefix, int64_t capacity,
-                                                     int32_t* __restrict__ out_faces) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || !bit_test(fwords, f)) return;
-    int r[3];
-    if (!ms_corners(faces, f, nv, rep, r)) return;                   // such a face never has its bit set
-    const int64_t dst = bit_rank(fwords, fprefix, f);
-    if (dst >= capacity) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out_faces[3 * dst + k] = (int32_t)bit_rank(vwords, vprefix, r[k]);
-}
-
 // the smallest power of two >= 2 n (at least 64)
 static uint64_t ms_capacity(int64_t n) {
     uint64_t cap = 64;
@@ -387,12 +348,9 @@ struct MsWorkspace {
     int* rep;
     int* ftab;
     uint32_t* fslot;
-    unsigned long long* vwords;
-    uint32_t* vprefix;
-    unsigned long long* fwords;
-    uint32_t* fprefix;
+    SubsetBits bits;
     uint64_t cap, fcap;
-    int64_t nvw, nfw, bytes;
+    int64_t bytes;
 };
 
 static MsWorkspace ms_carve(const void* ws, int64_t nv, int64_t nf) {
@@ -400,31 +358,24 @@ static MsWorkspace ms_carve(const void* ws, int64_t nv, int64_t nf) {
     MsWorkspace w;
     w.cap = ms_capacity(nv);
     w.fcap = ms_capacity(nf);
-    w.nvw = (nv + 63) / 64;
-    w.nfw = (nf + 63) / 64;
     w.hdr = c.take<MsHeader>(1);
     w.table = c.take<MsSlot>((int64_t)w.cap);
     w.slot_of = c.take<uint32_t>(nv);
     w.rep = c.take<int>(nv);
     w.ftab = c.take<int>((int64_t)w.fcap);
     w.fslot = c.take<uint32_t>(nf);
-    w.vwords = c.take<unsigned long long>(w.nvw);
-    w.vprefix = c.take<uint32_t>(w.nvw);
-    w.fwords = c.take<unsigned long long>(w.nfw);
-    w.fprefix = c.take<uint32_t>(w.nfw);
+    w.bits = take_subset_bits(c, nv, nf);
     w.bytes = c.offset;
     return w;
 }
 
-static bool ms_finite(float x) { return x - x == 0.0f; }
+// compact.h's is_finite under the name that the grid requirements' texts carry (NM_REQUIRE quotes its condition)
+static bool ms_finite(float x) { return is_finite(x); }
 
 }  // namespace nm
 
 using namespace nm;
 
-#define MS_REQUIRE_MESH(nv, nf)                                                                                          \
-    NM_REQUIRE(mesh_size_ok(nv) && mesh_size_ok(nf), "mesh simplify: vertex and face counts must be in [0, 2^31 - 64)");  \
-    NM_REQUIRE(nf == 0 || nv > 0, "mesh simplify: faces without vertices")
 #define MS_REQUIRE_GRID(ox, oy, oz, cell)                                                                                \
     NM_REQUIRE(ms_finite(cell) && cell > 0.0f, "mesh simplify: the cell size must be finite and > 0");                   \
     NM_REQUIRE(ms_finite(ox) && ms_finite(oy) && ms_finite(oz), "mesh simplify: the origin must be finite")
@@ -439,7 +390,7 @@ int64_t nm_mesh_simplify_workspace_bytes(int64_t num_vertices, int64_t num_faces
 int nm_mesh_simplify_cluster(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
                              const float* d_normals, float origin_x, float origin_y, float origin_z, float cell, int32_t flags,
                              void* d_workspace, int64_t* h_counts, void* stream) {
-    MS_REQUIRE_MESH(num_vertices, num_faces);
+    if (require_mesh("mesh simplify", num_vertices, num_faces)) return 2;
     MS_REQUIRE_GRID(origin_x, origin_y, origin_z, cell);
     NM_REQUIRE((flags & ~NM_MESH_SIMPLIFY_AGGREGATE) == 0, "mesh simplify: unknown flags");
     NM_REQUIRE(d_workspace && h_counts && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces), "bad argument");
@@ -450,7 +401,7 @@ int nm_mesh_simplify_cluster(const float* d_verts, int64_t num_vertices, const i
     const unsigned vgrid = launch_grid(num_vertices), fgrid = launch_grid(num_faces);
     const uint64_t most = w.cap > w.fcap ? w.cap : w.fcap;
     hipLaunchKernelGGL(ms_init, dim3((unsigned)(most / 256 > 4096 ? 4096 : most / 256 ? most / 256 : 1)), dim3(256), 0, s, w.table,
-                       w.cap, w.ftab, w.fcap, w.vwords, w.nvw, w.hdr);
+                       w.cap, w.ftab, w.fcap, w.bits.vwords, w.bits.nvw, w.hdr);
     NM_HIP_CHECK(hipGetLastError());
     if (nv) {
         if (flags & NM_MESH_SIMPLIFY_AGGREGATE)
@@ -467,12 +418,11 @@ int nm_mesh_simplify_cluster(const float* d_verts, int64_t num_vertices, const i
         hipLaunchKernelGGL(ms_insert_faces, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.ftab, w.fcap,
                            w.fslot);
         NM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(ms_mark, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.ftab, w.fslot, w.fwords,
-                           w.vwords, w.hdr);
+        hipLaunchKernelGGL(ms_mark, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.ftab, w.fslot, w.bits.fwords,
+                           w.bits.vwords, w.hdr);
         NM_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(ms_scan, dim3(2), dim3(SCAN_THREADS), 0, s, w.vwords, w.nvw, w.vprefix, w.fwords, w.nfw, w.fprefix, w.hdr);
-    NM_HIP_CHECK(hipGetLastError());
+    if (const int rc = subset_scan(w.bits, w.hdr->totals, s)) return rc;
     MsHeader h;
     NM_HIP_CHECK(hipMemcpyAsync(&h, w.hdr, sizeof(MsHeader), hipMemcpyDeviceToHost, s));
     NM_HIP_CHECK(hipStreamSynchronize(s));
@@ -490,29 +440,20 @@ int nm_mesh_simplify_emit(const void* d_workspace, const float* d_verts, int64_t
                           int64_t num_faces, const float* d_normals, float origin_x, float origin_y, float origin_z, float cell,
                           int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
                           float* d_out_normals, void* stream) {
-    MS_REQUIRE_MESH(num_vertices, num_faces);
+    if (require_mesh("mesh simplify", num_vertices, num_faces)) return 2;
     MS_REQUIRE_GRID(origin_x, origin_y, origin_z, cell);
-    NM_REQUIRE(vertices_kept >= 0 && vertices_kept <= num_vertices && faces_kept >= 0 && faces_kept <= num_faces,
-               "mesh simplify: the kept counts must lie within the mesh's");
-    NM_REQUIRE(d_workspace && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces), "bad argument");
-    NM_REQUIRE(vertices_kept == 0 || (d_out_verts && (!d_normals || d_out_normals)), "mesh simplify: an input array without its output");
-    NM_REQUIRE(faces_kept == 0 || d_out_faces, "mesh simplify: null face output");
+    NM_REQUIRE_COMPACT_OUTPUTS("mesh simplify", d_workspace && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces),
+                               d_out_verts && (!d_normals || d_out_normals));
     const MsWorkspace w = ms_carve(d_workspace, num_vertices, num_faces);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nv = (int)num_vertices;
     const MsGrid g{{origin_x, origin_y, origin_z}, cell};
-    const unsigned vgrid = launch_grid(num_vertices), fgrid = launch_grid(num_faces);
     if (vertices_kept) {
-        hipLaunchKernelGGL(ms_emit_vertices, dim3(vgrid), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.slot_of,
-                           w.vwords, w.vprefix, vertices_kept, d_out_verts, d_out_normals);
+        hipLaunchKernelGGL(ms_emit_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table,
+                           w.slot_of, w.bits.vwords, w.bits.vprefix, vertices_kept, d_out_verts, d_out_normals);
         NM_HIP_CHECK(hipGetLastError());
     }
-    if (faces_kept) {
-        hipLaunchKernelGGL(ms_emit_faces, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, w.rep, w.fwords, w.fprefix,
-                           w.vwords, w.vprefix, faces_kept, d_out_faces);
-        NM_HIP_CHECK(hipGetLastError());
-    }
-    return 0;
+    return subset_compact_faces(d_faces, num_faces, nv, faces_kept, w.bits, w.rep, d_out_faces, nullptr, s);
 }
 
 }  // extern "C"

@@ -41,7 +41,6 @@
 
 namespace nm {
 
-constexpr unsigned long long SM_EMPTY = ~0ull;
 constexpr int SM_BITS = 40;                      // |q| <= 2^40 for every coordinate of the input mesh
 constexpr double SM_QMAX = 8796093022208.0;      // 2^43: the largest |q| of any later position
 constexpr double SM_SPLIT = 1048576.0;           // 2^20: q = (q >> 20) * 2^20 + (q & 0xFFFFF)
@@ -57,8 +56,6 @@ struct SmHeader {
 };
 static_assert(sizeof(SmHeader) == 128, "the header is two lines");
 
-#define SM_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
 // frexp's exponent of the positive float with these bits: the e with 2^(e-1) <= x < 2^e (0 for x = 0)
 __host__ __device__ inline int sm_exponent(unsigned bits) {
     const int field = (int)(bits >> 23) & 0xff;
@@ -72,7 +69,7 @@ __global__ __launch_bounds__(256) void sm_init(unsigned long long* __restrict__ 
                                                unsigned long long* __restrict__ bwords, int64_t nvw, SmHeader* hdr) {
     const uint64_t stride = (uint64_t)gridDim.x * 256, first = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     for (uint64_t i = first; i < cap; i += stride) {
-        keys[i] = SM_EMPTY;
+        keys[i] = EMPTY_KEY;
         counts[i] = 0u;
     }
     for (uint64_t i = first; i < (uint64_t)nv; i += stride) degree[i] = cursor[i] = 0u;
@@ -106,22 +103,6 @@ __global__ __launch_bounds__(256) void sm_vertices(const float* __restrict__ ver
     }
 }
 
-// The slot of `key`; claimed = this thread's compare-and-swap put the key there.  At most 3 F keys live in >= 6 F slots, so an
-// empty slot always ends the walk; `cap` iterations bound it all the same (-> cap: not placed).
-__device__ __forceinline__ uint64_t sm_find_or_insert(unsigned long long* keys, uint64_t cap, unsigned long long key, bool& claimed) {
-    uint64_t s = mix64(key) & (cap - 1);
-    claimed = false;
-    for (uint64_t i = 0; i < cap; ++i, s = (s + 1) & (cap - 1)) {
-        unsigned long long k = __hip_atomic_load(keys + s, SM_RELAXED_AGENT);
-        if (k == SM_EMPTY && __hip_atomic_compare_exchange_strong(keys + s, &k, key, __ATOMIC_RELAXED, SM_RELAXED_AGENT)) {
-            claimed = true;
-            return s;
-        }
-        if (k == key) return s;                  // found, or the thread that beat us to the slot brought the same edge
-    }
-    return cap;
-}
-
 __global__ __launch_bounds__(256) void sm_insert_edges(const int32_t* __restrict__ faces, int64_t nf, int nv, unsigned long long* keys,
                                                        unsigned* counts, uint64_t cap, unsigned* degree, SmHeader* hdr) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -134,13 +115,13 @@ __global__ __launch_bounds__(256) void sm_insert_edges(const int32_t* __restrict
         for (int k = 0; k < 3; ++k) {
             const int a = c[k], b = c[(k + 1) % 3];
             const unsigned lo = (unsigned)(a < b ? a : b), hi = (unsigned)(a < b ? b : a);
-            bool claimed;
-            const uint64_t s = sm_find_or_insert(keys, cap, ((unsigned long long)lo << 32) | hi, claimed);
+            bool claimed;                        // at most 3 F edges live in >= 6 F slots
+            const uint64_t s = find_or_insert(keys, cap, ((unsigned long long)lo << 32) | hi, claimed);
             if (s >= cap) continue;
-            __hip_atomic_fetch_add(counts + s, 1u, SM_RELAXED_AGENT);
+            __hip_atomic_fetch_add(counts + s, 1u, NM_RELAXED_AGENT);
             if (claimed) {
-                __hip_atomic_fetch_add(degree + lo, 1u, SM_RELAXED_AGENT);
-                __hip_atomic_fetch_add(degree + hi, 1u, SM_RELAXED_AGENT);
+                __hip_atomic_fetch_add(degree + lo, 1u, NM_RELAXED_AGENT);
+                __hip_atomic_fetch_add(degree + hi, 1u, NM_RELAXED_AGENT);
             }
         }
     }
@@ -158,7 +139,7 @@ __global__ __launch_bounds__(256) void sm_boundary(const unsigned long long* __r
     unsigned long long edges = 0, open = 0, fans = 0;
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += stride) {   // cap is a multiple of 64
         const unsigned long long key = keys[s];
-        const bool edge = key != SM_EMPTY;
+        const bool edge = key != EMPTY_KEY;
         const unsigned n = edge ? counts[s] : 0u;
         if (n == 1u) {
             const unsigned a = (unsigned)(key >> 32), b = (unsigned)key;
@@ -218,7 +199,7 @@ __global__ __launch_bounds__(256) void sm_fill(const unsigned long long* __restr
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += stride) {
         const unsigned long long key = keys[s];
-        if (key == SM_EMPTY) continue;
+        if (key == EMPTY_KEY) continue;
         const unsigned a = (unsigned)(key >> 32), b = (unsigned)key;
         const unsigned at_a = atomicAdd(cursor + a, 1u), at_b = atomicAdd(cursor + b, 1u);
         if (at_a < degree[a]) neighbours[offsets[a] + at_a] = (int32_t)b;       // never past a list's end
@@ -304,15 +285,15 @@ __global__ __launch_bounds__(256) void sn_faces(const float* __restrict__ verts,
     const float xx = n[0] * n[0], yy = n[1] * n[1], zz = n[2] * n[2];
     const float xy = xx + yy;
     const float len = sqrtf(xy + zz);
-    if (!(len > 0.0f) || !(len - len == 0.0f)) return;                          // zero, infinite or a NaN
+    if (!(len > 0.0f) || !is_finite(len)) return;                          // zero, infinite or a NaN
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float unit = n[k] / len;
         const long long q = (long long)rint((double)(unit * flip) * SM_QUANTUM);
         if (q) {
-            __hip_atomic_fetch_add(nsum + 3 * (int64_t)c[0] + k, q, SM_RELAXED_AGENT);
-            __hip_atomic_fetch_add(nsum + 3 * (int64_t)c[1] + k, q, SM_RELAXED_AGENT);
-            __hip_atomic_fetch_add(nsum + 3 * (int64_t)c[2] + k, q, SM_RELAXED_AGENT);
+            __hip_atomic_fetch_add(nsum + 3 * (int64_t)c[0] + k, q, NM_RELAXED_AGENT);
+            __hip_atomic_fetch_add(nsum + 3 * (int64_t)c[1] + k, q, NM_RELAXED_AGENT);
+            __hip_atomic_fetch_add(nsum + 3 * (int64_t)c[2] + k, q, NM_RELAXED_AGENT);
         }
     }
 }
@@ -383,10 +364,6 @@ static unsigned sm_slot_grid(uint64_t cap) { return launch_grid((int64_t)cap, GR
 
 using namespace nm;
 
-#define SM_REQUIRE_MESH(nv, nf)                                                                                        \
-    NM_REQUIRE(mesh_size_ok(nv) && mesh_size_ok(nf), "mesh smooth: vertex and face counts must be in [0, 2^31 - 64)");  \
-    NM_REQUIRE(nf == 0 || nv > 0, "mesh smooth: faces without vertices")
-
 extern "C" {
 
 int64_t nm_mesh_smooth_workspace_bytes(int64_t num_vertices, int64_t num_faces) {
@@ -396,7 +373,7 @@ int64_t nm_mesh_smooth_workspace_bytes(int64_t num_vertices, int64_t num_faces) 
 
 int nm_mesh_smooth_build(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces, void* d_workspace,
                          int64_t* h_counts, void* stream) {
-    SM_REQUIRE_MESH(num_vertices, num_faces);
+    if (require_mesh("mesh smooth", num_vertices, num_faces)) return 2;
     NM_REQUIRE(d_workspace && h_counts && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces), "bad argument");
     const SmWorkspace w = sm_carve(d_workspace, num_vertices, num_faces);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -470,7 +447,7 @@ int nm_mesh_smooth_run(const void* d_workspace, const float* d_verts, int64_t nu
 
 int nm_mesh_vertex_normals(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
                            const float* d_in_normals, int32_t flip, void* d_workspace, float* d_out_normals, void* stream) {
-    SM_REQUIRE_MESH(num_vertices, num_faces);
+    if (require_mesh("mesh smooth", num_vertices, num_faces)) return 2;
     NM_REQUIRE(flip == 1 || flip == -1, "mesh vertex normals: flip must be +1 or -1");
     NM_REQUIRE(d_workspace && (num_vertices == 0 || (d_verts && d_out_normals)) && (num_faces == 0 || d_faces), "bad argument");
     if (num_vertices == 0) return 0;

@@ -37,7 +37,6 @@ static bool mt_layout(int64_t faces, int n, MtLayout& l) {
     return false;
 }
 
-__device__ __forceinline__ bool mt_finite(float x) { return x - x == 0.0f; }
 
 // "lattice": index within the face of the point (i, j)
 __device__ __forceinline__ int mt_index(int n, int i, int j) { return j * (n + 1) - j * (j - 1) / 2 + i; }
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(256) void mt_samples(const float* __restrict__ vert
                     m[a] = (t0 + t1) + t2;
                 }
                 const float len = mt_length(m);
-                if (len > 0.0f && mt_finite(len)) {
+                if (len > 0.0f && is_finite(len)) {
                     have = true;
 #pragma unroll
                     for (int a = 0; a < 3; ++a) d[a] = -(m[a] / len);
@@ -114,7 +113,7 @@ __global__ __launch_bounds__(256) void mt_samples(const float* __restrict__ vert
                     g[a] = l - r;
                 }
                 const float len = mt_length(g);
-                if (len > 0.0f && mt_finite(len)) {
+                if (len > 0.0f && is_finite(len)) {
 #pragma unroll
                     for (int a = 0; a < 3; ++a) d[a] = (g[a] / len) * minus_flip;
                 } else {
@@ -198,7 +197,7 @@ __global__ __launch_bounds__(256) void mt_lookup(const int32_t* __restrict__ fac
             const float t0 = b0 * face_uv[6 * f + a], t1 = b1 * face_uv[6 * f + 2 + a], t2 = b2 * face_uv[6 * f + 4 + a];
             uv[a] = (t0 + t1) + t2;
         }
-        ok = mt_finite(uv[0]) && mt_finite(uv[1]);
+        ok = is_finite(uv[0]) && is_finite(uv[1]);
     }
     if (!ok) {
 #pragma unroll
@@ -254,8 +253,7 @@ int nm_mesh_texture_samples(const float* d_verts, int64_t num_vertices, const in
                             const float* d_normals, int32_t n, int32_t flip, int64_t first, int64_t count, float* d_positions,
                             float* d_directions, int64_t* d_counts, void* stream) {
     NM_REQUIRE(n >= 1 && n <= NM_MESH_TEXTURE_MAX_RES, "mesh texture: the resolution n must be in [1, 255]");
-    NM_REQUIRE(mesh_size_ok(num_vertices) && mesh_size_ok(num_faces), "mesh texture: vertex and face counts must be in [0, 2^31 - 64)");
-    NM_REQUIRE(num_faces == 0 || num_vertices > 0, "mesh texture: faces without vertices");
+    if (require_mesh("mesh texture", num_vertices, num_faces)) return 2;
     NM_REQUIRE(flip == 1 || flip == -1, "mesh texture: flip must be +1 or -1");
     NM_REQUIRE(first >= 0 && count >= 0 && first <= num_faces && count <= num_faces - first,
                "mesh texture: the window must lie inside [0, F]");

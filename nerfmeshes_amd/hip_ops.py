@@ -696,6 +696,34 @@ def _mesh_faces(faces, num_vertices):
     return faces.detach().contiguous(), nv, nf
 
 
+def _mesh_inputs(what, verts, faces, normals=None, values=None, keys=None):
+    """The opening of the wrapper `what`: the checked faces (_mesh_faces) and, on their device, contiguous, the (V,3) f32 vertices
+    and whichever of normals (V,3) f32, values (V,) f32 and keys (V,) i64 came, all of the same V.
+    -> (verts, faces, normals, values, keys, nv, nf, device)"""
+    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
+    dev = faces.device
+    verts = _dev32(verts, dev, "verts")
+    normals = _dev32(normals, dev, "normals") if normals is not None else None
+    values = _dev32(values, dev, "values") if values is not None else None
+    if keys is not None:
+        if keys.dtype is not torch.int64 or keys.device != dev:
+            raise ValueError("keys must be an int64 tensor on the faces' device")
+        keys = keys.contiguous()
+    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)) or \
+            (values is not None and values.shape != (nv,)) or (keys is not None and keys.shape != (nv,)):
+        raise ValueError(f"{what}: the per-vertex arrays disagree on the vertex count")
+    return verts, faces, normals, values, keys, nv, nf, dev
+
+
+def _mesh_subset_outputs(kv, kf, dev, normals=None, values=None, keys=None):
+    """What a _compact / _emit entry fills: kv vertices, kf faces and a row array for each per-vertex input that came.
+    -> (verts, faces, normals, values, keys)"""
+    return (torch.empty(kv, 3, dtype=torch.float32, device=dev), torch.empty(kf, 3, dtype=torch.int32, device=dev),
+            torch.empty(kv, 3, dtype=torch.float32, device=dev) if normals is not None else None,
+            torch.empty(kv, dtype=torch.float32, device=dev) if values is not None else None,
+            torch.empty(kv, dtype=torch.int64, device=dev) if keys is not None else None)
+
+
 def _mesh_check(lib, rc, what):
     """status of a nm_mesh_* entry: 2 (an argument the entry refuses) is the caller's ValueError, in the entry's own words"""
     if rc == 2:
@@ -746,28 +774,13 @@ def mesh_filter_components(verts, faces, normals, values=None, keys=None, min_fa
         raise ValueError("min_faces and keep_largest must be >= 0")
     if keep_largest > KEEP_LARGEST_MAX:
         raise ValueError(f"keep_largest is at most {KEEP_LARGEST_MAX}, got {keep_largest}")
-    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
-    dev = faces.device
-    verts = _dev32(verts, dev, "verts")
-    normals = _dev32(normals, dev, "normals")
-    values = _dev32(values, dev, "values") if values is not None else None
-    if keys is not None:
-        if keys.dtype is not torch.int64 or keys.device != dev:
-            raise ValueError("keys must be an int64 tensor on the faces' device")
-        keys = keys.contiguous()
-    if verts.shape != (nv, 3) or normals.shape != (nv, 3) or (values is not None and values.shape != (nv,)) or \
-            (keys is not None and keys.shape != (nv,)):
-        raise ValueError("mesh_filter_components: the per-vertex arrays disagree on the vertex count")
+    verts, faces, normals, values, keys, nv, nf, dev = _mesh_inputs("mesh_filter_components", verts, faces, normals, values, keys)
     labels, counts, ws = _mesh_components(lib, faces, nv, nf)
     kv, kf, comps, kept = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
     rc = lib.nm_mesh_components_select(_ptr(faces), nf, nv, _ptr(labels), _ptr(counts), min_faces, keep_largest, _ptr(ws),
                                        C.byref(kv), C.byref(kf), C.byref(comps), C.byref(kept), _stream())
     _mesh_check(lib, rc, "nm_mesh_components_select")
-    out_verts = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
-    out_normals = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
-    out_faces = torch.empty(kf.value, 3, dtype=torch.int32, device=dev)
-    out_values = torch.empty(kv.value, dtype=torch.float32, device=dev) if values is not None else None
-    out_keys = torch.empty(kv.value, dtype=torch.int64, device=dev) if keys is not None else None
+    out_verts, out_faces, out_normals, out_values, out_keys = _mesh_subset_outputs(kv.value, kf.value, dev, normals, values, keys)
     if kv.value:
         check(lib.nm_mesh_components_compact(_ptr(ws), _ptr(faces), nf, nv, _ptr(verts), _ptr(normals), _ptr(values), _ptr(keys),
                                              kv.value, kf.value, _ptr(out_verts), _ptr(out_faces), _ptr(out_normals),
@@ -797,12 +810,7 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     cell = float(np.float32(cell))
     if not (np.isfinite(cell) and cell > 0):
         raise ValueError(f"mesh_simplify: the cell size must be finite and > 0, got {cell}")
-    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
-    dev = faces.device
-    verts = _dev32(verts, dev, "verts")
-    normals = _dev32(normals, dev, "normals") if normals is not None else None
-    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)):
-        raise ValueError("mesh_simplify: the per-vertex arrays disagree on the vertex count")
+    verts, faces, normals, _, _, nv, nf, dev = _mesh_inputs("mesh_simplify", verts, faces, normals)
     if origin is None:
         # the minimum of the finite coordinates: a NaN or infinite vertex is reported below with its count, not as a bad origin
         low = torch.where(torch.isfinite(verts), verts, torch.full_like(verts, float("inf"))).min(dim=0).values if nv else None
@@ -821,9 +829,7 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
         raise ValueError(f"mesh simplify: {bad_v} vertices have a non-finite coordinate or a cell index outside [0, {SIMPLIFY_CELLS})")
     if bad_f:
         raise ValueError(f"mesh simplify: {bad_f} faces have a vertex index outside [0, {nv})")
-    out_verts = torch.empty(kv, 3, dtype=torch.float32, device=dev)
-    out_faces = torch.empty(kf, 3, dtype=torch.int32, device=dev)
-    out_normals = torch.empty(kv, 3, dtype=torch.float32, device=dev) if normals is not None else None
+    out_verts, out_faces, out_normals, _, _ = _mesh_subset_outputs(kv, kf, dev, normals)
     if kv:
         check(lib.nm_mesh_simplify_emit(_ptr(ws), _ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin, cell, kv, kf,
                                         _ptr(out_verts), _ptr(out_faces), _ptr(out_normals), _stream()), "nm_mesh_simplify_emit")
@@ -858,12 +864,7 @@ def mesh_smooth(verts, faces, normals=None, iterations=10, lam=0.5, mu=-0.53, fr
         raise ValueError(f"mesh_smooth: mu must be in [-1, 0], got {mu}")
     if flip not in (None, 1, -1):
         raise ValueError(f"mesh_smooth: flip must be +1 or -1, got {flip}")
-    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
-    dev = faces.device
-    verts = _dev32(verts, dev, "verts")
-    normals = _dev32(normals, dev, "normals") if normals is not None else None
-    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)):
-        raise ValueError("mesh_smooth: the per-vertex arrays disagree on the vertex count")
+    verts, faces, normals, _, _, nv, nf, dev = _mesh_inputs("mesh_smooth", verts, faces, normals)
     ws = _mesh_workspace(int(lib.nm_mesh_smooth_workspace_bytes(nv, nf)), "mesh smooth", nv, nf, dev)
     counts = (C.c_int64 * 9)()
     _mesh_check(lib, lib.nm_mesh_smooth_build(_ptr(verts), nv, _ptr(faces), nf, _ptr(ws), counts, _stream()), "nm_mesh_smooth_build")
@@ -956,12 +957,7 @@ def mesh_cull_hidden(verts, faces, normals, views, near, rings=1, large_threshol
     rings = int(rings)
     if not 0 <= rings <= VISIBILITY_MAX_RINGS:
         raise ValueError(f"mesh_cull_hidden: rings must be in [0, {VISIBILITY_MAX_RINGS}], got {rings}")
-    faces, nv, nf = _mesh_faces(faces, verts.shape[0])
-    dev = faces.device
-    verts = _dev32(verts, dev, "verts")
-    normals = _dev32(normals, dev, "normals") if normals is not None else None
-    if verts.shape != (nv, 3) or (normals is not None and normals.shape != (nv, 3)):
-        raise ValueError("mesh_cull_hidden: the per-vertex arrays disagree on the vertex count")
+    verts, faces, normals, _, _, nv, nf, dev = _mesh_inputs("mesh_cull_hidden", verts, faces, normals)
     views = list(views)
     array = (_lib.View * max(len(views), 1))(*views)
     height, width = (max(int(v.height) for v in views), max(int(v.width) for v in views)) if views else (1, 1)
@@ -975,9 +971,7 @@ def mesh_cull_hidden(verts, faces, normals, views, near, rings=1, large_threshol
     rc = lib.nm_mesh_visibility_select(_ptr(faces), nf, nv, rings, _ptr(ws), C.byref(kv), C.byref(kf), C.byref(seen), C.byref(bad),
                                        _stream())
     _mesh_check(lib, rc, "nm_mesh_visibility_select")
-    out_verts = torch.empty(kv.value, 3, dtype=torch.float32, device=dev)
-    out_normals = torch.empty(kv.value, 3, dtype=torch.float32, device=dev) if normals is not None else None
-    out_faces = torch.empty(kf.value, 3, dtype=torch.int32, device=dev)
+    out_verts, out_faces, out_normals, _, _ = _mesh_subset_outputs(kv.value, kf.value, dev, normals)
     face_index = torch.empty(kf.value, dtype=torch.int32, device=dev)
     if kv.value:
         check(lib.nm_mesh_visibility_compact(_ptr(ws), _ptr(faces), nf, nv, _ptr(verts), _ptr(normals), kv.value, kf.value,

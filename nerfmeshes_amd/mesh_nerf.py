@@ -20,6 +20,7 @@ import argparse
 import json
 import math
 import os
+import typing
 
 import torch
 
@@ -393,115 +394,140 @@ def chamfer_to_target(vertices, triangles, args, device):
     return report
 
 
+class Feature(typing.NamedTuple):
+    """One optional addition to the export, as data: what export_marching_cubes checks before anything is read or written, and
+    for a geometry stage what postprocess calls."""
+    what: str                   # the options' names, as the --route script refusal lists them
+    options: dict               # option -> default; a namespace without the option has the default
+    on: typing.Callable         # o -> switched on, with o = the options' values
+    valid: typing.Callable = lambda o: True     # o -> every option is in range
+    invalid: typing.Callable = None             # o -> the ValueError's text when not
+    any_option: bool = False    # refused and range-checked as soon as ANY option differs from its default, not only when on
+    script_has: str = "has no such step"        # what the reference's script has instead
+    run: typing.Callable = None                 # a geometry stage: (vertices, triangles, normals, o, args) -> the three
+
+    def values(self, args):
+        return {name: getattr(args, name, default) for name, default in self.options.items()}
+
+    def checked(self, o):
+        return bool(self.on(o)) or (self.any_option and any(o[name] != default for name, default in self.options.items()))
+
+
+# The geometry stages run in this order (postprocess).  The component filter comes first: its thresholds count original
+# triangles, and a filter that leaves nothing raises before anything is written.  The cull comes next, on the full-resolution
+# geometry, so that the smoothing, the clustering, the appearance rays and the texture bake work on less.  Smoothing comes
+# before the clustering, which then averages smoothed positions and the recomputed normals.  All four come before
+# --target-mesh, the network normals and the appearance query, which see the final geometry and spend no ray on a dropped
+# vertex.  The stage functions are looked up on this module when they are called, so that a tool can replace one.
+FEATURES = {
+    "normals": Feature(
+        "--normals network", {"normals": "grid"}, on=lambda o: o["normals"] == "network",
+        script_has="only has the grid's normals"),
+    "components": Feature(
+        "--min-component-faces / --keep-largest", {"min_component_faces": 0, "keep_largest": 0},
+        on=lambda o: int(o["min_component_faces"]) or int(o["keep_largest"]),
+        valid=lambda o: int(o["min_component_faces"]) >= 0 and 0 <= int(o["keep_largest"]) <= hip_ops.KEEP_LARGEST_MAX,
+        invalid=lambda o: f"--min-component-faces must be >= 0 and --keep-largest in [0, {hip_ops.KEEP_LARGEST_MAX}]",
+        run=lambda v, t, n, o, args: filter_components(v, t, n, int(o["min_component_faces"]), int(o["keep_largest"]))),
+    "cull": Feature(
+        "--cull-hidden-views / --cull-size / --cull-rings / --cull-radius",
+        {"cull_hidden_views": 0, "cull_size": 0, "cull_rings": 1, "cull_radius": 3.0},
+        on=lambda o: int(o["cull_hidden_views"]), any_option=True,
+        valid=lambda o: (int(o["cull_hidden_views"]) >= 0 and 0 <= int(o["cull_size"]) <= CULL_MAX_SIZE
+                         and 0 <= int(o["cull_rings"]) <= hip_ops.VISIBILITY_MAX_RINGS
+                         and 1.0 < float(o["cull_radius"]) < float("inf")),
+        invalid=lambda o: (f"--cull-hidden-views must be >= 0, --cull-size in [0, {CULL_MAX_SIZE}], --cull-rings in "
+                           f"[0, {hip_ops.VISIBILITY_MAX_RINGS}] and --cull-radius finite and > 1"),
+        run=lambda v, t, n, o, args: cull_hidden(v, t, n, args)),
+    "smooth": Feature(
+        "--smooth-iters / --smooth-lambda / --smooth-mu / --smooth-boundary",
+        {"smooth_iters": 0, "smooth_lambda": 0.5, "smooth_mu": -0.53, "smooth_boundary": "fixed"},
+        on=lambda o: int(o["smooth_iters"]), any_option=True,
+        valid=lambda o: (0 <= int(o["smooth_iters"]) <= hip_ops.SMOOTH_MAX_ITERATIONS and 0.0 < o["smooth_lambda"] <= 1.0
+                         and -1.0 <= o["smooth_mu"] <= 0.0),
+        invalid=lambda o: (f"--smooth-iters must be in [0, {hip_ops.SMOOTH_MAX_ITERATIONS}], --smooth-lambda in (0, 1] and "
+                           "--smooth-mu in [-1, 0]"),
+        run=lambda v, t, n, o, args: smooth_mesh(v, t, n, args)),
+    "simplify": Feature(
+        "--simplify-cell", {"simplify_cell": 0.0}, on=lambda o: float(o["simplify_cell"]),
+        valid=lambda o: 0.0 < float(o["simplify_cell"]) < float("inf"),
+        invalid=lambda o: f"--simplify-cell must be finite and >= 0, got {float(o['simplify_cell'])}",
+        run=lambda v, t, n, o, args: simplify_mesh(v, t, n, float(o["simplify_cell"]), args)),
+    "target": Feature(
+        "--target-mesh", {"target_mesh": None, "chamfer_samples": 100000}, on=lambda o: o["target_mesh"],
+        valid=lambda o: int(o["chamfer_samples"]) >= 1,
+        invalid=lambda o: f"--chamfer-samples must be >= 1, got {o['chamfer_samples']}"),
+    "render": Feature(
+        "--render-views", {"render_views": 0, "render_size": 800}, on=lambda o: int(o["render_views"]),
+        valid=lambda o: int(o["render_views"]) >= 0 and 1 <= int(o["render_size"]) <= 16384,
+        invalid=lambda o: "--render-views must be >= 0 and --render-size in [1, 16384]"),
+    "texture": Feature(
+        "--texture-res", {"texture_res": 0}, on=lambda o: int(o["texture_res"]),
+        valid=lambda o: 1 <= int(o["texture_res"]) <= hip_ops.TEXTURE_MAX_RES,
+        invalid=lambda o: f"--texture-res must be in [0, {hip_ops.TEXTURE_MAX_RES}], got {int(o['texture_res'])}"),
+}
+
+
+def check_features(args):
+    """Every record of FEATURES against `args`: a feature whose options are set refuses --route script, then range-checks them
+    (ValueError).  -> the names of the features that are switched on."""
+    script = getattr(args, "route", "kernel") == "script"
+    on = set()
+    for name, feature in FEATURES.items():
+        o = feature.values(args)
+        if feature.checked(o):
+            if script:
+                verb = "have" if " / " in feature.what else "has"
+                raise ValueError(f"{feature.what} {verb} no --route script: the reference's script {feature.script_has}")
+            if not feature.valid(o):
+                raise ValueError(feature.invalid(o))
+        if feature.on(o):
+            on.add(name)
+    return on
+
+
+def postprocess(vertices, triangles, normals, args):
+    """The geometry stages of FEATURES that are switched on, in its order, on the mesh the geometry stage or the cache gave.
+    Under torch.distributed every rank runs every stage on the gathered mesh redundantly."""
+    for feature in FEATURES.values():
+        o = feature.values(args)
+        if feature.run is not None and feature.on(o):
+            vertices, triangles, normals = feature.run(vertices, triangles, normals, o, args)
+    return vertices, triangles, normals
+
+
 def export_marching_cubes(model, args, cfg, device):
     """mesh_nerf.py:131-201.  `--super-sampling N >= 1` refines the geometry (extract_geometry_with_super_sampling); the
-    appearance, the cache and the OBJ are the same steps as without it.  `--normals network` replaces the geometry stage's grid
-    normals by the network's (network_normals) before the appearance query and the OBJ; the cache keeps the grid normals.
-    `--min-component-faces` / `--keep-largest` drop whole connected components (filter_components) right after the geometry stage
-    or the cache load -- before the network normals and the appearance query, so no ray is spent on a dropped vertex; the cache
-    keeps the unfiltered geometry.  Under torch.distributed every rank filters the gathered mesh redundantly.
-    `--simplify-cell K` clusters the vertices (simplify_mesh) after that filter -- its thresholds count original triangles -- and
-    before `--target-mesh`, the network normals and the appearance query, which all see the final geometry; the cache keeps the
-    unsimplified mesh, and every rank simplifies redundantly.
-    `--smooth-iters N` smooths the full-resolution mesh (smooth_mesh) between the component filter and the clustering, which
-    then averages smoothed positions and the recomputed normals; the cache keeps the unsmoothed mesh, and every rank smooths
-    redundantly.
-    `--cull-hidden-views N` drops the faces that none of N cameras around the mesh sees (cull_hidden) right after the component
-    filter, on the full-resolution geometry: the smoothing, the clustering, the appearance rays and the texture bake then work on
-    less; the cache keeps the unculled mesh, and every rank culls redundantly.
+    appearance, the cache and the OBJ are the same steps as without it.  The optional additions are the records of FEATURES:
+    all are checked before anything is read or written, and the geometry stages among them run right after the geometry stage
+    or the cache load (postprocess).  The cache keeps the geometry as it was before them -- grid normals, unfiltered, unculled,
+    unsmoothed, unsimplified --, so that they can be tuned on it.
+    `--normals network` replaces the grid normals by the network's (network_normals) before the appearance query and the OBJ.
     `--texture-res N` bakes a texture atlas after the per-vertex appearance (bake_texture), which stays: the `v` lines keep
     their colours, so a viewer without textures still shows them; the OBJ gains `vt` lines, an .mtl and a .png."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
-    normals_mode = getattr(args, "normals", "grid")
-    if normals_mode == "network" and getattr(args, "route", "kernel") == "script":
-        raise ValueError("--normals network has no --route script: the reference's script only has the grid's normals")
-    min_faces, keep_largest = int(getattr(args, "min_component_faces", 0)), int(getattr(args, "keep_largest", 0))
-    if min_faces or keep_largest:
-        if getattr(args, "route", "kernel") == "script":
-            raise ValueError("--min-component-faces / --keep-largest have no --route script: the reference's script has no such step")
-        if min_faces < 0 or not 0 <= keep_largest <= hip_ops.KEEP_LARGEST_MAX:
-            raise ValueError(f"--min-component-faces must be >= 0 and --keep-largest in [0, {hip_ops.KEEP_LARGEST_MAX}]")
-    simplify_cell = float(getattr(args, "simplify_cell", 0.0))
-    if simplify_cell:
-        if getattr(args, "route", "kernel") == "script":
-            raise ValueError("--simplify-cell has no --route script: the reference's script has no such step")
-        if not 0.0 < simplify_cell < float("inf"):
-            raise ValueError(f"--simplify-cell must be finite and >= 0, got {simplify_cell}")
-    smooth_iters = int(getattr(args, "smooth_iters", 0))
-    if smooth_iters or any(getattr(args, name, default) != default for name, default in
-                           (("smooth_lambda", 0.5), ("smooth_mu", -0.53), ("smooth_boundary", "fixed"))):
-        if getattr(args, "route", "kernel") == "script":
-            raise ValueError("--smooth-iters / --smooth-lambda / --smooth-mu / --smooth-boundary have no --route script: the "
-                             "reference's script has no such step")
-        if not (0 <= smooth_iters <= hip_ops.SMOOTH_MAX_ITERATIONS and 0.0 < args.smooth_lambda <= 1.0
-                and -1.0 <= args.smooth_mu <= 0.0):
-            raise ValueError(f"--smooth-iters must be in [0, {hip_ops.SMOOTH_MAX_ITERATIONS}], --smooth-lambda in (0, 1] and "
-                             "--smooth-mu in [-1, 0]")
-    cull_views = int(getattr(args, "cull_hidden_views", 0))
-    if cull_views or any(getattr(args, name, default) != default for name, default in
-                         (("cull_size", 0), ("cull_rings", 1), ("cull_radius", 3.0))):
-        if getattr(args, "route", "kernel") == "script":
-            raise ValueError("--cull-hidden-views / --cull-size / --cull-rings / --cull-radius have no --route script: the "
-                             "reference's script has no such step")
-        if not (cull_views >= 0 and 0 <= int(args.cull_size) <= CULL_MAX_SIZE and 0 <= int(args.cull_rings) <= hip_ops.VISIBILITY_MAX_RINGS
-                and 1.0 < float(args.cull_radius) < float("inf")):
-            raise ValueError(f"--cull-hidden-views must be >= 0, --cull-size in [0, {CULL_MAX_SIZE}], --cull-rings in "
-                             f"[0, {hip_ops.VISIBILITY_MAX_RINGS}] and --cull-radius finite and > 1")
-    target_mesh = getattr(args, "target_mesh", None)
-    if target_mesh:
-        if getattr(args, "route", "kernel") == "script":
-            raise ValueError("--target-mesh has no --route script: the reference's script has no such step")
-        if int(args.chamfer_samples) < 1:
-            raise ValueError(f"--chamfer-samples must be >= 1, got {args.chamfer_samples}")
-    render_views = int(getattr(args, "render_views", 0))
-    if render_views:
-        if getattr(args, "route", "kernel") == "script":
-            raise ValueError("--render-views has no --route script: the reference's script has no such step")
-        if render_views < 0 or not 1 <= int(args.render_size) <= 16384:
-            raise ValueError("--render-views must be >= 0 and --render-size in [1, 16384]")
-    texture_res = int(getattr(args, "texture_res", 0))
-    if texture_res:
-        if getattr(args, "route", "kernel") == "script":
-            raise ValueError("--texture-res has no --route script: the reference's script has no such step")
-        if not 1 <= texture_res <= hip_ops.TEXTURE_MAX_RES:
-            raise ValueError(f"--texture-res must be in [0, {hip_ops.TEXTURE_MAX_RES}], got {texture_res}")
+    on = check_features(args)
     from . import dist as nd
     cache_path = os.path.join(args.save_dir, args.cache_name)
-    cached = os.path.exists(cache_path)
-    cache_new = args.use_cached_mesh and not cached
-    if args.use_cached_mesh and cached:
+    load = args.use_cached_mesh and os.path.exists(cache_path)
+    if load:
         print("Loading cached mesh geometry...")
         vertices, triangles, normals, density = torch.load(cache_path, weights_only=False)
-        vertices, triangles, normals = (torch.as_tensor(t).to(device) for t in (vertices, triangles, normals))
-        if min_faces or keep_largest:
-            vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
-        if cull_views:
-            vertices, triangles, normals = cull_hidden(vertices, triangles, normals, args)
-        if smooth_iters:
-            vertices, triangles, normals = smooth_mesh(vertices, triangles, normals, args)
-        if simplify_cell:
-            vertices, triangles, normals = simplify_mesh(vertices, triangles, normals, simplify_cell, args)
+        unprocessed = tuple(torch.as_tensor(t).to(device) for t in (vertices, triangles, normals))
     else:
         print("Generating mesh geometry...")
         vertices, triangles, normals, density = geometry(model, device, args)
-        unfiltered = vertices, triangles, normals          # what the cache keeps, so that the filter can be tuned on it
-        if min_faces or keep_largest:                      # first: a filter that leaves nothing raises before anything is written
-            vertices, triangles, normals = filter_components(vertices, triangles, normals, min_faces, keep_largest)
-        if cull_views:                                     # likewise, on the full-resolution geometry: the later stages work on less
-            vertices, triangles, normals = cull_hidden(vertices, triangles, normals, args)
-        if smooth_iters:
-            vertices, triangles, normals = smooth_mesh(vertices, triangles, normals, args)
-        if simplify_cell:                                  # likewise: no triangle left raises here
-            vertices, triangles, normals = simplify_mesh(vertices, triangles, normals, simplify_cell, args)
-        if cache_new or args.override_cache_mesh:
-            if nd.world()[1] > 1 and getattr(args, "gather", "triangles") == "triangles":
-                density = _assemble_grid_from_slabs(density, _nums(args.res), device)   # the cache holds the whole grid
-            if nd.world()[0] == 0:
-                torch.save(tuple(t.cpu() for t in unfiltered) + (
-                            density.cpu().numpy() if isinstance(density, torch.Tensor) else density,), cache_path)
-                print(f"Cached mesh geometry saved to {cache_path}")
+        unprocessed = vertices, triangles, normals         # what the cache keeps
+    vertices, triangles, normals = postprocess(*unprocessed, args)   # a stage that leaves nothing raises before anything is written
+    if not load and (args.use_cached_mesh or args.override_cache_mesh):
+        if nd.world()[1] > 1 and getattr(args, "gather", "triangles") == "triangles":
+            density = _assemble_grid_from_slabs(density, _nums(args.res), device)   # the cache holds the whole grid
+        if nd.world()[0] == 0:
+            torch.save(tuple(t.cpu() for t in unprocessed) + (
+                        density.cpu().numpy() if isinstance(density, torch.Tensor) else density,), cache_path)
+            print(f"Cached mesh geometry saved to {cache_path}")
 
-    if target_mesh:                                        # the geometry is final here: judge it before any ray is spent
+    if "target" in on:                                     # the geometry is final here: judge it before any ray is spent
         chamfer_to_target(vertices, triangles, args, device)
 
     # Appearance: one query per vertex.  Vertices are independent, so under torch.distributed every rank queries a
@@ -509,7 +535,7 @@ def export_marching_cubes(model, args, cfg, device):
     rank, world = nd.world()
     counts = [b - a for a, b in (nd.split_range(vertices.shape[0], r, world) for r in range(world))]
     lo, hi = nd.split_range(vertices.shape[0], rank, world)
-    if normals_mode == "network":
+    if "normals" in on:
         # the fp32 handle whatever --precision is (as the geometry); every rank its own vertex range, one ragged all-gather
         # (the fallback flag travels as a 4th column)
         own, kept = network_normals(model.get_model().hip("f32"), vertices[lo:hi], normals[lo:hi])
@@ -531,7 +557,7 @@ def export_marching_cubes(model, args, cfg, device):
     diffuse = query_appearance(model, args, targets, directions, device, chunk, to_host=script)
     diffuse = torch.cat(diffuse, dim=0) if diffuse else torch.empty(0, 3, dtype=torch.float32, device=device)
     diffuse = nd.all_gather_rows(diffuse.contiguous(), counts).cpu().numpy()
-    texture = bake_texture(model, vertices, triangles, normals, args, device, chunk) if texture_res else None
+    texture = bake_texture(model, vertices, triangles, normals, args, device, chunk) if "texture" in on else None
     if getattr(args, "precision", "f32") != "f32":
         model.set_precision("f32")
     path = os.path.join(args.save_dir, args.mesh_name)
@@ -539,7 +565,7 @@ def export_marching_cubes(model, args, cfg, device):
         export_obj(vertices.cpu(), triangles.cpu(), diffuse, normals.cpu(), path)
     elif rank == 0:
         export_obj_textured(vertices.cpu(), triangles.cpu(), diffuse, normals.cpu(), texture[0], texture[1], path)
-    if render_views:
+    if "render" in on:
         render_report(model, vertices, triangles, diffuse, args, cfg, device, texture=texture)
     return vertices, triangles, normals, diffuse
 

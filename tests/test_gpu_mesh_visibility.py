@@ -107,6 +107,37 @@ def test_small_bad_and_empty_inputs(ops):
         ops.mesh_cull_hidden(torch.rand(5, 3, device="cuda"), torch.zeros(0, 3, dtype=torch.int32, device="cuda"), None, [], 0.0)
 
 
+def folded_strip(nv=65539, shown=40):
+    """A triangle strip of nv - 2 faces over nv vertices (two per column) in the plane z = -1, seen by a camera at the origin
+    (focal 64 on 64 x 64 pixels: the image spans x, y in [-0.5, 0.5)): its first `shown` columns run left to right through the
+    upper half of the image, its last `shown` right to left through the lower half, and everything between lies off screen to
+    the right.  Columns are 1.28 pixels wide and 0.64 tall, across one pixel row, so of the faces in view some win a pixel centre and some
+    do not.
+    -> (verts, faces, camera)"""
+    j = np.arange(nv) // 2
+    last = j[-1] + 1 - shown
+    x = np.where(j < shown, -0.45 + 0.02 * j, np.where(j >= last, 0.45 - 0.02 * (j - last), 5.0 + 1e-4 * j))
+    y = 0.2 - 0.39 * np.clip((j - shown) / float(last - shown), 0.0, 1.0) + 0.01 * (np.arange(nv) % 2)
+    first = np.arange(nv - 2, dtype=np.int32)
+    pose = np.eye(4, dtype=F32)[None, :3]
+    return np.stack([x, y, np.full(nv, -1.0)], -1).astype(F32), np.stack([first, first + 1, first + 2], -1), (pose, 64, 64.0, F32(0.1))
+
+
+def test_compaction_at_the_chunk_boundary_of_the_scan(ops):
+    """65 537 faces over 65 539 vertices: 1025 words of face keep bits and as many of vertex bits, so the last face and the last
+    vertices sit in the first word of the second chunk of the one-workgroup scan (csrc/compact.h) and their rows out need the
+    carry that the first chunk hands over.  The strip's two ends are in view, so kept and dropped faces alternate in the first
+    words and in the last, and everything between is dropped."""
+    verts, faces, camera = folded_strip()
+    assert len(faces) == 65537 and len(verts) == 65539 and (len(faces) + 63) // 64 == 1025
+    want = MV.cull_hidden(verts, faces, None, *camera, 0)
+    _same(_device(ops, verts, faces, None, camera, 0), want, "folded strip")
+    kept, info = want[3], want[4]
+    assert kept[-1] == 65536 and want[1][-1].max() == info["vertices_kept"] - 1, "the last face and its vertices are rows out"
+    front, back = int((kept < 80).sum()), int((kept >= 65537 - 80).sum())    # 78 faces in view + the two that leave it
+    assert 8 < front < 70 and 8 < back < 70 and front + back == info["faces_kept"] == info["faces_seen"], "both ends, in part"
+
+
 def test_both_raster_paths_give_the_same_bytes_run_after_run(ops, shell, soup_case):
     for tag, case in (("shell", shell), ("soup", soup_case)):
         runs = [_device(ops, *case, 1, large_threshold=t) for t in (None, None, 0, 2 ** 30)]

@@ -150,6 +150,71 @@ def test_keep_largest_over_the_cap_is_rejected_before_anything_runs(tmp_path):
     assert not any(tmp_path.iterdir())
 
 
+NO_STEP = "no --route script: the reference's script has no such step"
+SMOOTH_OPTIONS = "--smooth-iters / --smooth-lambda / --smooth-mu / --smooth-boundary have " + NO_STEP
+CULL_OPTIONS = "--cull-hidden-views / --cull-size / --cull-rings / --cull-radius have " + NO_STEP
+
+
+# one option per record of mesh_nerf.FEATURES, and the two of the hidden-face filter that no other test sets on their own
+@pytest.mark.parametrize("option, text", [
+    (["--normals", "network"], "--normals network has no --route script: the reference's script only has the grid's normals"),
+    (["--keep-largest", "1"], "--min-component-faces / --keep-largest have " + NO_STEP),
+    (["--cull-hidden-views", "2"], CULL_OPTIONS), (["--cull-size", "512"], CULL_OPTIONS), (["--cull-radius", "2.5"], CULL_OPTIONS),
+    (["--smooth-mu", "-0.4"], SMOOTH_OPTIONS),
+    (["--simplify-cell", "2"], "--simplify-cell has " + NO_STEP),
+    (["--target-mesh", "t.obj"], "--target-mesh has " + NO_STEP),
+    (["--render-views", "2"], "--render-views has " + NO_STEP),
+    (["--texture-res", "4"], "--texture-res has " + NO_STEP)], ids=lambda x: x[0] if isinstance(x, list) else None)
+def test_route_script_rejects_every_feature_in_its_own_words(tmp_path, option, text):
+    from nerfmeshes_amd import mesh_nerf
+    args = mesh_nerf.build_parser().parse_args([*option, "--route", "script", "--save-dir", str(tmp_path)])
+    with pytest.raises(ValueError) as e:
+        mesh_nerf.export_marching_cubes(None, args, None, "cpu")
+    assert str(e.value) == text
+    assert not any(tmp_path.iterdir()), "rejected before anything is written"
+
+
+def test_a_namespace_without_the_newer_options_passes_the_checks():
+    import argparse
+    from nerfmeshes_amd import mesh_nerf
+    assert mesh_nerf.check_features(argparse.Namespace()) == set()
+    assert mesh_nerf.check_features(argparse.Namespace(route="script", min_component_faces=0)) == set()
+    assert mesh_nerf.check_features(argparse.Namespace(simplify_cell=2.0, normals="network")) == {"simplify", "normals"}
+    # smoothing's other options do not switch it on, but they are checked
+    assert mesh_nerf.check_features(argparse.Namespace(smooth_lambda=0.4)) == set()
+    with pytest.raises(ValueError, match="--smooth-lambda in"):
+        mesh_nerf.check_features(argparse.Namespace(smooth_lambda=1.5))
+
+
+@pytest.mark.parametrize("options, expected", [
+    (["--min-component-faces", "4", "--cull-hidden-views", "2", "--smooth-iters", "3", "--simplify-cell", "2"],
+     ["filter_components", "cull_hidden", "smooth_mesh", "simplify_mesh"]),
+    (["--simplify-cell", "2", "--keep-largest", "1", "--smooth-lambda", "0.4", "--cull-rings", "2"],
+     ["filter_components", "simplify_mesh"]),
+    ([], [])], ids=["all four", "two", "none"])
+def test_postprocess_runs_the_enabled_stages_in_order(monkeypatch, options, expected):
+    """the stubs are set on the module: postprocess must look the stage functions up when it calls them, as the timing tools
+    replace them the same way"""
+    from nerfmeshes_amd import mesh_nerf
+    calls = []
+
+    def stub(name):
+        def record(vertices, triangles, normals, *rest):
+            calls.append((name, vertices, rest))
+            return vertices + 1, triangles, normals
+        return record
+
+    for name in ("filter_components", "cull_hidden", "smooth_mesh", "simplify_mesh"):
+        monkeypatch.setattr(mesh_nerf, name, stub(name))
+    args = mesh_nerf.build_parser().parse_args(options)
+    assert mesh_nerf.postprocess(0, "t", "n", args) == (len(expected), "t", "n")
+    assert [c[0] for c in calls] == expected
+    assert [c[1] for c in calls] == list(range(len(expected))), "each stage gets what the one before returned"
+    for name, _, rest in calls:               # the signatures the stage functions have
+        assert rest == {"filter_components": (args.min_component_faces, args.keep_largest), "cull_hidden": (args,),
+                        "smooth_mesh": (args,), "simplify_mesh": (args.simplify_cell, args)}[name]
+
+
 def test_argument_errors_without_a_gpu():
     from nerfmeshes_amd import _lib, hip_ops
     lib = _lib.load()
