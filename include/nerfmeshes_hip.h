@@ -59,6 +59,8 @@ extern "C" {
  * --appearance).  Additions only. */
 /* 6, later: + nm_mesh_visibility_views (+ _workspace_bytes), _select, _compact: the faces no camera of a set sees are dropped
  * (mesh_nerf --cull-hidden-views).  Additions only. */
+/* 6, later: + nm_image_ssim: the structural similarity of two images, bit for bit a closed rule (eval_nerf --ssim, mesh_render
+ * --ssim, mesh_nerf --render-ssim).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -1088,6 +1090,45 @@ int nm_mesh_texture_lookup(const int32_t* d_face_id, const float* d_bary, int64_
 int nm_export_obj_textured(const float* h_vertices, int64_t num_vertices, const float* h_diffuse, int64_t num_diffuse,
                            const float* h_normals, int64_t num_normals, const int32_t* h_triangles, int64_t num_triangles,
                            const float* h_face_uv, const char* mtllib, const char* material, const char* path);
+
+/* ------------------------------------------------------------------------------------------
+ * Image SSIM (eval_nerf --ssim, mesh_render --ssim, mesh_nerf --render-ssim; DESIGN.md, "Image SSIM"): the structural
+ * similarity of Wang et al. 2004 as scikit-image's structural_similarity(gaussian_weights=True, use_sample_covariance=False,
+ * data_range=1) computes it on float images, as a closed rule that a numpy restatement (tests/image_ssim.py) reproduces bit
+ * for bit -- the map, the sums and the mean.  THE RULE:
+ *
+ *   inputs     two fp32 images a, b of shape (H, W, C), row 0 on top, channels interleaved; 11 <= H, W <= 16384, 1 <= C <= 4.
+ *              The data range is 1.0; nothing is clamped or quantised.
+ *   arithmetic fp64 throughout, every product, sum and difference rounded on its own (no fused multiply-add), IEEE division.
+ *   window     11 taps, sigma = 1.5, normalised -- these constants, not a call to exp:
+ *                w[0] = w[10] = 0x1.0d956b52a1d6cp-10    w[1] = w[9] = 0x1.f1fe01ae5a5b8p-8    w[2] = w[8] = 0x1.26eb175d83f67p-5
+ *                w[3] = w[7]  = 0x1.bff0fe8e98418p-4     w[4] = w[6] = 0x1.b43c3f52b19f2p-3    w[5]        = 0x1.106560aa892c0p-2
+ *   fields     per channel five fields f in {x, y, x x, y y, x y} with x = (double) a, y = (double) b.
+ *   filter     horizontal first, then vertical, over the valid positions only (no padding): the output is (H - 10, W - 10).
+ *              h[r][c] = w[0] f[r][c], then + w[k] f[r][c + k] for k = 1..10 in ascending order; v[r][c] likewise over
+ *              h[r + k][c].  This is scikit-image's own crop of the 5-pixel border.
+ *   pixel      with the five filtered values ux, uy, uxx, uyy, uxy: vx = uxx - ux ux, vy = uyy - uy uy, vxy = uxy - ux uy,
+ *              S = (((2 ux) uy + C1) (2 vxy + C2)) / (((ux ux + uy uy) + C1) ((vx + vy) + C2)),
+ *              C1 = 0.01 * 0.01 and C2 = 0.03 * 0.03 as fp64 products.
+ *   mean       per channel an int64 sum of llrint(S 2^32) (round half to even) over the finite S and an int64 count of the
+ *              non-finite S, which are left out of the sum: integer addition does not depend on the order of the workgroups.
+ *              ssim_c = sum_c / ((H - 10)(W - 10) 2^32), the correctly rounded quotient of the two integers; ssim = the mean
+ *              of the ssim_c, added in channel order and divided by C, or NaN if any non-finite S was counted.  At 16384^2
+ *              |sum_c| < 2^60; the fixed point moves the mean by at most 2^-33.  (|S| <= 1 up to rounding for every finite
+ *              input whose squares stay far below fp64's range; the rounding of an |S| >= 2^31 is not defined.)
+ *
+ * d_map: NULL or (H - 10, W - 10, C) fp64, which receives S.  d_sums: (C, 2) int64 on the DEVICE, [c][NM_IMAGE_SSIM_SUM] and
+ * [c][NM_IMAGE_SSIM_NONFINITE]; the call zeroes it on the stream in front of its one kernel.  Nothing allocates and nothing
+ * waits for the host.  Argument errors -- a null d_a, d_b or d_sums, a side below 11 ("image must be at least 11x11") or above
+ * 16384, channels outside [1, 4] -- return 2 before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_IMAGE_SSIM_WINDOW 11
+#define NM_IMAGE_SSIM_MAX_SIDE 16384
+#define NM_IMAGE_SSIM_MAX_CHANNELS 4
+#define NM_IMAGE_SSIM_SUM 0
+#define NM_IMAGE_SSIM_NONFINITE 1
+int nm_image_ssim(const float* d_a, const float* d_b, int32_t height, int32_t width, int32_t channels, double* d_map,
+                  int64_t* d_sums, void* stream);
 
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex

@@ -61,11 +61,29 @@ def _imwrite(path, image):
         Image.fromarray(image).save(path)
 
 
+def _gather_in_order(values, counts, slots, device):
+    """fp64 values of this rank's images -> the values of all ranks' images in image order: counts[r] values come from rank r,
+    slots = (owner rank, index among that rank's), in image order"""
+    from . import dist as nd
+    flat = nd.all_gather_rows(torch.tensor(values, dtype=torch.float64, device=device).reshape(-1), counts)
+    starts = [sum(counts[:r]) for r in range(len(counts))]
+    return [float(flat[starts[r] + k]) for r, k in slots]
+
+
+def _mean_ssim(values):
+    """the dataset SSIM: the fp64 mean over the images, in image order"""
+    total = 0.0
+    for v in values:
+        total = total + v
+    return total / len(values)
+
+
 def eval_nerf(model, config_args, cfg, device):
     """eval_nerf.py:23-105, call for call: dataset -> DataLoader -> `DataBundle.deserialize(...).to_ray_batch()` ->
     `batchify(directions, targets)` -> `model.query((origins, directions_chunk, bounds))` (bounds stay on the host, as
     the reference passes them) -> loss bookkeeping / image files.  Returns the dataset loss (None with
-    `--synthesis-images`; the reference returns nothing and prints it)."""
+    `--synthesis-images`; the reference returns nothing and prints it).  `--ssim` (addition) appends the image's structural
+    similarity to its target (hip_ops.image_ssim) to every [EVAL] line and prints the mean over the images."""
     from . import dist as nd
     rank, world = nd.world()
     dataset = BlenderDataset(cfg, type=DatasetType.TEST)
@@ -80,7 +98,8 @@ def eval_nerf(model, config_args, cfg, device):
     if config_args.save_disparity:
         os.makedirs(disparity_dir, exist_ok=True)
     score = not config_args.synthesis_images
-    losses = []
+    want_ssim = score and bool(getattr(config_args, "ssim", False))
+    losses, ssims = [], []
     for img_nr, ray_batch in enumerate(data_loader):
         if img_nr % world != rank:                 # images are independent: round-robin over the ranks
             continue
@@ -111,8 +130,10 @@ def eval_nerf(model, config_args, cfg, device):
         if config_args.save_disparity:
             _imwrite(os.path.join(disparity_dir, f"{img_nr:04d}.png"),
                      cast_to_disparity_image(disp_map.view(height, width), white_background=True))
+        if want_ssim:
+            ssims.append(hip_ops.image_ssim(rgb_map, bundle.ray_targets.to(device), height=height)["ssim"])
         if score:
-            print(f"[EVAL] Iter: {img_nr} Loss MSE {loss} / PSNR: {mse2psnr(loss)}")
+            print(f"[EVAL] Iter: {img_nr} Loss MSE {loss} / PSNR: {mse2psnr(loss)}" + (f" / SSIM: {ssims[-1]}" if want_ssim else ""))
     if not score:
         return None
     if world > 1:
@@ -121,23 +142,29 @@ def eval_nerf(model, config_args, cfg, device):
         flat = nd.all_gather_rows(mine, counts)
         starts = [sum(counts[:r]) for r in range(world)]
         losses = [flat[starts[i % world] + i // world] for i in range(len(dataset))]     # back to image order
+        if want_ssim:
+            ssims = _gather_in_order(ssims, counts, [(i % world, i // world) for i in range(len(dataset))], device)
     total_loss = torch.stack(losses).mean()
     print(f"Dataset loss MSE: {total_loss} / PSNR: {mse2psnr(total_loss)}")
+    if want_ssim:
+        print(f"Dataset SSIM: {_mean_ssim(ssims)}")
     return total_loss
 
 
-def eval_views(model, views, cfg, device="cuda", chunksize=None, render_chunk=None):
+def eval_views(model, views, cfg, device="cuda", chunksize=None, render_chunk=None, metrics=None):
     """The same bookkeeping over an iterable of `(c2w pose, height, width, focal, targets | None)` -- e.g.
     `synthetic_views()` -- with ray directions generated on the GPU.  Returns (per-view losses, dataset loss, dataset
     PSNR, last rgb map).  `targets` may be a callable `(view_nr, rgb) -> (rays, 3) targets` (bench.py photographs the
     render itself).  `render_chunk` renders in larger calls than the bookkeeping's `chunksize` -- the pixels do not depend
     on the chunking (tests/test_gpu_parity.py::test_full_size_view_properties), the loss is still summed per `chunksize`
-    rays and divided by the float batch count."""
+    rays and divided by the float batch count.  `metrics`: a dict that receives `ssim` -- the structural similarity of every
+    scored view to its targets (hip_ops.image_ssim), in view order -- and `ssim_mean`, printed as ` / SSIM:` and `Dataset SSIM:`;
+    None (default): nothing of it is computed or printed, and the returned tuple is the same either way."""
     chunksize = chunksize or cfg.nerf.validation.chunksize
     bounds = torch.tensor([cfg.dataset.near, cfg.dataset.far], dtype=torch.float32)
     from . import dist as nd
     rank, world = nd.world()
-    losses, rgb = [], None
+    losses, ssims, rgb = [], [], None
     scored = [0] * world                      # views WITH targets per rank (every rank walks the whole iterable)
     slots = []                                # (owner rank, index among that rank's scored views), in view order
     for view_nr, (pose, h, w, focal, targets) in enumerate(views):
@@ -158,7 +185,10 @@ def eval_views(model, views, cfg, device="cuda", chunksize=None, render_chunk=No
                 loss += torch.nn.functional.mse_loss(rgb[s:s + chunksize], targets[s:s + chunksize])
             loss /= batch_count
             losses.append(loss)
-            print(f"[EVAL] Iter: {len(losses) - 1} Loss MSE {loss} / PSNR: {mse2psnr(loss)}")
+            if metrics is not None:
+                ssims.append(hip_ops.image_ssim(rgb, targets, height=h)["ssim"])
+            print(f"[EVAL] Iter: {len(losses) - 1} Loss MSE {loss} / PSNR: {mse2psnr(loss)}"
+                  + (f" / SSIM: {ssims[-1]}" if metrics is not None else ""))
     if world > 1:
         # Ranks hold DIFFERENT numbers of views when the view count is not a multiple of the world size (possibly
         # none): every rank enters the one collective with its (scored[rank],) tensor -- empty included -- and the
@@ -167,9 +197,16 @@ def eval_views(model, views, cfg, device="cuda", chunksize=None, render_chunk=No
         flat = nd.all_gather_rows(mine.to(torch.float32), scored)
         starts = [sum(scored[:r]) for r in range(world)]
         losses = [flat[starts[r] + k] for r, k in slots]
+        if metrics is not None:
+            ssims = _gather_in_order(ssims, scored, slots, device)
     total = torch.stack(losses).mean() if losses else None
     if total is not None:
         print(f"Dataset loss MSE: {total} / PSNR: {mse2psnr(total)}")
+    if metrics is not None:
+        metrics["ssim"] = list(ssims)
+        metrics["ssim_mean"] = _mean_ssim(ssims) if ssims else None
+        if ssims:
+            print(f"Dataset SSIM: {metrics['ssim_mean']}")
     return losses, total, (mse2psnr(total) if total is not None else None), rgb
 
 
@@ -190,6 +227,9 @@ def build_parser():
     p.add_argument("--precision", choices=("f32", "bf16x3"), default="f32",
                    help="(addition) arithmetic of the network kernels: f32 = the reference's (default); bf16x3 = fp32 products "
                         "emulated on the bf16 matrix pipe (fp32-class error, |dPSNR| <= 1e-4 dB on the parity fixtures, ~1.8x faster)")
+    p.add_argument("--ssim", action="store_true", default=False,
+                   help="(addition) score every image with the structural similarity too (11-tap Gaussian window, valid windows, "
+                        "data range 1, computed on the GPU): ` / SSIM:` on every [EVAL] line and `Dataset SSIM:`, the mean")
     return p
 
 
@@ -209,7 +249,7 @@ def main(argv=None):
     try:
         with torch.no_grad():
             if args.views > 0:
-                return eval_views(model, synthetic_views(args.views), cfg, device, args.chunksize)
+                return eval_views(model, synthetic_views(args.views), cfg, device, args.chunksize, metrics={} if args.ssim else None)
             return eval_nerf(model, args, cfg, device)
     finally:
         nd.shutdown()

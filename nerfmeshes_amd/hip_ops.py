@@ -1076,6 +1076,46 @@ def mesh_texture_lookup(raster, face_uv, texture, background):
     return out
 
 
+SSIM_WINDOW = 11                         # NM_IMAGE_SSIM_WINDOW
+SSIM_MAX_CHANNELS = 4                    # NM_IMAGE_SSIM_MAX_CHANNELS
+
+
+def image_ssim(a, b, want_map=False, height=None):
+    """The structural similarity of two images (nm_image_ssim; the rule in include/nerfmeshes_hip.h, "Image SSIM"): a, b (H,W,C)
+    -- or (H*W,C) with `height=` -- fp32 on the GPU, data range 1.  -> dict(ssim: the mean over the valid windows and the
+    channels, NaN when a window was not finite; per_channel: C floats; nonfinite: how many S were not finite; sums: the (C,2)
+    int64 the library wrote, as numpy; map: (H-10,W-10,C) fp64 on the GPU, or None).  One host read, of the sums.  ValueError for
+    what the library refuses: a side below 11 or above 16384, channels outside [1, 4]."""
+    lib = _lib.load()
+    a = _dev32(a, name="a")
+    b = _dev32(b, a.device, "b")
+    if a.shape != b.shape:
+        raise ValueError(f"image_ssim: the images must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if height is not None:
+        if a.dim() != 2 or int(height) <= 0 or a.shape[0] % int(height):
+            raise ValueError(f"image_ssim: height={height} needs (H*W,C) images, got {tuple(a.shape)}")
+        shape = (int(height), a.shape[0] // int(height), a.shape[1])
+    elif a.dim() == 3:
+        shape = tuple(a.shape)
+    else:
+        raise ValueError(f"image_ssim: the images must be (H,W,C), or (H*W,C) with height=, got {tuple(a.shape)}")
+    h, w, c = shape
+    if h > 2 ** 31 - 1 or w > 2 ** 31 - 1 or c > 2 ** 31 - 1:
+        raise ValueError(f"image_ssim: {shape} is beyond the supported sizes")
+    ok = h >= SSIM_WINDOW and w >= SSIM_WINDOW and 1 <= c <= SSIM_MAX_CHANNELS    # nothing is allocated for what is refused
+    out = torch.empty(h - 10, w - 10, c, dtype=torch.float64, device=a.device) if want_map and ok else None
+    sums = torch.empty(max(c, 1), 2, dtype=torch.int64, device=a.device)
+    _mesh_check(lib, lib.nm_image_ssim(_ptr(a), _ptr(b), h, w, c, _ptr(out), _ptr(sums), _stream()), "nm_image_ssim")
+    host = sums.cpu().numpy()
+    windows = (h - 10) * (w - 10) * 2 ** 32
+    per_channel = [int(s) / windows for s in host[:, 0]]
+    nonfinite = int(host[:, 1].sum())
+    total = 0.0
+    for v in per_channel:
+        total = total + v
+    return dict(ssim=float("nan") if nonfinite else total / c, per_channel=per_channel, nonfinite=nonfinite, sums=host, map=out)
+
+
 def _mesh_arrays(verts, faces, what):
     """(V,3) fp32 vertices and (F,3) int32 faces of one mesh on the GPU (host arrays are copied over), checked."""
     verts = _dev32(verts if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.as_tensor(verts).cuda(), name="verts")

@@ -461,6 +461,10 @@ FEATURES = {
         "--render-views", {"render_views": 0, "render_size": 800}, on=lambda o: int(o["render_views"]),
         valid=lambda o: int(o["render_views"]) >= 0 and 1 <= int(o["render_size"]) <= 16384,
         invalid=lambda o: "--render-views must be >= 0 and --render-size in [1, 16384]"),
+    "render_ssim": Feature(
+        "--render-ssim", {"render_ssim": False, "render_views": 0, "render_size": 800}, on=lambda o: bool(o["render_ssim"]),
+        valid=lambda o: int(o["render_views"]) > 0 and int(o["render_size"]) >= hip_ops.SSIM_WINDOW,
+        invalid=lambda o: f"--render-ssim needs --render-views N > 0 and --render-size >= {hip_ops.SSIM_WINDOW}"),
     "texture": Feature(
         "--texture-res", {"texture_res": 0}, on=lambda o: int(o["texture_res"]),
         valid=lambda o: 1 <= int(o["texture_res"]) <= hip_ops.TEXTURE_MAX_RES,
@@ -635,7 +639,8 @@ def render_report(model, vertices, triangles, diffuse, args, cfg, device, textur
     network's own render of each pose -- PSNR, depth difference, silhouette IoU --, printed; rank 0 writes
     <save-dir>/<mesh-name stem>.render.json.  Under torch.distributed the views are dealt out over the ranks.  With
     `--texture-res` the numbers describe the textured mesh, and the per-vertex colours' PSNR of the same views (one
-    rasterisation, one network render) stands beside them."""
+    rasterisation, one network render) stands beside them.  `--render-ssim` adds the structural similarity to the network's render
+    (mesh_render.SSIM_ROW) to every view and to the means."""
     from . import dist as nd
     from . import mesh_render, synthetic
     if not (hasattr(model, "can_query_view") and model.can_query_view()):
@@ -646,7 +651,8 @@ def render_report(model, vertices, triangles, diffuse, args, cfg, device, textur
     background = (1.0,) * 3 if cfg.dataset.white_background else (0.0,) * 3
     report = mesh_render.evaluate(vertices, triangles.to(torch.int32), torch.as_tensor(diffuse), views, cfg.dataset.near / 4,
                                   background, model=model, bounds=bounds, chunksize=cfg.nerf.validation.chunksize,
-                                  compare_nerf=True, device=device, texture=texture, vertex_too=texture is not None)
+                                  compare_nerf=True, device=device, texture=texture, vertex_too=texture is not None,
+                                  ssim=bool(getattr(args, "render_ssim", False)))
     if texture is not None:
         report["mesh"] = dict(appearance="texture", atlas=dict(width=int(texture[1].shape[1]), height=int(texture[1].shape[0])),
                               texture_res=int(args.texture_res))
@@ -745,6 +751,9 @@ def build_parser():
                         "against the network's own render of each pose: PSNR, depth difference, silhouette IoU; writes "
                         "<save-dir>/<mesh-name stem>.render.json (0 = off)")
     p.add_argument("--render-size", type=int, default=800, help="(addition) side in pixels of the --render-views images")
+    p.add_argument("--render-ssim", action="store_true", default=False,
+                   help="(addition) with --render-views: the structural similarity (SSIM, 11-tap Gaussian window) of every mesh "
+                        "image to the network's render too, per view and in the means of <stem>.render.json")
     p.add_argument("--texture-res", type=_non_negative, default=0,
                    help="(addition) bake a texture atlas from the network: every face gets a chart of this many lattice "
                         "intervals per triangle side, (N+1)(N+2)/2 samples queried like the vertices; writes <stem>.obj with "

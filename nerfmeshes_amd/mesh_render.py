@@ -11,7 +11,8 @@ hip_ops.mesh_texture_lookup fetches the image at the interpolated texture coordi
 along the same ray.  The rasteriser's depth is measured along the camera's axis; the network's depth_map along the unit ray:
 `ray_lengths` converts.  With a dataset the PSNR uses eval_nerf's bookkeeping (chunks of cfg.nerf.validation.chunksize, the
 float batch count), so it compares with the PSNR eval_nerf prints for the network.  `--compare-nerf` renders every pose with
-the network too (query_view, keep_depth) and reports the mesh against it.  Under torch.distributed.run the views are dealt
+the network too (query_view, keep_depth) and reports the mesh against it.  `--ssim` scores the same image pairs with the
+structural similarity too (hip_ops.image_ssim), `--save-ssim-maps` writes its per-pixel map.  Under torch.distributed.run the views are dealt
 round-robin to the ranks and the per-view rows gathered; the report does not depend on the number of ranks."""
 import argparse
 import json
@@ -120,15 +121,28 @@ def _to_u8(rgb):
 
 
 VERTEX_ROW = ("psnr_target_vertex", "psnr_nerf_vertex")
+SSIM_ROW = ("ssim_target", "ssim_nerf")                          # only with ssim=True (--ssim, mesh_nerf --render-ssim)
+SSIM_VERTEX_ROW = ("ssim_target_vertex", "ssim_nerf_vertex")     # ... and vertex_too
+
+
+def ssim_gray_u8(ssim_map):
+    """(H-10,W-10,C) fp64 S -> (H-10,W-10) uint8: the channel mean clamped to [0,1] as 8-bit grey (a NaN is black)"""
+    grey = torch.nan_to_num(ssim_map.mean(dim=-1), nan=0.0).clamp(0.0, 1.0)
+    return (grey * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
 
 
 def evaluate(verts, faces, colors, views, near, background, model=None, bounds=None, chunksize=None, compare_nerf=False,
-             cull_back=False, save_dir=None, save_images=False, save_depth=False, device="cuda", texture=None, vertex_too=False):
+             cull_back=False, save_dir=None, save_images=False, save_depth=False, device="cuda", texture=None, vertex_too=False,
+             ssim=False, save_ssim_maps=False):
     """The report over an iterable of views `(pose, height, width, focal, targets | None)`: rank r draws views r, r + world,
     ...; the rows are gathered, so every rank returns the single-rank report.  targets: (H*W, 3) on any device.
     texture = (face_uv, image): the mesh is drawn with it (render_mesh) and every number describes the textured mesh;
     vertex_too then adds VERTEX_ROW -- the PSNR of the per-vertex colours from the same rasterisation against the same target and
-    the same network render -- to every view and to the means."""
+    the same network render -- to every view and to the means.
+    ssim adds SSIM_ROW (hip_ops.image_ssim of the mesh image against the target and, with compare_nerf, against the network's
+    render; with vertex_too SSIM_VERTEX_ROW as well) to every view and to the means: the views must be at least 11 x 11.
+    save_ssim_maps writes mesh_ssim/NNNN.png, the map against the target -- against the network's render for a view without
+    one --, (H-10, W-10) in 8-bit grey.  Without ssim the columns do not exist."""
     from . import dist as nd
     rank, world = nd.world()
     verts, faces, _, _ = hip_ops._mesh_arrays(verts, faces, "mesh_render")
@@ -136,7 +150,9 @@ def evaluate(verts, faces, colors, views, near, background, model=None, bounds=N
     if texture is not None:
         texture = device_texture(texture, verts.device)
     vertex_too = bool(vertex_too and texture is not None)
-    columns = ROW + (VERTEX_ROW if vertex_too else ())
+    ssim = bool(ssim or save_ssim_maps)
+    columns = ROW + (VERTEX_ROW if vertex_too else ()) + ((SSIM_ROW + (SSIM_VERTEX_ROW if vertex_too else ())) if ssim else ())
+    want_map = bool(save_dir and save_ssim_maps)
     rows, total = [], 0
     for nr, (pose, height, width, focal, targets) in enumerate(views):
         total += 1
@@ -156,6 +172,19 @@ def evaluate(verts, faces, colors, views, near, background, model=None, bounds=N
                 row["psnr_nerf_vertex"] = psnr(torch.nn.functional.mse_loss(out["rgb_vertex"].reshape(-1, 3), net_rgb))
         if vertex_too and targets is not None:
             row["psnr_target_vertex"] = psnr(chunked_mse(out["rgb_vertex"].reshape(-1, 3), targets.to(verts.device).reshape(-1, 3), chunk))
+        if ssim:
+            image, ssim_map = out["rgb"].reshape(height, width, 3), None
+            shots = ([("target", targets.to(verts.device).reshape(height, width, 3))] if targets is not None else []) + (
+                [("nerf", net_rgb.reshape(height, width, 3))] if compare_nerf else [])
+            for nr_shot, (name, other) in enumerate(shots):
+                got = hip_ops.image_ssim(image, other, want_map=want_map and nr_shot == 0)
+                row[f"ssim_{name}"] = got["ssim"]
+                ssim_map = got["map"] if nr_shot == 0 else ssim_map
+                if vertex_too:
+                    row[f"ssim_{name}_vertex"] = hip_ops.image_ssim(out["rgb_vertex"].reshape(height, width, 3), other)["ssim"]
+            if ssim_map is not None:
+                os.makedirs(os.path.join(save_dir, "mesh_ssim"), exist_ok=True)
+                _imwrite(os.path.join(save_dir, "mesh_ssim", f"{nr:04d}.png"), ssim_gray_u8(ssim_map))
         rows.append([row[k] for k in columns])
         if save_dir and save_images:
             os.makedirs(os.path.join(save_dir, "mesh_images"), exist_ok=True)
@@ -182,7 +211,8 @@ def build_report(table, near, columns=ROW):
     for r in table:
         views.append({k: (int(v) if k in integer and not np.isnan(v) else (None if np.isnan(v) else float(v))) for k, v in zip(columns, r)})
     mean = {}
-    for k in ("psnr_target", "psnr_nerf", "depth_mean", "depth_median", "iou") + tuple(k for k in VERTEX_ROW if k in columns):
+    for k in ("psnr_target", "psnr_nerf", "depth_mean", "depth_median", "iou") + tuple(
+            k for k in VERTEX_ROW + SSIM_ROW + SSIM_VERTEX_ROW if k in columns):
         have = [v[k] for v in views if v[k] is not None]
         mean[k] = float(np.mean(have)) if have else None
     mse = [10.0 ** (-v["psnr_target"] / 10.0) for v in views if v["psnr_target"] is not None]
@@ -205,6 +235,11 @@ def format_report(report):
                          f"IoU {v['iou']:.4f}")
         if v.get("psnr_nerf_vertex") is not None:
             parts.append(f"per-vertex colours: PSNR to the network {v['psnr_nerf_vertex']:.4f}")
+        have = [(what, v.get(key)) for what, key in (("the target", "ssim_target"), ("the network", "ssim_nerf"),
+                                                     ("the target, per-vertex colours", "ssim_target_vertex"),
+                                                     ("the network, per-vertex colours", "ssim_nerf_vertex"))]
+        if any(value is not None for _, value in have):
+            parts.append("SSIM to " + ", to ".join(f"{what} {value:.6f}" for what, value in have if value is not None))
         lines.append(", ".join(parts))
     mean = ", ".join(f"{k} {v:.6f}" for k, v in report["mean"].items() if v is not None)
     lines.append(f"Mesh render: {len(report['views'])} views" + (f", mean {mean}" if mean else ""))
@@ -324,6 +359,12 @@ def build_parser():
     p.add_argument("--save-images", action="store_true", default=False)
     p.add_argument("--save-depth", action="store_true", default=False)
     p.add_argument("--out", type=str, default=None, help="write the report as JSON")
+    p.add_argument("--ssim", action="store_true", default=False,
+                   help="score every view with the structural similarity too (hip_ops.image_ssim: 11-tap Gaussian window, valid "
+                        "windows, data range 1): ssim_target and, with --compare-nerf, ssim_nerf per view and in the means")
+    p.add_argument("--save-ssim-maps", action="store_true", default=False,
+                   help="implies --ssim: write <save-dir>/mesh_ssim/NNNN.png, the per-pixel SSIM (channel mean, clamped to "
+                        "[0, 1]) as 8-bit grey, 10 pixels smaller than the view each way")
     return p
 
 
@@ -369,7 +410,7 @@ def main(argv=None):
             report = evaluate(verts, faces, colors, views, near, (1.0,) * 3 if white else (0.0,) * 3, model=model, bounds=bounds,
                               chunksize=chunksize, compare_nerf=args.compare_nerf, cull_back=args.cull == "back",
                               save_dir=args.save_dir, save_images=args.save_images, save_depth=args.save_depth, device=device,
-                              texture=texture)
+                              texture=texture, ssim=args.ssim, save_ssim_maps=args.save_ssim_maps)
         report["mesh"] = dict(path=args.mesh, vertices=int(verts.shape[0]), faces=int(faces.shape[0]),
                               appearance="vertex" if texture is None else "texture")
         if texture is not None:
