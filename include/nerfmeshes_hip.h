@@ -61,6 +61,8 @@ extern "C" {
  * (mesh_nerf --cull-hidden-views).  Additions only. */
 /* 6, later: + nm_image_ssim: the structural similarity of two images, bit for bit a closed rule (eval_nerf --ssim, mesh_render
  * --ssim, mesh_nerf --render-ssim).  Additions only. */
+/* 6, later: + nm_tsdf_integrate (+ nm_tsdf_workspace_bytes): rendered depth maps fused into a truncated signed distance field,
+ * bit for bit a closed rule (mesh_nerf --geometry tsdf).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -1129,6 +1131,50 @@ int nm_export_obj_textured(const float* h_vertices, int64_t num_vertices, const 
 #define NM_IMAGE_SSIM_NONFINITE 1
 int nm_image_ssim(const float* d_a, const float* d_b, int32_t height, int32_t width, int32_t channels, double* d_map,
                   int64_t* d_sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * TSDF fusion (mesh_nerf --geometry tsdf; DESIGN.md, "TSDF geometry"): depth maps rendered from V cameras are fused into a
+ * truncated signed distance field on a range of the voxels of a grid, as a closed rule that a numpy restatement
+ * (tests/tsdf_fuse.py) reproduces bit for bit -- the field, the observation counts and the three counters.  THE RULE:
+ *
+ *   inputs     V views (a HOST array of nm_view, 1 <= V <= NM_TSDF_MAX_VIEWS, all of one height H and width W in [1, 16384],
+ *              use_ndc = 0, focal finite and > 0; R = c2w[:3,:3], c = c2w[:3,3]); depth (V,H,W) fp32: the depth of the surface
+ *              every pixel sees, measured ALONG THE CAMERA'S AXIS (camera z), row 0 on top; opacity (V,H,W) fp32 or NULL; the
+ *              three fp32 axes of the (n0,n1,n2) grid, as nm_mlp_grid_query takes them; the flat voxel range [first, first +
+ *              count), last axis fastest; trunc > 0, near > 0, min_opacity.
+ *   arithmetic fp64 throughout -- every fp32 input widened first --, every product, sum, difference and quotient rounded on
+ *              its own (no fused multiply-add), IEEE division, in exactly the order written here.
+ *   voxel      p = (ax0[i0], ax1[i1], ax2[i2]); sum = 0, n = 0, occluded = false; the views in index order:
+ *   project    d = p - c;  cx = (R00 dx + R10 dy) + R20 dz, cy and cz likewise from columns 1 and 2 of R;  z = -cz.
+ *              Unless z >= near the voxel is not in this view.
+ *              col = rint((cx / z) focal + 0.5 W), row = rint(0.5 H - (cy / z) focal), rint rounding half to even: pixel i
+ *              sits at u = i, get_ray_bundle's grid and the rasteriser's.  Unless 0 <= col <= W - 1 and 0 <= row <= H - 1
+ *              the voxel is not in this view.
+ *   hit        D = depth[v][row][col].  The ray is a hit iff D is finite and D > 0 and -- where there is an opacity map --
+ *              opacity[v][row][col] >= min_opacity (a NaN opacity is a miss).
+ *   observe    miss: t = -1 (the ray saw free space all the way).  hit: s = z - D; if s > trunc the voxel is occluded in this
+ *              view (occluded = true) and there is no observation; otherwise t = max(-1, s / trunc).
+ *              An observation does sum = sum + t, n = n + 1.
+ *   field      inside-positive: phi = (float)(sum / (double) n) if n > 0; +1 if n == 0 and occluded (interior); -1 if n == 0
+ *              and not occluded: the voxel was in no view's frustum and counts as empty.
+ *   counters   int64: [NM_TSDF_OBSERVED] voxels with n > 0, [NM_TSDF_INTERIOR] n == 0 and occluded, [NM_TSDF_OUTSIDE] the
+ *              rest; integer additions, so the order the workgroups run in shows in no output.
+ *
+ * d_field (count,) fp32; d_observations NULL or (count,) int32, which receives n; d_counts (3,) int64 on the DEVICE, zeroed by
+ * the call on the stream.  d_workspace: nm_tsdf_workspace_bytes(V, H, W) bytes (0 for sizes the entry refuses): the view table
+ * and the merged hit-depth map.  The views are read before the call returns.  Nothing allocates and nothing waits for the
+ * host.  Argument errors -- a null pointer, V outside [1, 1024], views of unequal size or with use_ndc, a focal, trunc or near
+ * that is not finite and > 0, a NaN min_opacity, a voxel range outside the grid -- return 2 before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_TSDF_MAX_VIEWS 1024
+#define NM_TSDF_OBSERVED 0
+#define NM_TSDF_INTERIOR 1
+#define NM_TSDF_OUTSIDE 2
+int64_t nm_tsdf_workspace_bytes(int64_t num_views, int32_t height, int32_t width);
+int nm_tsdf_integrate(const nm_view* views, int64_t num_views, const float* d_depth, const float* d_opacity, const float* d_ax0,
+                      const float* d_ax1, const float* d_ax2, int32_t n0, int32_t n1, int32_t n2, int64_t first, int64_t count,
+                      double trunc, double near, double min_opacity, void* d_workspace, float* d_field, int32_t* d_observations,
+                      int64_t* d_counts, void* stream);
 
 /* PLY export of a point cloud (HOST arrays): element vertex with x y z nx ny nz as float and red green blue as uchar, the
  * property names of the reference's export_ply (src/mesh_surface_ray.py:46-58).  binary = 0: "format ascii 1.0", one vertex

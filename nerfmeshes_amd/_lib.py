@@ -236,6 +236,10 @@ SIGNATURES = {
     "nm_export_obj_textured": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64,
                                          c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "nm_image_ssim": (C.c_int, [c_void_p, c_void_p, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p]),
+    "nm_tsdf_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "nm_tsdf_integrate": (C.c_int, [C.POINTER(View), C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
     "nm_export_ply": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int, C.c_char_p]),
 }
 

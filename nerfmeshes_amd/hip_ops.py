@@ -1116,6 +1116,51 @@ def image_ssim(a, b, want_map=False, height=None):
     return dict(ssim=float("nan") if nonfinite else total / c, per_channel=per_channel, nonfinite=nonfinite, sums=host, map=out)
 
 
+TSDF_MAX_VIEWS = 1024                    # NM_TSDF_MAX_VIEWS
+TSDF_COUNTS = ("observed", "interior", "outside")     # NM_TSDF_OBSERVED, _INTERIOR, _OUTSIDE
+
+
+def tsdf_integrate(views, depth, opacity, axes, trunc, near, min_opacity=0.5, first=0, count=None, want_observations=False):
+    """Depth maps fused into a truncated signed distance field on voxels [first, first + count) of a grid (nm_tsdf_integrate; the
+    rule in include/nerfmeshes_hip.h, "TSDF fusion").  views: V non-NDC hip_ops.make_view results of one size; depth (V,H,W) fp32
+    on the GPU, measured along the camera's axis; opacity (V,H,W) or None; axes: the three fp32 axes of the grid, as
+    HipMLP.grid_query takes them.  -> dict(field (count,) fp32: inside-positive, in [-1, 1]; observations (count,) int32 or None;
+    counts (3,) int64 ON THE DEVICE in the order of TSDF_COUNTS -- no host read here).  ValueError for what the library refuses."""
+    lib = _lib.load()
+    views = list(views)
+    depth = _dev32(depth, name="depth")
+    dev = depth.device
+    if not views or depth.dim() != 3 or depth.shape[0] != len(views):
+        raise ValueError(f"tsdf_integrate: depth must be (V,H,W) with one image per view, got {tuple(depth.shape)} for {len(views)} views")
+    if tuple(depth.shape[1:]) != (int(views[0].height), int(views[0].width)):
+        raise ValueError(f"tsdf_integrate: depth images of {tuple(depth.shape[1:])} for views of "
+                         f"({int(views[0].height)}, {int(views[0].width)})")
+    if opacity is not None:
+        opacity = _dev32(opacity, dev, "opacity")
+        if opacity.shape != depth.shape:
+            raise ValueError(f"tsdf_integrate: opacity {tuple(opacity.shape)} must have depth's shape {tuple(depth.shape)}")
+    ax = [_dev32(a, dev, "axis").reshape(-1) for a in axes]
+    if len(ax) != 3 or any(a.numel() == 0 or a.numel() > 2 ** 31 - 1 for a in ax):
+        raise ValueError("tsdf_integrate: axes must be three non-empty arrays")
+    n0, n1, n2 = (a.numel() for a in ax)
+    first = int(first)
+    count = n0 * n1 * n2 - first if count is None else int(count)
+    v, h, w = (int(s) for s in depth.shape)
+    nbytes = int(lib.nm_tsdf_workspace_bytes(v, h, w))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)      # 0: a size the entry refuses, in its own words below
+    array = (_lib.View * len(views))(*views)
+    ok = 0 <= first and 0 <= count <= n0 * n1 * n2 - first                # nothing is allocated for what is refused
+    field = torch.empty(count if ok else 0, dtype=torch.float32, device=dev)
+    obs = torch.empty(count, dtype=torch.int32, device=dev) if want_observations and ok else None
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    # a zero-size tensor has no address: the entry takes none for count == 0
+    _mesh_check(lib, lib.nm_tsdf_integrate(array, v, _ptr(depth), _ptr(opacity), _ptr(ax[0]), _ptr(ax[1]), _ptr(ax[2]), n0, n1, n2,
+                                           first, count, float(trunc), float(near), float(min_opacity), _ptr(ws),
+                                           _ptr(field) if field.numel() else None, _ptr(obs) if obs is not None and obs.numel() else None,
+                                           _ptr(counts), _stream()), "nm_tsdf_integrate")
+    return dict(field=field, observations=obs, counts=counts)
+
+
 def _mesh_arrays(verts, faces, what):
     """(V,3) fp32 vertices and (F,3) int32 faces of one mesh on the GPU (host arrays are copied over), checked."""
     verts = _dev32(verts if isinstance(verts, torch.Tensor) and verts.is_cuda else torch.as_tensor(verts).cuda(), name="verts")

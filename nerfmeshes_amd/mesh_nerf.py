@@ -265,6 +265,148 @@ def extract_geometry_with_super_sampling(model, device, args):
     return vertices, triangles, normals, density
 
 
+def tsdf_focal(args):
+    """`--tsdf-focal 0`: the synthetic scenes' 1111.1111 at 800 pixels, scaled to --tsdf-size"""
+    from . import synthetic
+    return float(args.tsdf_focal) or synthetic.LEGO_FOCAL_800 * int(args.tsdf_size) / 800.0
+
+
+def tsdf_ray_lengths(size, focal):
+    """(size, size) fp64 on the host: |(x, y, -1)| of get_ray_bundle's camera-space ray through every pixel of a square view --
+    the distance along the unit ray over the depth along the camera's axis"""
+    import numpy as np
+    i = (np.arange(size, dtype=np.float64) - size * 0.5) / np.float64(focal)
+    return np.sqrt(i[None, :] * i[None, :] + i[:, None] * i[:, None] + 1.0)
+
+
+def check_tsdf(args, cfg=None):
+    """What `--geometry tsdf` cannot be combined with (ValueError): --super-sampling, whose refinement reads density along the
+    cut edges, and a scene in NDC, whose rays are not the pinhole rays the fusion projects along."""
+    if int(getattr(args, "super_sampling", 0)) >= 1:
+        raise ValueError("--geometry tsdf has no --super-sampling: the refinement moves a vertex to a sign change of the density, "
+                         "and the fused field has none")
+    if cfg is not None and cfg.dataset.use_ndc:
+        raise ValueError("--geometry tsdf needs pinhole views: the scene is in normalised device coordinates (cfg.dataset.use_ndc)")
+
+
+def tsdf_render_views(model, args, cfg, device):
+    """The depth and the opacity of the --tsdf-views cameras -> (views: hip_ops.make_view results, depth (V,S,S), opacity (V,S,S)).
+    `query_view(..., keep_depth=True)` measures the depth along the UNIT ray of each pixel (get_ray_bundle normalises its
+    directions); the fusion compares it with a voxel's depth along the camera's axis, so every depth is divided by its pixel's
+    |(x, y, -1)| (tsdf_ray_lengths) in fp64 and rounded to fp32 once.  Under torch.distributed the VIEWS are split over the
+    ranks (dist.split_range) and ONE all-gather assembles both stacks on every rank."""
+    from . import dist as nd
+    from . import mesh_render
+    rank, world = nd.world()
+    count, size, focal = int(args.tsdf_views), int(args.tsdf_size), tsdf_focal(args)
+    poses = mesh_render.sphere_poses(count, (0.0, 0.0, 0.0), float(args.tsdf_radius))
+    bounds = torch.tensor([cfg.dataset.near, cfg.dataset.far], dtype=torch.float32)
+    lo, hi = nd.split_range(count, rank, world)
+    own = torch.empty(hi - lo, 2, size, size, dtype=torch.float32, device=device)
+    lengths = torch.from_numpy(tsdf_ray_lengths(size, focal)).to(device)
+    for k in range(lo, hi):
+        out = model.query_view(torch.from_numpy(poses[k]), size, size, focal, bounds, keep_depth=True)
+        own[k - lo, 0] = (out.depth_map.view(size, size).double() / lengths).float()
+        own[k - lo, 1] = out.acc_map.view(size, size)
+    if world > 1:
+        own = nd.all_gather_rows(own, [b - a for a, b in (nd.split_range(count, r, world) for r in range(world))])
+    views = [hip_ops.make_view(pose, size, size, focal) for pose in poses]
+    return views, own[:, 0].contiguous(), own[:, 1].contiguous()
+
+
+def extract_geometry_tsdf(model, device, args, cfg):
+    """`--geometry tsdf` -> the four values of `extract_geometry`, the 4th being the fused field ("TSDF geometry"): the
+    network's depth is rendered from --tsdf-views cameras all around the volume (tsdf_render_views), fused into a truncated
+    signed distance field on the density grid's own axes (hip_ops.tsdf_integrate: inside-positive, so that marching cubes winds
+    and orients the mesh as on the density path) and meshed at --tsdf-level -- no iso level to clamp.  Under torch.distributed
+    the views are split for the render; `--gather triangles` then fuses and meshes per slab (dist.marching_cubes_sharded),
+    `--gather grid` fuses slabs and assembles the field; both give the single-rank mesh bit for bit.  Rank 0 writes
+    <save-dir>/<mesh-name stem>.tsdf.json."""
+    import time
+    from . import dist as nd
+    check_tsdf(args, cfg)
+    if not (hasattr(model, "can_query_view") and model.can_query_view()):
+        raise RuntimeError("--geometry tsdf needs a model with the deterministic in-kernel view render (NeRFModel.query_view "
+                           "in eval mode, no perturb / noise): there is no fallback")
+    rank, world = nd.world()
+    nums = _nums(args.res)
+    if min(nums) < 2:
+        raise ValueError("Input array must be at least 2x2x2.")
+    plane = nums[1] * nums[2]
+    ax = _axes(args, nums, device)
+    level = float(args.tsdf_level)
+    trunc = float(args.tsdf_trunc) * 2.0 * args.limit / (nums[0] - 1)        # --tsdf-trunc voxels of the grid's own spacing
+    seconds = {}
+
+    def clock(name, start):
+        torch.cuda.synchronize(device)
+        seconds[name] = seconds.get(name, 0.0) + time.perf_counter() - start
+
+    start = time.perf_counter()
+    views, depth, opacity = tsdf_render_views(model, args, cfg, device)
+    clock("render", start)
+    tally = torch.zeros(3, dtype=torch.int64, device=device)
+
+    def integrate(p_lo, p_hi, counted=True):
+        nonlocal tally
+        out = hip_ops.tsdf_integrate(views, depth, opacity, ax, trunc, cfg.dataset.near, min_opacity=float(args.tsdf_min_opacity),
+                                     first=p_lo * plane, count=(p_hi - p_lo) * plane)
+        if counted:
+            tally = tally + out["counts"]
+        return out["field"]
+
+    start = time.perf_counter()
+    if world > 1 and getattr(args, "gather", "triangles") == "triangles":
+        # a rank's ghost planes are fused in calls of their own: voxels are independent, so the field is the same bytes, and the
+        # counters then count every plane of the grid on exactly one rank
+        lo, hi, _, _, _, _ = nd.slab_layers(nums[0], rank, world)
+        top = hi + (1 if hi == nums[0] - 1 else 0)
+
+        def query(p_lo, p_hi):
+            start = time.perf_counter()
+            parts = [integrate(a, b, counted) for a, b, counted in ((p_lo, lo, False), (lo, top, True), (top, p_hi, False)) if b > a]
+            clock("integrate", start)
+            return torch.cat(parts)
+
+        vertices, triangles, normals, _, field = nd.marching_cubes_sharded(query, *nums, lambda *slab: level)
+        seconds["marching_cubes"] = time.perf_counter() - start - seconds.get("integrate", 0.0)
+    else:
+        if world > 1:
+            field = nd.density_grid_sharded(integrate, *nums)
+        else:
+            field = integrate(0, nums[0]).view(*nums)
+        clock("integrate", start)
+        start = time.perf_counter()
+        vertices, triangles, normals, _ = hip_ops.marching_cubes(field, level)
+        clock("marching_cubes", start)
+    if world > 1:
+        nd.all_reduce(tally)
+    counts = dict(zip(hip_ops.TSDF_COUNTS, (int(x) for x in tally.tolist())))
+    if vertices.shape[0] == 0:              # the sharded path: skimage's two errors, in its order (see hip_ops.marching_cubes)
+        import torch.distributed as td
+        ends = torch.tensor([1.0, -1.0] if field is None else [float(field.min()), float(field.max())], device=device)
+        lo, hi = float(nd.all_reduce(ends[:1], td.ReduceOp.MIN)), float(nd.all_reduce(ends[1:], td.ReduceOp.MAX))
+        if level < lo or level > hi:
+            raise ValueError("Surface level must be within volume data range.")
+        raise RuntimeError("No surface found at the given iso value.")
+    print(f"TSDF: {len(views)} views of {int(args.tsdf_size)}² fused into {nums[0]} x {nums[1]} x {nums[2]} voxels: "
+          f"{counts['observed']} observed, {counts['interior']} interior (occluded in every view), {counts['outside']} outside every "
+          f"view; {vertices.shape[0]} vertices, {triangles.shape[0]} faces")
+    if rank == 0:
+        path = os.path.join(args.save_dir, os.path.splitext(args.mesh_name)[0] + ".tsdf.json")
+        report = dict(geometry="tsdf", res=list(nums), limit=float(args.limit), views=len(views), size=int(args.tsdf_size),
+                      radius=float(args.tsdf_radius), focal=tsdf_focal(args), trunc_voxels=float(args.tsdf_trunc), trunc=trunc,
+                      near=float(cfg.dataset.near), min_opacity=float(args.tsdf_min_opacity), level=level, voxels=counts,
+                      vertices=int(vertices.shape[0]), faces=int(triangles.shape[0]),
+                      seconds={k: seconds.get(k, 0.0) for k in ("render", "integrate", "marching_cubes")})   # last: all that varies
+        with open(path, "w") as fh:
+            json.dump(report, fh, indent=1)
+            fh.write("\n")
+        print(f"TSDF report saved to {path}")
+    vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)   # res/2, not (res-1)/2: as the density path
+    return vertices, triangles, normals, field
+
+
 def network_normals(net, vertices, normals):
     """`--normals network`: n = -grad / |grad| of the network's raw sigma at the world-space vertices (HipMLP.density_gradient),
     normalised in fp32 -- towards lower density, the orientation of skimage's default (gradient_direction="descent") and so of
@@ -413,6 +555,13 @@ class Feature(typing.NamedTuple):
         return bool(self.on(o)) or (self.any_option and any(o[name] != default for name, default in self.options.items()))
 
 
+def _finite(x, lo=float("-inf"), hi=float("inf")):
+    return lo < float(x) < hi                       # a NaN fails both comparisons
+
+
+TSDF_OPTIONS = {"geometry": "density", "tsdf_views": 32, "tsdf_size": 800, "tsdf_radius": 4.0, "tsdf_focal": 0.0, "tsdf_trunc": 3.0,
+                "tsdf_min_opacity": 0.5, "tsdf_level": 0.0}
+
 # The geometry stages run in this order (postprocess).  The component filter comes first: its thresholds count original
 # triangles, and a filter that leaves nothing raises before anything is written.  The cull comes next, on the full-resolution
 # geometry, so that the smoothing, the clustering, the appearance rays and the texture bake work on less.  Smoothing comes
@@ -420,6 +569,16 @@ class Feature(typing.NamedTuple):
 # --target-mesh, the network normals and the appearance query, which see the final geometry and spend no ray on a dropped
 # vertex.  The stage functions are looked up on this module when they are called, so that a tool can replace one.
 FEATURES = {
+    "tsdf": Feature(
+        "--geometry tsdf / --tsdf-views / --tsdf-size / --tsdf-radius / --tsdf-focal / --tsdf-trunc / --tsdf-min-opacity / "
+        "--tsdf-level", TSDF_OPTIONS, on=lambda o: o["geometry"] == "tsdf", any_option=True,
+        valid=lambda o: (o["geometry"] in ("density", "tsdf") and 1 <= int(o["tsdf_views"]) <= hip_ops.TSDF_MAX_VIEWS
+                         and 1 <= int(o["tsdf_size"]) <= 16384 and _finite(o["tsdf_radius"], lo=0.0)
+                         and (float(o["tsdf_focal"]) == 0.0 or _finite(o["tsdf_focal"], lo=0.0)) and _finite(o["tsdf_trunc"], lo=0.0)
+                         and _finite(o["tsdf_min_opacity"]) and _finite(o["tsdf_level"], -1.0, 1.0)),
+        invalid=lambda o: (f"--geometry must be density or tsdf, --tsdf-views in [1, {hip_ops.TSDF_MAX_VIEWS}], --tsdf-size in "
+                           "[1, 16384], --tsdf-radius and --tsdf-trunc finite and > 0, --tsdf-focal finite and >= 0, "
+                           "--tsdf-min-opacity finite and --tsdf-level in (-1, 1)")),
     "normals": Feature(
         "--normals network", {"normals": "grid"}, on=lambda o: o["normals"] == "network",
         script_has="only has the grid's normals"),
@@ -506,11 +665,16 @@ def export_marching_cubes(model, args, cfg, device):
     all are checked before anything is read or written, and the geometry stages among them run right after the geometry stage
     or the cache load (postprocess).  The cache keeps the geometry as it was before them -- grid normals, unfiltered, unculled,
     unsmoothed, unsimplified --, so that they can be tuned on it.
+    `--geometry tsdf` takes the geometry from depth maps of the network fused into a truncated signed distance field instead
+    of from the density grid (extract_geometry_tsdf); everything after the geometry stage is the same.
     `--normals network` replaces the grid normals by the network's (network_normals) before the appearance query and the OBJ.
     `--texture-res N` bakes a texture atlas after the per-vertex appearance (bake_texture), which stays: the `v` lines keep
     their colours, so a viewer without textures still shows them; the OBJ gains `vt` lines, an .mtl and a .png."""
     geometry = extract_geometry_with_super_sampling if args.super_sampling >= 1 else extract_geometry
     on = check_features(args)
+    if "tsdf" in on:                                       # `--geometry tsdf`: the same four values from the fused depth maps
+        check_tsdf(args)
+        geometry = lambda model, device, args: extract_geometry_tsdf(model, device, args, cfg)  # noqa: E731
     from . import dist as nd
     cache_path = os.path.join(args.save_dir, args.cache_name)
     load = args.use_cached_mesh and os.path.exists(cache_path)
@@ -758,6 +922,20 @@ def build_parser():
                    help="(addition) bake a texture atlas from the network: every face gets a chart of this many lattice "
                         "intervals per triangle side, (N+1)(N+2)/2 samples queried like the vertices; writes <stem>.obj with "
                         "vt lines, <stem>.mtl and <stem>.png, and --render-views scores the textured mesh (0 = off)")
+    p.add_argument("--geometry", choices=("density", "tsdf"), default="density",
+                   help="(addition) where the surface comes from: density (default) -- the density grid thresholded at --iso-level "
+                        "-- or tsdf: the network's depth rendered from --tsdf-views cameras all around the volume, fused into a "
+                        "truncated signed distance field on the --res grid on the GPU and meshed at its zero level; writes "
+                        "<save-dir>/<mesh-name stem>.tsdf.json")
+    p.add_argument("--tsdf-views", type=int, default=32, help="(addition) cameras of --geometry tsdf, spread evenly over a sphere")
+    p.add_argument("--tsdf-size", type=int, default=800, help="(addition) side in pixels of the square depth images")
+    p.add_argument("--tsdf-radius", type=float, default=4.0, help="(addition) radius of the camera sphere around the origin")
+    p.add_argument("--tsdf-focal", type=float, default=0.0, help="(addition) focal length in pixels; 0 (default): 1111.1111 * size / 800")
+    p.add_argument("--tsdf-trunc", type=float, default=3.0,
+                   help="(addition) truncation distance of the field, in voxels of the --res grid")
+    p.add_argument("--tsdf-min-opacity", type=float, default=0.5,
+                   help="(addition) a ray counts as having hit a surface when its accumulated opacity is at least this")
+    p.add_argument("--tsdf-level", type=float, default=0.0, help="(addition) level of the fused field handed to marching cubes, in (-1, 1)")
     p.add_argument("--gather", choices=("triangles", "grid"), default="triangles",
                    help="(addition, multi-GPU) what travels between the ranks: the emitted triangles of per-slab marching "
                         "cubes (default) or the density grid")
