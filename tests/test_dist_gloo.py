@@ -1,7 +1,6 @@
 """CPU, world_size 2, gloo: the multi-GPU sharding layer (nerfmeshes_amd.dist) assembles exactly what a single
 process produces -- rays / grid slabs are disjoint contiguous ranges, one all-gather at the end."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -10,12 +9,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from nerfmeshes_amd import dist as nd
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+from tests.gpu_support import free_port
 
 
 def _worker(rank, world, port, fn, out):
@@ -30,7 +24,7 @@ def _worker(rank, world, port, fn, out):
 def _run(fn, world=2):
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), fn, out), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), fn, out), nprocs=world, join=True)
     return [out[r] for r in range(world)]
 
 
@@ -171,7 +165,7 @@ def test_init_from_env_gloo(monkeypatch):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     assert nd.init_from_env()[:2] == (0, 1)
     monkeypatch.setenv("WORLD_SIZE", "1"); monkeypatch.setenv("RANK", "0"); monkeypatch.setenv("LOCAL_RANK", "0")
-    monkeypatch.setenv("MASTER_ADDR", "127.0.0.1"); monkeypatch.setenv("MASTER_PORT", str(_free_port()))
+    monkeypatch.setenv("MASTER_ADDR", "127.0.0.1"); monkeypatch.setenv("MASTER_PORT", str(free_port()))
     try:
         rank, ws, dev = nd.init_from_env(backend="gloo")
         assert (rank, ws) == (0, 1) and dist.is_initialized()
@@ -327,7 +321,7 @@ def test_trainer_fit_keeps_two_replicas_identical_on_different_rays(tmp_path, de
     `--deterministic` seeded them alike; and all ranks log into the version directory rank 0 picked."""
     mgr = mp.Manager()
     out = mgr.dict()
-    mp.spawn(_fit_worker, args=(2, _free_port(), str(tmp_path), deterministic, out), nprocs=2, join=True)
+    mp.spawn(_fit_worker, args=(2, free_port(), str(tmp_path), deterministic, out), nprocs=2, join=True)
     a, b = out[0], out[1]
     assert a["version"] == b["version"] == 0
     assert sorted(os.listdir(tmp_path / "run")) == ["version_0"]

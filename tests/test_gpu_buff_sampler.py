@@ -15,16 +15,9 @@ import pytest
 import torch
 
 from tests import buff_cases as B
+from tests.gpu_support import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 def _run(ops, case, mode, rows=slice(None)):

@@ -5,42 +5,16 @@ the visible GPUs must exit non-zero instead of mislabelling a 1-GPU run, and the
 what the all-gather delivered."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 import torch
 
+from tests.gpu_support import assert_ranks_ok, clean_env, launch_ranks
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
-def _torchrun(nproc, script, *args, timeout=600, env=None):
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), script, *args]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), **(env or {})), capture_output=True, text=True, timeout=timeout)
-    if r.returncode != 0:      # the launcher's summary hides the workers' own tracebacks: put the first one in front
-        lines = r.stderr.splitlines()
-        first = next((i for i, ln in enumerate(lines) if ln.startswith("Traceback")), None)
-        if first is not None:
-            r.stderr = "\n".join(lines[first:first + 40]) + "\n...\n" + r.stderr
-            r.stdout = ""
-    return r
 
 
 @pytest.mark.parametrize("world", [1, 2])
@@ -49,9 +23,8 @@ def test_rccl_sharded_render_grid_mesh(world):
         pytest.fail("GPU tests need a MI355X")
     if torch.cuda.device_count() < world:
         pytest.skip(f"needs {world} GPUs, this box has {torch.cuda.device_count()}")
-    r = _torchrun(world, os.path.join("tests", "tools", "dist_worker.py"))
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert f"DIST_OK world={world} backend=nccl" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "dist_worker.py"), world, ranks_per_gpu=False)
+    assert_ranks_ok(r, f"DIST_OK world={world} backend=nccl")
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
@@ -63,16 +36,14 @@ def test_ranks_sharing_one_gpu_over_gloo(world):
     bit.  world = 8 is the node size the driver's scaling run uses: every 8-rank code path has run before it does."""
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
-    r = _torchrun(world, os.path.join("tests", "tools", "dist_worker.py"), timeout=1500,
-                  env={"NERFMESHES_RANKS_PER_GPU": str(world), "NM_EXPECT_BACKEND": "gloo"})
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[:6000]
-    assert f"DIST_OK world={world} backend=gloo device=cuda:0" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "dist_worker.py"), world, timeout=1500, env={"NM_EXPECT_BACKEND": "gloo"})
+    assert_ranks_ok(r, f"DIST_OK world={world} backend=gloo device=cuda:0")
 
 
 def test_bench_refuses_more_gpus_than_visible():
     n = torch.cuda.device_count() + 1
     r = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--headline-only"],
-                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+                       cwd=ROOT, env=clean_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode != 0
     assert "visible" in (r.stderr + r.stdout)
     assert '"n_gpus"' not in r.stdout, "no bench line may be printed for a run that could not happen"
@@ -82,7 +53,7 @@ def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
     """A plain `bench.py` run measures the headline alone (everything else takes `--full`), `--steps` is the number of timed
     steps, `ms_per_step` the time of one, and `--dump-outputs` writes the pixels the last timed step rendered."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path)],
-                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+                       cwd=ROOT, env=clean_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(printed) == 1, printed
@@ -100,7 +71,7 @@ def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
 def test_bench_rccl_leg_on_one_rank():
     """bench.py under a launcher environment of ONE rank: RCCL is initialised, the pixels go through the all-gather,
     and the line says how many ranks the collective saw."""
-    r = _torchrun(1, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--headline-only")
+    r = launch_ranks("bench.py", 1, "--gpus", "1", "--steps", "1", "--warmup", "1", "--headline-only", ranks_per_gpu=False)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(printed) == 1, f"stdout must carry the ONE JSON line only (RCCL prints its banner there): {printed}"
@@ -118,7 +89,7 @@ def test_bench_two_ranks_on_one_gpu_carries_the_sharded_objects(mode):
     per-rank roofline fractions, and labelled as a functional (not a scaling) run."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--ranks-per-gpu", "2", "--steps", "1", "--warmup", "1",
                         "--mode", mode, "--mesh-res", "120", "--no-cpu-baseline", "--full"],
-                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
+                       cwd=ROOT, env=clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(printed) == 1, printed
@@ -155,8 +126,7 @@ def test_bench_line_survives_a_failing_secondary_object_at_two_ranks(inject, exp
     which rank 1 never joins; rank 1 gives up waiting for the others' verdicts, leaves, the launcher terminates rank 0 and
     its emergency writer still emits the ONE line (headline + an error for the object) -- or on every rank, where all
     ranks agree through the rendezvous store, skip the object together and the REST of the line is complete."""
-    env = _env()
-    env["NM_BENCH_INJECT_FAILURE"] = inject
+    env = clean_env(NM_BENCH_INJECT_FAILURE=inject)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--ranks-per-gpu", "2", "--steps", "1", "--warmup", "1",
                         "--mesh-res", "60", "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -177,7 +147,7 @@ def test_bench_eight_ranks_on_one_gpu():
     gloo -- a functional run: its rates say nothing about scaling, its objects must all be there and consistent."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--ranks-per-gpu", "8", "--steps", "1", "--warmup", "1",
                         "--mesh-res", "120", "--no-cpu-baseline", "--full"],
-                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=1500)
+                       cwd=ROOT, env=clean_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     printed = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(printed) == 1, printed
@@ -200,7 +170,7 @@ def test_bench_self_launches_two_ranks():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs 2 GPUs")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1", "--headline-only"],
-                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+                       cwd=ROOT, env=clean_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl"]["ranks_in_all_gather"] == 2 and line["rccl"]["slots_match_rank_checksums"]

@@ -8,16 +8,9 @@ import torch
 
 from nerfmeshes_amd import synthetic as S
 from oracle import nerf_oracle as O
+from tests.gpu_support import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 def _desc(kw):

@@ -5,9 +5,6 @@ tile, for 1, 3 and 4 channels, run after run and on a second stream."""
 import contextlib
 import io
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,19 +14,12 @@ from nerfmeshes_amd import synthetic as S
 from tests import image_ssim as IS
 from tests.test_image_ssim import TODAYS_ROW, pair
 from tests.test_mesh_raster import sheet
+from tests.gpu_support import assert_ranks_ok, export_mesh, launch_ranks, scene_model
+from tests.gpu_support import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 TH, TW = 24, 32                          # IS_TH, IS_TW of nerfmeshes_amd/csrc/image_ssim.hip
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 def _dev(a):
@@ -165,14 +155,7 @@ def test_mesh_render_scores_with_ssim_only_when_asked(ops, tmp_path):
 
 @pytest.fixture(scope="module")
 def scene(ops):
-    from nerfmeshes_amd import models
-    model = models.NeRFModel(S.hparams(chunksize=1500))
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
+    return scene_model("cuda", chunksize=1500)
 
 
 def test_eval_views_fills_the_metrics_and_is_silent_without(ops, scene):
@@ -206,17 +189,14 @@ def test_eval_views_fills_the_metrics_and_is_silent_without(ops, scene):
 
 def test_the_exporter_adds_the_columns_only_with_render_ssim(ops, scene, tmp_path):
     import json
-    from nerfmeshes_amd import mesh_nerf, mesh_render
+    from nerfmeshes_amd import mesh_render
     reports, texts = {}, {}
     for tag, extra in (("plain", []), ("ssim", ["--render-ssim"])):
         d = tmp_path / tag
         d.mkdir()
-        args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), "--view-disparity-max-bound", "1.0", "--batch-size", "4096",
-                                                    "--res", "48", "--iso-level", "32", "--render-views", "2", "--render-size", "64",
-                                                    *extra])
         text = io.StringIO()
-        with torch.no_grad(), contextlib.redirect_stdout(text):
-            v, f, _, c = mesh_nerf.export_marching_cubes(scene, args, scene.cfg, "cuda")
+        with contextlib.redirect_stdout(text):
+            v, f, _, c = export_mesh(scene, d, "--res", "48", "--render-views", "2", "--render-size", "64", *extra)
         reports[tag], texts[tag] = json.load(open(d / "mesh.render.json")), text.getvalue().replace(str(d), "")
     assert [tuple(sorted(r)) for r in reports["plain"]["views"]] == [tuple(sorted(TODAYS_ROW))] * 2 and "SSIM" not in texts["plain"]
     rows = reports["ssim"]["views"]
@@ -241,24 +221,9 @@ def test_the_exporter_adds_the_columns_only_with_render_ssim(ops, scene, tmp_pat
 
 # ---- two ranks ---------------------------------------------------------------------------------------------------------------
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 def test_two_ranks_sharing_one_gpu_equal_one_rank():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
     world = 2
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "ssim_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"SSIM_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "ssim_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"SSIM_DIST_OK world={world}")

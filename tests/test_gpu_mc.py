@@ -7,16 +7,9 @@ import torch
 
 from oracle import mc_oracle
 from tests.helpers import load_golden
+from tests.gpu_support import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 def _same(a, b):

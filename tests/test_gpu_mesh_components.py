@@ -4,36 +4,17 @@
 adversarial connectivity built as index arrays, canonical labels under a permutation of the faces, and the exporter end to
 end -- geometry, normals and colours of the kept vertices bit for bit the unfiltered run's rows, the cache, 2 ranks against 1."""
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from nerfmeshes_amd import synthetic as S
 from tests import mesh_components as MC
 from tests.helpers import load_golden
+from tests.gpu_support import assert_ranks_ok, export_mesh, launch_ranks, to_device as _dev, to_numpy as _np
+from tests.gpu_support import ops, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _np(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def _same_filter(got, want, tag):
@@ -213,28 +194,10 @@ def test_labels_do_not_depend_on_face_order_and_runs_repeat(ops, kind):
         assert roots > 3, "the noise volume is there to give the races many trees to merge"
 
 
-@pytest.fixture(scope="module")
-def scene():
-    from nerfmeshes_amd import models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
-
-
 def _run(model, tmp_path, tag, *extra):
-    from nerfmeshes_amd import mesh_nerf
     d = tmp_path / tag
     d.mkdir(exist_ok=True)
-    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), "--view-disparity-max-bound", "1.0", "--batch-size", "4096",
-                                                "--res", "64", "--iso-level", "32", *extra])
-    with torch.no_grad():
-        return mesh_nerf.export_marching_cubes(model, args, model.cfg, "cuda"), d
+    return export_mesh(model, d, "--res", "64", *extra), d
 
 
 FILTER = ["--min-component-faces", "100", "--keep-largest", "2"]
@@ -288,24 +251,9 @@ def test_cache_keeps_the_unfiltered_geometry(ops, scene, tmp_path):
     assert 0 < f3.shape[0] < f1.shape[0]
 
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 def test_two_ranks_sharing_one_gpu_equal_one_rank():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
     world = 2
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "cc_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"CC_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "cc_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"CC_DIST_OK world={world}")

@@ -5,32 +5,18 @@ validation hook, and 2 / 3 ranks against 1."""
 import json
 import math
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from nerfmeshes_amd import synthetic as S
 from tests import mesh_metrics as MM
 from tests.helpers import load_golden
+from tests.gpu_support import assert_ranks_ok, launch_ranks, scene_model, to_device as _dev
+from tests.gpu_support import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
 
 
 def _np(t):
@@ -328,18 +314,7 @@ def test_chamfer_identities_and_the_fp64_mean(ops, sphere_clouds):
 
 # ---- end to end ----------------------------------------------------------------------------------
 def _scene(**experiment):
-    from nerfmeshes_amd import models
-    hp = S.hparams(chunksize=3000)
-    for k, v in experiment.items():
-        hp[f"experiment.{k}"] = v
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
+    return scene_model("cuda", chunksize=3000, **{f"experiment.{k}": v for k, v in experiment.items()})
 
 
 @pytest.fixture(scope="module")
@@ -507,24 +482,9 @@ def test_validation_epoch_end_skips_a_grid_without_a_surface(ops, own_mesh, monk
 
 
 # ---- ranks ---------------------------------------------------------------------------------------
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 @pytest.mark.parametrize("world", [2, 3])
 def test_ranks_sharing_one_gpu_equal_one_rank(world):
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "chamfer_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"CHAMFER_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "chamfer_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"CHAMFER_DIST_OK world={world}")

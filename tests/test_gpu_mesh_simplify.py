@@ -4,36 +4,17 @@ an exact integer sum and every fp operation is rounded on its own, so every comp
 adversarial index and coordinate arrays, the same bytes run after run and under a renumbering, and the exporter end to end --
 the cache, 2 ranks against 1.  Both insertion variants (lane atomics, wave aggregation) are held to the same bytes."""
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from nerfmeshes_amd import synthetic as S
 from tests import mesh_simplify as MS
 from tests.helpers import load_golden
+from tests.gpu_support import assert_ranks_ok, export_mesh, launch_ranks, to_device as _dev, to_numpy as _np
+from tests.gpu_support import ops, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _np(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def _same(got, want, tag):
@@ -240,31 +221,13 @@ def test_runs_repeat_and_the_numbering_does_not_matter(ops, kind):
     assert rows(other[0]).tobytes() == rows(first[0]).tobytes(), "the same set of vertex rows, bit for bit"
 
 
-@pytest.fixture(scope="module")
-def scene():
-    from nerfmeshes_amd import models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
-
-
 LIMIT, RES = 1.2, 64
 
 
 def _run(model, tmp_path, tag, *extra):
-    from nerfmeshes_amd import mesh_nerf
     d = tmp_path / tag
     d.mkdir(exist_ok=True)
-    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), "--view-disparity-max-bound", "1.0", "--batch-size", "4096",
-                                                "--res", str(RES), "--iso-level", "32", "--limit", str(LIMIT), *extra])
-    with torch.no_grad():
-        return mesh_nerf.export_marching_cubes(model, args, model.cfg, "cuda"), d
+    return export_mesh(model, d, "--res", str(RES), "--limit", str(LIMIT), *extra), d
 
 
 def _restated(v0, f0, n0, k):
@@ -325,24 +288,9 @@ def test_cache_keeps_the_unsimplified_geometry(ops, scene, tmp_path):
     assert 0 < f3.shape[0] < f1.shape[0]
 
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 def test_two_ranks_sharing_one_gpu_equal_one_rank():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
     world = 2
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "simplify_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"SIMPLIFY_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "simplify_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"SIMPLIFY_DIST_OK world={world}")

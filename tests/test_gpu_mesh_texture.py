@@ -8,9 +8,6 @@ import contextlib
 import io
 import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,22 +17,11 @@ from nerfmeshes_amd import synthetic as S
 from tests import mesh_metrics as MM
 from tests import mesh_texture as MT
 from tests.test_mesh_raster import SPHERE_VIEWS, reject_mesh, sheet
+from tests.gpu_support import assert_ranks_ok, export_args, export_mesh, launch_ranks, to_device as _dev
+from tests.gpu_support import ops, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
 
 
 def _np(t):
@@ -220,33 +206,16 @@ def test_render_mesh_draws_the_texture_and_keeps_the_vertex_path(ops):
         mesh_render.render_mesh(verts, faces, colors, pose, 48, 48, 60.0, 0.1, BACKGROUND, texture=(uv[:5], atlas))
 
 
-@pytest.fixture(scope="module")
-def scene():
-    from nerfmeshes_amd import models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
-
-
-COMMON = ["--view-disparity-max-bound", "1.0", "--batch-size", "4096", "--res", "48", "--iso-level", "32", "--limit", "1.2",
-          "--simplify-cell", "2"]
+COMMON = ["--res", "48", "--limit", "1.2", "--simplify-cell", "2"]
 SIZE = 80
 
 
 def _run(model, tmp, tag, *extra):
-    from nerfmeshes_amd import mesh_nerf
     d = tmp / tag
     d.mkdir(exist_ok=True)
-    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), *COMMON, *extra])
     text = io.StringIO()
-    with torch.no_grad(), contextlib.redirect_stdout(text):
-        out = mesh_nerf.export_marching_cubes(model, args, model.cfg, "cuda")
+    with contextlib.redirect_stdout(text):
+        out = export_mesh(model, d, *COMMON, *extra)
     return out, d, text.getvalue()
 
 
@@ -275,7 +244,7 @@ def test_the_exporter_writes_a_textured_obj_and_scores_it(ops, scene, exported):
     assert f"{num_faces * 15} samples" in text
     # the image is the fill of the network's colours at the samples, queried as the vertices are
     from nerfmeshes_amd import mesh_nerf
-    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), *COMMON, "--texture-res", "4"])
+    args = export_args(d, *COMMON, "--texture-res", "4")
     positions, directions, fallback, bad = ops.mesh_texture_samples(v, f.to(torch.int32), n, 4, flip=mesh_nerf.SMOOTH_FLIP)
     assert bad == 0 and f"{fallback} with the face's own normal" in text
     with torch.no_grad():
@@ -337,24 +306,9 @@ def test_mesh_render_on_the_written_files_reproduces_the_report(ops, scene, expo
     assert plain["mesh"]["appearance"] == "vertex"
 
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 def test_two_ranks_sharing_one_gpu_equal_one_rank():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
     world = 2
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "texture_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"TEXTURE_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "texture_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"TEXTURE_DIST_OK world={world}")

@@ -8,9 +8,6 @@ import ctypes as C
 import io
 import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,27 +18,12 @@ from tests import mesh_visibility as MV
 from tests.test_gpu_mesh_raster import soup
 from tests.test_mesh_raster import reject_mesh
 from tests.test_mesh_visibility import NESTED, framed, nested, small_cases, vertex_normals, windowed_shell  # noqa: F401
+from tests.gpu_support import assert_ranks_ok, export_mesh, launch_ranks, to_device as _dev, to_numpy as _np
+from tests.gpu_support import ops, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 NAMES = ("verts", "faces", "normals", "face_index")
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
-
-
-def _dev(a, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def _np(t):
-    return None if t is None else t.cpu().numpy()
 
 
 def _views(ops, camera):
@@ -220,29 +202,12 @@ def test_the_rasteriser_is_unchanged_afterwards(ops, nested):  # noqa: F811
     assert raster[3] == restated[3] and all(_np(a).tobytes() == b.tobytes() for a, b in zip(raster[:3], restated[:3]))
 
 
-@pytest.fixture(scope="module")
-def scene():
-    from nerfmeshes_amd import models, synthetic as S
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
-
-
 def _run(model, tmp_path, tag, *extra):
-    from nerfmeshes_amd import mesh_nerf
     d = tmp_path / tag
     d.mkdir(exist_ok=True)
-    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), "--view-disparity-max-bound", "1.0", "--batch-size", "4096",
-                                                "--res", "64", "--iso-level", "32", "--limit", "1.2", *extra])
     text = io.StringIO()
-    with torch.no_grad(), contextlib.redirect_stdout(text):
-        mesh_nerf.export_marching_cubes(model, args, model.cfg, "cuda")
+    with contextlib.redirect_stdout(text):
+        export_mesh(model, d, "--res", "64", "--limit", "1.2", *extra)
     return d, text.getvalue()
 
 
@@ -269,24 +234,9 @@ def test_end_to_end_through_the_exporter(scene, tmp_path):
     print(text)
 
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 def test_two_ranks_sharing_one_gpu_equal_one_rank():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
     world = 2
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "visibility_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"VISIBILITY_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "visibility_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"VISIBILITY_DIST_OK world={world}")

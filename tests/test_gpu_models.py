@@ -8,6 +8,7 @@ import torch
 
 from nerfmeshes_amd import synthetic as S
 from oracle import mc_oracle, nerf_oracle as O
+from tests.gpu_support import scene_model
 from tests.helpers import (BUNDLE_KEYS, well_conditioned_rays, gen_weights, golden_hparams, golden_weights, load_golden, mlp_kwargs,
                            specs_from_hparams)
 
@@ -276,9 +277,7 @@ def test_checkpoint_round_trip_and_layout(pkg, tmp_path):
     keys as the reference (54 entries for NeRFModel)."""
     import yaml
     hp = S.hparams()
-    m = pkg["models"].NeRFModel(hp)
-    _load(m, "model_coarse.", S.make_scene_weights())
-    _load(m, "model_fine.", S.make_scene_weights())
+    m = scene_model("cpu")
     keys = list(m.state_dict().keys())
     assert len(keys) == 54 and "model_fine.layers_xyz.4.weight" in keys and "sample_pdf.u" in keys
     assert "sampler.point_intervals" not in keys and "volume_renderer.one_e_10" in keys
@@ -407,12 +406,7 @@ def test_eval_nerf_loop_matches_oracle_bookkeeping(pkg):
     """eval_nerf mirror: per-view loss with the reference's float batch_count quirk (eval_nerf.py:57,76),
     dataset loss = mean over views, PSNR = -10 log10; rendered through model.query in ragged chunks."""
     from nerfmeshes_amd import eval_nerf as ev
-    hp = S.hparams(chunksize=1500)
-    m = pkg["models"].NeRFModel(hp)
-    w = S.make_scene_weights()
-    _load(m, "model_coarse.", w)
-    _load(m, "model_fine.", w)
-    m = m.eval().to("cuda")
+    m, w = scene_model("cuda", chunksize=1500), S.make_scene_weights()
     views = list(ev.synthetic_views(2, height=40, width=52, focal=70.0))
     with torch.no_grad():
         losses, total, psnr, rgb = ev.eval_views(m, views, m.cfg, "cuda")
@@ -444,12 +438,7 @@ def test_eval_dataset_psnr_many_views_vs_oracle(pkg):
     (tests/test_gpu_parity.py) and 32 768 rays in bench.py."""
     from nerfmeshes_amd import eval_nerf as ev
     from oracle import parity
-    hp = S.hparams()
-    m = pkg["models"].NeRFModel(hp)
-    w = S.make_scene_weights()
-    _load(m, "model_coarse.", w)
-    _load(m, "model_fine.", w)
-    m = m.eval().to("cuda")
+    m, w = scene_model("cuda"), S.make_scene_weights()
     h, wd, focal = 72, 64, S.LEGO_FOCAL_800 * 72 / 800.0
     spec, rs = O.MLPSpec(), O.RenderSpec()
     views, ref_losses = [], []

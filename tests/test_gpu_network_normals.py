@@ -3,7 +3,6 @@ fp64 autograd over the CPU oracle on every kernel family, exactly on an affine n
 offset or the chunking; the bf16x3 rejection and the weights guard; the mesh end to end (geometry untouched, normals
 = -g / |g| at the final vertices), a planar surface against the grid's exact normals, the CLI, and 2 / 3 ranks against 1."""
 import os
-import socket
 import subprocess
 import sys
 
@@ -13,6 +12,8 @@ import torch
 
 from nerfmeshes_amd import synthetic as S
 from oracle import nerf_oracle as O
+from tests.gpu_support import assert_ranks_ok, export_mesh, launch_ranks, scene_model
+from tests.gpu_support import ops, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,14 +26,6 @@ NETS = {"8x256": dict(num_layers=8, hidden_size=256, skip_step=4, num_encoding_f
                             use_viewdirs=False),
         "layerwise": dict(num_layers=4, hidden_size=768, skip_step=4, num_encoding_fn_xyz=10, num_encoding_fn_dir=4),
         "20 functions": dict(num_layers=4, hidden_size=128, skip_step=2, num_encoding_fn_xyz=20, num_encoding_fn_dir=4)}
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 def _points(n, seed):
@@ -166,28 +159,10 @@ def test_bf16x3_rejected_and_weights_guard(ops):
     assert torch.equal(after, fresh), "the gradient of the edited weights"
 
 
-@pytest.fixture(scope="module")
-def scene():
-    from nerfmeshes_amd import models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
-
-
 def _run(model, tmp_path, tag, *extra):
-    from nerfmeshes_amd import mesh_nerf
     d = tmp_path / tag
     d.mkdir()
-    args = mesh_nerf.build_parser().parse_args(["--save-dir", str(d), "--view-disparity-max-bound", "1.0", "--batch-size", "4096",
-                                                *extra])
-    with torch.no_grad():
-        return mesh_nerf.export_marching_cubes(model, args, model.cfg, "cuda"), d
+    return export_mesh(model, d, *extra), d                      # every caller sets its own --iso-level
 
 
 @pytest.mark.parametrize("res", [64, 96])
@@ -212,20 +187,12 @@ def test_planar_surface_matches_the_grid_normals(ops, tmp_path):
     """On the affine network the surface is a plane: the grid's central differences are exact there, so the network normals
     (-c / |c|, to 1e-5) and the grid normals agree -- the orientation end to end.  The grid normals carry the rounding of the
     fp32 density values they difference (sigma is a large sum minus its bias here): they agree to 1e-4."""
-    from nerfmeshes_amd import models
     kw = NETS["8x256"]
     w, c = _affine_weights(kw, seed=3, gain=40.0)
     sigma0 = O.mlp_forward({k: torch.as_tensor(v).double() for k, v in w.items()}, O.MLPSpec(**kw),
                            torch.zeros(1, 3, dtype=torch.float64), torch.zeros(1, 3, dtype=torch.float64), keep_graph=True)[0, 3]
     w["fc_alpha.bias"] = (w["fc_alpha.bias"] - np.float32(float(sigma0))).astype(np.float32)     # sigma(0) = 0: the plane through 0
-    hp = S.hparams(chunksize=3000)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in w.items():
-            sd[prefix + k] = torch.from_numpy(np.ascontiguousarray(v))
-    model.load_state_dict(sd)
-    model = model.eval().to("cuda")
+    model = scene_model("cuda", chunksize=3000, weights=w)
     common = ["--res", "32", "--iso-level", "0", "--no-view-dependence"]
     (v0, f0, n0, _), _ = _run(model, tmp_path, "grid", *common)
     (v, f, n, _), _ = _run(model, tmp_path, "network", *common, "--normals", "network")
@@ -280,24 +247,9 @@ def test_cli_writes_network_normals(ops, tmp_path):
     assert got.tobytes() == want.cpu().numpy().tobytes()
 
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 @pytest.mark.parametrize("world", [2, 3])
 def test_ranks_sharing_one_gpu_equal_one_rank(world):
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "nn_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"NN_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "nn_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"NN_DIST_OK world={world}")

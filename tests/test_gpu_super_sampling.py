@@ -3,8 +3,6 @@ the refinement kernel bitwise against the numpy restatement (tests/ss_refine.py)
 grid_query, the whole extract_geometry_with_super_sampling against the dense construction the reference sketched, the CLI,
 and 2 / 3 ranks against 1."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,17 +10,11 @@ import torch
 
 from nerfmeshes_amd import synthetic as S
 from tests import ss_refine
+from tests.gpu_support import assert_ranks_ok, launch_ranks
+from tests.gpu_support import ops, scene  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 def _volume(kind, shape, seed):
@@ -178,20 +170,6 @@ def test_sample_density_rejects_bf16x3(ops):
         mlp.sample_density(torch.zeros(64, 3, device="cuda"))
 
 
-@pytest.fixture(scope="module")
-def scene():
-    from nerfmeshes_amd import models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
-
-
 def _args(res, ss, *extra):
     from nerfmeshes_amd import mesh_nerf
     return mesh_nerf.build_parser().parse_args(["--res", str(res), "--super-sampling", str(ss), "--iso-level", "32", *extra])
@@ -285,25 +263,9 @@ def test_cli_writes_the_refined_coloured_obj(ops, tmp_path):
         mesh_nerf.main(common + ["--mesh-name", "script.obj", "--super-sampling", "2", "--route", "script"])
 
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 @pytest.mark.parametrize("world", [2, 3])
 def test_ranks_sharing_one_gpu_equal_one_rank(world):
-    import socket
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "ss_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"SS_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "ss_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"SS_DIST_OK world={world}")

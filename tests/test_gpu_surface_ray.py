@@ -4,7 +4,6 @@ reference filter (tests/surface_filter.py) bit for bit; (2) the reference rule e
 one rank, PLY files byte for byte; (5) the command line."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
@@ -14,18 +13,12 @@ import torch
 
 from nerfmeshes_amd import synthetic as S
 from tests import surface_filter as SF
+from tests.gpu_support import assert_ranks_ok, clean_env, launch_ranks, scene_model
+from tests.gpu_support import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [(1, 1), (3, 7), (97, 131), (800, 800)]       # no multiple of the 16 x 64 tile; smaller than the halo
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 # ---- inputs (CPU tensors; a case = origins (1|H*W, 3), dirs (H, W, 3), depth (H, W), dist_threshold) ----------------------
@@ -265,22 +258,13 @@ def test_gather_at_a_row_offset_and_within_the_capacity(ops):
 
 # ---- 2. the reference rule end to end on the device -------------------------------------------------------------------------
 
-def _model(weights, hp, device="cuda"):
-    from nerfmeshes_amd import models
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in weights.items():
-            if prefix + k in sd:
-                sd[prefix + k] = torch.from_numpy(np.ascontiguousarray(v))
-    model.load_state_dict(sd)
-    return model.eval().to(device)
+def _model(weights, **hparams):
+    return scene_model("cuda", weights=weights, **hparams)
 
 
 @pytest.fixture(scope="module")
 def scene():
-    return _model(S.make_scene_weights(), S.hparams(chunksize=3000))
+    return _model(S.make_scene_weights(), chunksize=3000)
 
 
 def _args(tmp_path, *extra):
@@ -404,10 +388,9 @@ def test_against_the_cpu_oracle_under_min_opacity(ops, tmp_path):
     assert share >= 0.99 and kept_stable >= 1000
 
     size = TINY["size"]
-    hp = S.hparams(hidden_size=kw["hidden_size"], num_layers=kw["num_layers"], skip_step=kw["skip_step"],
+    model = _model(w, hidden_size=kw["hidden_size"], num_layers=kw["num_layers"], skip_step=kw["skip_step"],
                    num_encoding_fn_xyz=kw["num_encoding_fn_xyz"], num_encoding_fn_dir=kw["num_encoding_fn_dir"],
                    num_coarse=TINY["coarse"], num_fine=TINY["fine"], near=TINY["near"], far=TINY["far"])
-    model = _model(w, hp)
     pose = S.pose_spherical(*TINY["pose"])
     args = _args(tmp_path, "--img-size", str(size), "--focal", str(1111.1111 * size / 800), "--min-opacity", str(TINY["min_opacity"]))
     with torch.no_grad():
@@ -452,28 +435,13 @@ def test_against_the_cpu_oracle_under_min_opacity(ops, tmp_path):
 
 # ---- 4. ranks -----------------------------------------------------------------------------------------------------------------
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 @pytest.mark.parametrize("world", [2, 3, 7])
 def test_ranks_sharing_one_gpu_write_the_one_rank_file(world):
     """5 views: a ragged split over 2 and 3 ranks, and 7 ranks with two of them idle"""
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "sr_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=700)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"SR_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "sr_dist_worker.py"), world, timeout=600)
+    assert_ranks_ok(r, f"SR_DIST_OK world={world}")
 
 
 # ---- 5. the command line --------------------------------------------------------------------------------------------------------
@@ -482,7 +450,7 @@ def _cli(tmp_path, vdir, name, *extra):
     cmd = ["timeout", "-k", "10", "600", sys.executable, "-m", "nerfmeshes_amd.mesh_surface_ray", "--log-checkpoint", vdir,
            "--save-dir", str(tmp_path), "--ply-name", name, "--img-size", "100", "--focal", str(1111.1111 * 100 / 800),
            "--views-y", "3", "--views-x", "2", *extra]
-    r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=700)
+    r = subprocess.run(cmd, cwd=ROOT, env=clean_env(), capture_output=True, text=True, timeout=700)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return SF.read_ply(tmp_path / name), r.stdout
 

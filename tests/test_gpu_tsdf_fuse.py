@@ -8,9 +8,6 @@ import contextlib
 import io
 import json
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,17 +15,10 @@ import torch
 
 from tests import tsdf_fuse as TF
 from tests.test_tsdf_fuse import GRIDS, IMAGES, TRUNC_KEPT, TRUNC_OCCLUDED, VIEW_COUNTS, edge_scene
+from tests.gpu_support import assert_ranks_ok, export_args, export_mesh, launch_ranks, scene_model
+from tests.gpu_support import ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a MI355X")
-    from nerfmeshes_amd import hip_ops
-    return hip_ops
 
 
 def _device(ops, scene, trunc, first=0, count=None):
@@ -106,34 +96,22 @@ def test_what_the_wrapper_refuses(ops):
 
 @pytest.fixture(scope="module")
 def model():
-    from nerfmeshes_amd import models, synthetic as S
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    return model.eval().to("cuda")
+    return scene_model("cuda", chunksize=3000)
 
 
 TSDF = ("--geometry", "tsdf", "--res", "24", "--tsdf-views", "6", "--tsdf-size", "48")
 
 
 def _parse(directory, *extra):
-    from nerfmeshes_amd import mesh_nerf
-    return mesh_nerf.build_parser().parse_args(["--save-dir", str(directory), "--view-disparity-max-bound", "1.0", "--batch-size", "4096",
-                                                "--iso-level", "32", "--limit", "1.2", *extra])
+    return export_args(directory, "--limit", "1.2", *extra)
 
 
 def _run(model, tmp_path, tag, *extra):
-    from nerfmeshes_amd import mesh_nerf
     d = tmp_path / tag
     d.mkdir(exist_ok=True)
     text = io.StringIO()
-    with torch.no_grad(), contextlib.redirect_stdout(text):
-        mesh_nerf.export_marching_cubes(model, _parse(d, *extra), model.cfg, "cuda")
+    with contextlib.redirect_stdout(text):
+        export_mesh(model, d, "--limit", "1.2", *extra)
     return d, text.getvalue()
 
 
@@ -191,26 +169,11 @@ def test_end_to_end_and_the_density_geometry_is_untouched(model, tmp_path):
     print(text)
 
 
-def _env():
-    env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
-        env.pop(k, None)
-    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    return env
-
-
 def test_two_ranks_sharing_one_gpu_equal_one_rank():
     """both --gather modes in one launch of the worker: the OBJ byte for byte, and the report byte for byte up to its last entry,
     the seconds, which no two runs share"""
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a MI355X")
     world = 2
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join("tests", "tools", "tsdf_dist_worker.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(_env(), NERFMESHES_RANKS_PER_GPU=str(world)), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
-    assert f"TSDF_DIST_OK world={world}" in r.stdout, r.stdout[-2000:]
+    r = launch_ranks(os.path.join("tests", "tools", "tsdf_dist_worker.py"), world, timeout=900)
+    assert_ranks_ok(r, f"TSDF_DIST_OK world={world}")

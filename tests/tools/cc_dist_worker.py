@@ -4,63 +4,33 @@
 `--super-sampling 2`, with both `--gather` modes.  Every rank filters the gathered mesh redundantly, so the vertex ranges and
 the colour all-gather see the filtered vertex count on every rank: mesh, normals, colours and the OBJ must be the 1-rank
 run's bit for bit.  Prints CC_DIST_OK on rank 0."""
-import contextlib
-import io
 import os
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from nerfmeshes_amd import dist as nd, synthetic as S  # noqa: E402
-
-
-def single_rank(fn):
-    """`fn` as a process outside any group runs it (nd.world() -> (0, 1)), on this rank."""
-    real = nd.world, nd.all_gather_rows
-    nd.world, nd.all_gather_rows = (lambda: (0, 1)), (lambda local, counts: local)
-    try:
-        return fn()
-    finally:
-        nd.world, nd.all_gather_rows = real
+from nerfmeshes_amd import dist as nd  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def main():
     rank, world, dev = nd.init_from_env()
-    from nerfmeshes_amd import mesh_nerf, models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = contextlib.redirect_stdout(io.StringIO())
+    model = gs.scene_model(dev, chunksize=3000)
     out = {}
     cases = {"plain": ["--res", "64"], "network": ["--res", "44", "--normals", "network"], "ss2": ["--res", "64", "--super-sampling", "2"]}
     for case, extra in cases.items():
         for tag, gather in (("triangles", "triangles"), ("grid", "grid"), ("one", "triangles"), ("all", "triangles")):
-            d = tempfile.mkdtemp(prefix=f"nm_cc_{rank}_{case}_{tag}_")
+            d = gs.rank_dir("cc", rank, case, tag)
             flt = [] if tag == "all" else ["--min-component-faces", "60", "--keep-largest", "2"]
-            args = mesh_nerf.build_parser().parse_args(["--save-dir", d, "--view-disparity-max-bound", "1.0", "--iso-level", "32",
-                                                        "--batch-size", "4096", "--gather", gather, *extra, *flt])
-            with torch.no_grad(), quiet:
-                run = lambda: mesh_nerf.export_marching_cubes(model, args, model.cfg, dev)   # noqa: E731
-                out[case, tag] = (single_rank(run) if tag in ("one", "all") else run()) + (d,)
+            with gs.quiet():
+                run = lambda: gs.export_mesh(model, d, "--gather", gather, *extra, *flt, device=dev)   # noqa: E731
+                out[case, tag] = (gs.single_rank(run) if tag in ("one", "all") else run()) + (d,)
         assert 0 < out[case, "one"][1].shape[0] < out[case, "all"][1].shape[0], f"{case}: the filter drops something, not everything"
         for multi in ("triangles", "grid"):
-            got, want = out[case, multi], out[case, "one"]
-            for name, a, b in zip(("vertices", "triangles", "normals"), got[:3], want[:3]):
-                assert a.shape == b.shape and torch.equal(a, b), f"{case}, --gather {multi}: {name} differ from the 1-rank mesh"
-            assert got[3].shape == want[3].shape and (got[3] == want[3]).all(), f"{case}, --gather {multi}: colours differ"
-            if rank == 0:
-                a = open(os.path.join(got[4], "mesh.obj"), "rb").read()
-                assert a == open(os.path.join(want[4], "mesh.obj"), "rb").read(), f"{case}, --gather {multi}: OBJ differs"
+            gs.same_export(out[case, multi], out[case, "one"], f"{case}, --gather {multi}", rank)
     torch.cuda.synchronize()
     if rank == 0:
         print(f"CC_DIST_OK world={world} faces={int(out['plain', 'one'][1].shape[0])} of {int(out['plain', 'all'][1].shape[0])}", flush=True)

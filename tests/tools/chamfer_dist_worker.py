@@ -12,16 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from nerfmeshes_amd import dist as nd  # noqa: E402
-
-
-def single_rank(fn):
-    """`fn` as a process outside any group runs it (nd.world() -> (0, 1)), on this rank."""
-    real = nd.world, nd.all_gather_rows
-    nd.world, nd.all_gather_rows = (lambda: (0, 1)), (lambda local, counts: local)
-    try:
-        return fn()
-    finally:
-        nd.world, nd.all_gather_rows = real
+from tests import gpu_support as gs  # noqa: E402
 
 
 def main():
@@ -32,7 +23,7 @@ def main():
     y = torch.from_numpy((rng.standard_normal((7_777, 3)) * 1.5 + 0.25).astype(np.float32)).to(dev)
     x[17] = float("nan")                                             # a row without a winner travels as +inf
     got = hip_ops.chamfer_distance(x, y)
-    want = single_rank(lambda: hip_ops.chamfer_distance(x, y))
+    want = gs.single_rank(lambda: hip_ops.chamfer_distance(x, y))
     for k in ("chamfer", "x_to_y", "y_to_x"):
         assert isinstance(got[k], float) and np.float64(got[k]).tobytes() == np.float64(want[k]).tobytes(), (rank, k, got[k], want[k])
     for k, n in (("dist2_x", 10_001), ("dist2_y", 7_777)):

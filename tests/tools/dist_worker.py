@@ -15,40 +15,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 from nerfmeshes_amd import dist as nd, hip_ops, synthetic as S  # noqa: E402
-
-
-def single_rank(fn):
-    """Run `fn` as a process outside any group would (nd.world() -> (0, 1)): the 1-rank result, computed on this rank."""
-    real = nd.world, nd.all_gather_rows
-    nd.world, nd.all_gather_rows = (lambda: (0, 1)), (lambda local, counts: local)
-    try:
-        return fn()
-    finally:
-        nd.world, nd.all_gather_rows = real
+from tests import gpu_support as gs  # noqa: E402
 
 
 def model_level_checks(rank, world, dev):
     """The three consumers of the sharding layer inside the package, each against its own single-rank result."""
-    import argparse
-    import contextlib
-    import io
-    import tempfile
-    from nerfmeshes_amd import eval_nerf, mesh_nerf, models
-    hp = S.hparams(chunksize=3000, train_perturb=True, train_noise_std=0.0)
-    torch.manual_seed(0)                                     # identical replicas on every rank
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = contextlib.redirect_stdout(io.StringIO())
+    from nerfmeshes_amd import eval_nerf
+    model = gs.scene_model(dev, chunksize=3000, train_perturb=True, train_noise_std=0.0)
 
     # (1) eval_nerf: 3 views on `world` ranks (ragged; with 2 ranks rank 1 holds one view), losses back in view order
     views = list(eval_nerf.synthetic_views(3, height=36, width=44, focal=60.0))
-    with torch.no_grad(), quiet:
-        l1, t1, _, _ = single_rank(lambda: eval_nerf.eval_views(model, views, model.cfg, dev))
+    with torch.no_grad(), gs.quiet():
+        l1, t1, _, _ = gs.single_rank(lambda: eval_nerf.eval_views(model, views, model.cfg, dev))
         ln, tn, _, _ = eval_nerf.eval_views(model, views, model.cfg, dev)
     assert len(ln) == 3 and all(float(a) == float(b) for a, b in zip(l1, ln)) and float(t1) == float(tn), "eval losses differ"
 
@@ -59,12 +37,10 @@ def model_level_checks(rank, world, dev):
     out = {}
     for tag, res, gather in (("n", "44", "triangles"), ("g", "44", "grid"), ("1", "44", "triangles"),
                              ("N", "100", "triangles"), ("I", "100", "triangles")):
-        d = tempfile.mkdtemp(prefix=f"nm_dist_{rank}_{tag}_")
-        args = mesh_nerf.build_parser().parse_args(["--res", res, "--save-dir", d, "--view-disparity-max-bound", "1.0",
-                                                    "--iso-level", "32", "--batch-size", "4096", "--gather", gather])
-        with torch.no_grad(), quiet:
-            run = lambda: mesh_nerf.export_marching_cubes(model, args, model.cfg, dev)   # noqa: E731
-            out[tag] = (single_rank(run) if tag in "1I" else run()) + (d,)
+        d = gs.rank_dir("dist", rank, tag)
+        with gs.quiet():
+            run = lambda: gs.export_mesh(model, d, "--res", res, "--gather", gather, device=dev)   # noqa: E731
+            out[tag] = (gs.single_rank(run) if tag in "1I" else run()) + (d,)
     for multi, single in (("n", "1"), ("g", "1"), ("N", "I")):
         for a, b in zip(out[multi][:3], out[single][:3]):
             assert a.shape == b.shape and torch.equal(a, b), f"sharded mesh ({multi}) differs from the 1-rank mesh"

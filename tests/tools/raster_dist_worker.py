@@ -6,48 +6,26 @@ import contextlib
 import io
 import os
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from nerfmeshes_amd import dist as nd, synthetic as S  # noqa: E402
-
-
-def single_rank(fn):
-    """`fn` as a process outside any group runs it (nd.world() -> (0, 1)), on this rank."""
-    real = nd.world, nd.all_gather_rows
-    nd.world, nd.all_gather_rows = (lambda: (0, 1)), (lambda local, counts: local)
-    try:
-        return fn()
-    finally:
-        nd.world, nd.all_gather_rows = real
+from nerfmeshes_amd import dist as nd  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def main():
     rank, world, dev = nd.init_from_env()
-    from nerfmeshes_amd import mesh_nerf, models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev, chunksize=3000)
     reports = {}
     for tag in ("many", "one"):
-        d = tempfile.mkdtemp(prefix=f"nm_raster_{rank}_{tag}_")
-        args = mesh_nerf.build_parser().parse_args(["--save-dir", d, "--view-disparity-max-bound", "1.0", "--iso-level", "32",
-                                                    "--batch-size", "4096", "--res", "48", "--render-views", "3",
-                                                    "--render-size", "64"])
+        d = gs.rank_dir("raster", rank, tag)
         text = io.StringIO()
-        with torch.no_grad(), contextlib.redirect_stdout(text):
-            run = lambda: mesh_nerf.export_marching_cubes(model, args, model.cfg, dev)   # noqa: E731
-            single_rank(run) if tag == "one" else run()
+        with contextlib.redirect_stdout(text):
+            run = lambda: gs.export_mesh(model, d, "--res", "48", "--render-views", "3", "--render-size", "64", device=dev)   # noqa: E731
+            gs.single_rank(run) if tag == "one" else run()
         assert "Mesh render: 3 views" in text.getvalue(), f"{tag}: the report lines"
         path = os.path.join(d, "mesh.render.json")
         reports[tag] = open(path, "rb").read() if (rank == 0 or tag == "one") else None

@@ -3,61 +3,30 @@
 the synthetic scene with both `--gather` modes -- refinement after the redundant marching cubes (grid), or of every slab's
 own vertices before the triangle all-gather (triangles) -- must give the 1-rank mesh, colours and OBJ bit for bit.
 Prints SS_DIST_OK on rank 0."""
-import contextlib
-import io
 import os
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from nerfmeshes_amd import dist as nd, synthetic as S  # noqa: E402
-
-
-def single_rank(fn):
-    """`fn` as a process outside any group runs it (nd.world() -> (0, 1)), on this rank."""
-    real = nd.world, nd.all_gather_rows
-    nd.world, nd.all_gather_rows = (lambda: (0, 1)), (lambda local, counts: local)
-    try:
-        return fn()
-    finally:
-        nd.world, nd.all_gather_rows = real
+from nerfmeshes_amd import dist as nd  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def main():
     rank, world, dev = nd.init_from_env()
-    from nerfmeshes_amd import mesh_nerf, models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = contextlib.redirect_stdout(io.StringIO())
+    model = gs.scene_model(dev, chunksize=3000)
     out = {}
     for res in ("44", "100"):
         for tag, gather in (("triangles", "triangles"), ("grid", "grid"), ("one", "triangles")):
-            d = tempfile.mkdtemp(prefix=f"nm_ss_{rank}_{res}_{tag}_")
-            args = mesh_nerf.build_parser().parse_args(["--res", res, "--save-dir", d, "--view-disparity-max-bound", "1.0",
-                                                        "--iso-level", "32", "--batch-size", "4096", "--gather", gather,
-                                                        "--super-sampling", "2"])
-            with torch.no_grad(), quiet:
-                run = lambda: mesh_nerf.export_marching_cubes(model, args, model.cfg, dev)   # noqa: E731
-                out[res, tag] = (single_rank(run) if tag == "one" else run()) + (d,)
+            d = gs.rank_dir("ss", rank, res, tag)
+            with gs.quiet():
+                run = lambda: gs.export_mesh(model, d, "--res", res, "--gather", gather, "--super-sampling", "2", device=dev)   # noqa: E731
+                out[res, tag] = (gs.single_rank(run) if tag == "one" else run()) + (d,)
         for multi in ("triangles", "grid"):
-            got, want = out[res, multi], out[res, "one"]
-            for name, a, b in zip(("vertices", "triangles", "normals"), got[:3], want[:3]):
-                assert a.shape == b.shape and torch.equal(a, b), f"res {res}, --gather {multi}: {name} differ from the 1-rank mesh"
-            assert got[3].shape == want[3].shape and (got[3] == want[3]).all(), f"res {res}, --gather {multi}: colours differ"
-            if rank == 0:
-                a = open(os.path.join(got[4], "mesh.obj"), "rb").read()
-                assert a == open(os.path.join(want[4], "mesh.obj"), "rb").read(), f"res {res}, --gather {multi}: OBJ differs"
+            gs.same_export(out[res, multi], out[res, "one"], f"res {res}, --gather {multi}", rank)
     torch.cuda.synchronize()
     if rank == 0:
         print(f"SS_DIST_OK world={world} vertices={int(out['100', 'one'][0].shape[0])}", flush=True)

@@ -8,7 +8,6 @@ import io
 import json
 import os
 import sys
-import tempfile
 
 import numpy as np
 import torch
@@ -16,33 +15,15 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from nerfmeshes_amd import dist as nd, synthetic as S  # noqa: E402
-from tests import mesh_metrics as MM  # noqa: E402
-
-
-def single_rank(fn):
-    """`fn` as a process outside any group runs it (nd.world() -> (0, 1)), on this rank."""
-    real = nd.world, nd.all_gather_rows
-    nd.world, nd.all_gather_rows = (lambda: (0, 1)), (lambda local, counts: local)
-    try:
-        return fn()
-    finally:
-        nd.world, nd.all_gather_rows = real
+from nerfmeshes_amd import dist as nd  # noqa: E402
+from tests import gpu_support as gs, mesh_metrics as MM  # noqa: E402
 
 
 def main():
     rank, world, dev = nd.init_from_env()
     from nerfmeshes_amd import mesh_render, models
     from nerfmeshes_amd.nerf.nerf_helpers import export_obj
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev, chunksize=3000)
 
     class Parser:
         checkpoint_path = "memory"
@@ -57,9 +38,9 @@ def main():
     verts, faces = MM.uv_sphere(24, 12)
     colors = np.random.default_rng(7).random((len(verts), 3), dtype=np.float32)
     reports = {}
-    d = tempfile.mkdtemp(prefix=f"nm_ssim_{rank}_")
+    d = gs.rank_dir("ssim", rank)
     obj = os.path.join(d, "sphere.obj")                        # one file for both runs: the report names it
-    with contextlib.redirect_stdout(io.StringIO()):
+    with gs.quiet():
         export_obj(verts, faces, colors, verts, obj)
     for tag in ("many", "one"):
         out = os.path.join(d, f"R_{tag}.json")
@@ -68,7 +49,7 @@ def main():
         text = io.StringIO()
         with contextlib.redirect_stdout(text):
             run = lambda: mesh_render.main(argv)   # noqa: E731
-            single_rank(run) if tag == "one" else run()
+            gs.single_rank(run) if tag == "one" else run()
         assert "Mesh render: 3 views" in text.getvalue() and "SSIM to the network" in text.getvalue(), f"{tag}: the report lines"
         reports[tag] = open(out, "rb").read() if (rank == 0 or tag == "one") else None
     nd.init_from_env, nd.shutdown = real_init, real_shutdown

@@ -11,8 +11,6 @@ scene, under HIP events after warm-up (median of --reps):
     python tests/tools/time_chamfer.py [--res 480] [--reps 21] [--cdist-reps 3] [--runs 3] [--out profiles/r10_chamfer.json]
 """
 import argparse
-import contextlib
-import io
 import json
 import os
 import sys
@@ -24,39 +22,12 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from nerfmeshes_amd import hip_ops, mesh_nerf, models, synthetic as S  # noqa: E402
+from nerfmeshes_amd import hip_ops, mesh_nerf  # noqa: E402
 from nerfmeshes_amd.nerf.nerf_helpers import export_obj  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 ROOF_FLOPS = 157.3e12          # packed fp32 vector peak of the MI355X
 FLOPS_PER_PAIR = 8             # three subtractions, three products, two additions
-
-
-def gpu_ms(fn, reps, warm=2):
-    """median of `reps` HIP-event timings of fn() on the current stream (`warm` warm-up calls first)"""
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return sorted(times)[len(times) // 2]
 
 
 def cdist_nearest(x, y, block_bytes=4 << 30):
@@ -81,28 +52,18 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
+    model = gs.scene_model(dev)
     common = ["--res", str(opt.res), "--iso-level", "32", "--limit", "1.2"]
     out = {"res": opt.res, "scene": "synthetic.make_scene_weights (8x256)", "iso_level": 32, "limit": 1.2, "reps": opt.reps,
            "device": torch.cuda.get_device_name(0), "roof_flops": ROOF_FLOPS, "flops_per_pair": FLOPS_PER_PAIR}
 
     def save():
         print(json.dumps(out), flush=True)
-        if opt.out:
-            os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-            with open(opt.out, "w") as fh:
-                fh.write(json.dumps(out, indent=1) + "\n")
+        gs.write_json(out, opt.out)
 
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(common)
-        with quiet():
+        with gs.quiet():
             v, f, n, _ = mesh_nerf.extract_geometry(model, dev, args)
         f = f.to(torch.int32)
         out.update(vertices=int(v.shape[0]), faces=int(f.shape[0]))
@@ -113,7 +74,7 @@ def main():
         for size in opt.sizes:
             x = hip_ops.mesh_sample_points(v, f, n=size, generator=gen)[0]
             y = hip_ops.mesh_sample_points(jittered, f, n=size, generator=gen)[0]
-            ms = gpu_ms(lambda: hip_ops.points_nearest(x, y), opt.reps)
+            ms = gs.gpu_ms(lambda: hip_ops.points_nearest(x, y), opt.reps)
             pairs = float(size) * float(size) / (ms * 1e-3)
             row = {"n": size, "m": size, "ms": ms, "pairs_per_s": pairs, "fraction_of_valu_roof": pairs * FLOPS_PER_PAIR / ROOF_FLOPS}
             out["nearest"][str(size)] = row
@@ -122,27 +83,27 @@ def main():
             cd2, cidx = cdist_nearest(x, y)
             row["cdist_index_agreement"] = float((cidx == idx.long()).float().mean())
             row["cdist_max_abs_dist2_difference"] = float((cd2 - d2).abs().max())
-            row["cdist_ms"] = gpu_ms(lambda: cdist_nearest(x, y), opt.cdist_reps, warm=1)
+            row["cdist_ms"] = gs.gpu_ms(lambda: cdist_nearest(x, y), opt.cdist_reps, warm=1)
             row["cdist_over_kernel"] = row["cdist_ms"] / ms
             save()
         u = torch.rand(1_000_000, 3, device=dev, generator=gen)
-        out["sample_1e6_ms"] = gpu_ms(lambda: hip_ops.mesh_sample_points(v, f, u=u), opt.reps)
-        out["face_weights_ms"] = gpu_ms(lambda: hip_ops.mesh_face_weights(v, f), opt.reps)
+        out["sample_1e6_ms"] = gs.gpu_ms(lambda: hip_ops.mesh_sample_points(v, f, u=u), opt.reps)
+        out["face_weights_ms"] = gs.gpu_ms(lambda: hip_ops.mesh_face_weights(v, f), opt.reps)
         save()
         # the whole export with and without the stage; the target is the plain mesh itself, written once
         tdir = tempfile.mkdtemp(prefix="nm_chamfer_target_")
         target = os.path.join(tdir, "target.obj")
-        with quiet():
+        with gs.quiet():
             export_obj(v.cpu(), f.cpu(), torch.zeros(0, 3), n.cpu(), target)
         for tag, extra in (("export_default", []), ("export_target_mesh", ["--target-mesh", target])):
             d = tempfile.mkdtemp(prefix="nm_chamfer_time_")
             a = mesh_nerf.build_parser().parse_args(common + ["--save-dir", d, *extra])
 
             def run():
-                with quiet():
+                with gs.quiet():
                     mesh_nerf.export_marching_cubes(model, a, model.cfg, dev)
 
-            out[tag] = {"wall_ms": wall_ms(run, opt.runs)}
+            out[tag] = {"wall_ms": gs.wall_ms(run, opt.runs)}
             save()
         t0 = time.perf_counter()
         from nerfmeshes_amd.nerf.nerf_helpers import load_obj
@@ -155,7 +116,7 @@ def main():
             from nerfmeshes_amd import mesh_chamfer
             mesh_chamfer.compare_meshes(v, f, tv, tf, samples=args_t.chamfer_samples, seed=0, device=dev)
 
-        out["chamfer_stage_without_reading_ms"] = wall_ms(stage, opt.runs)
+        out["chamfer_stage_without_reading_ms"] = gs.wall_ms(stage, opt.runs)
         out["stage_share_of_export"] = 1.0 - out["export_default"]["wall_ms"] / out["export_target_mesh"]["wall_ms"]
         save()
 

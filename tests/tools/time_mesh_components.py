@@ -6,13 +6,10 @@ without --keep-largest 1 (vertex counts beside the times, so the saved appearanc
     python tests/tools/time_mesh_components.py [--res 480] [--reps 21] [--runs 3] [--out profiles/r09_mesh_components.json]
 """
 import argparse
-import contextlib
-import io
 import json
 import os
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -20,35 +17,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from nerfmeshes_amd import hip_ops, mesh_nerf, models, synthetic as S  # noqa: E402
-
-
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (two warm-up calls first)"""
-    fn()
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return sorted(times)[len(times) // 2]
+from nerfmeshes_amd import hip_ops, mesh_nerf  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def host_filter(v, f, n, keep_largest):
@@ -81,20 +51,13 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
+    model = gs.scene_model(dev)
     common = ["--res", str(opt.res), "--iso-level", "32", "--limit", "1.2"]
     out = {"res": opt.res, "scene": "synthetic.make_scene_weights (8x256)", "iso_level": 32, "limit": 1.2, "reps": opt.reps,
            "device": torch.cuda.get_device_name(0)}
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(common)
-        with quiet():
+        with gs.quiet():
             v, f, n, _ = mesh_nerf.extract_geometry(model, dev, args)
         nv, nf = int(v.shape[0]), int(f.shape[0])
         labels, counts = hip_ops.mesh_components(f, nv)
@@ -104,24 +67,24 @@ def main():
         stage = lambda k, m=0: hip_ops.mesh_filter_components(v, f, n, min_faces=m, keep_largest=k)      # noqa: E731
         kept = stage(1)[5]
         out["keep_largest_1"] = kept
-        out["filter_ms"] = {f"keep_largest_{k}": gpu_ms(lambda: stage(k), opt.reps) for k in (1, 3, 16)}
-        out["filter_ms"]["min_faces_50"] = gpu_ms(lambda: stage(0, 50), opt.reps)
-        out["label_and_count_ms"] = gpu_ms(lambda: hip_ops._mesh_components(hip_ops._lib.load(), f, nv, nf), opt.reps)
+        out["filter_ms"] = {f"keep_largest_{k}": gs.gpu_ms(lambda: stage(k), opt.reps) for k in (1, 3, 16)}
+        out["filter_ms"]["min_faces_50"] = gs.gpu_ms(lambda: stage(0, 50), opt.reps)
+        out["label_and_count_ms"] = gs.gpu_ms(lambda: hip_ops._mesh_components(hip_ops._lib.load(), f, nv, nf), opt.reps)
         # the pieces of the labelling on a permuted copy of the faces (the same graph, another arrival order)
         perm = torch.randperm(nf, device=dev)
         fp = f[perm].contiguous()
-        out["label_and_count_ms_faces_permuted"] = gpu_ms(lambda: hip_ops._mesh_components(hip_ops._lib.load(), fp, nv, nf), opt.reps)
+        out["label_and_count_ms_faces_permuted"] = gs.gpu_ms(lambda: hip_ops._mesh_components(hip_ops._lib.load(), fp, nv, nf), opt.reps)
         moved = 4 * (3 * nf * 3 + nv * 8 + 2 * (kept["vertices_kept"] * 6 + kept["faces_kept"] * 3))
         out["bytes_moved_estimate"] = moved
         try:
             a = host_filter(v, f, n, 1)
             b = stage(1)
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]), "host and device filters differ"
-            out["host_scipy_ms"] = wall_ms(lambda: host_filter(v, f, n, 1), max(3, opt.reps // 4))
+            out["host_scipy_ms"] = gs.wall_ms(lambda: host_filter(v, f, n, 1), max(3, opt.reps // 4))
         except ImportError:
             out["host_scipy_ms"] = None
-        with quiet():
-            out["geometry_ms"] = wall_ms(lambda: mesh_nerf.extract_geometry(model, dev, args), opt.runs)
+        with gs.quiet():
+            out["geometry_ms"] = gs.wall_ms(lambda: mesh_nerf.extract_geometry(model, dev, args), opt.runs)
         out["filter_over_geometry"] = out["filter_ms"]["keep_largest_1"] / out["geometry_ms"]
         for tag, extra in (("export_default", []), ("export_keep_largest_1", ["--keep-largest", "1"]),
                            ("export_min_faces_50", ["--min-component-faces", "50"])):
@@ -130,16 +93,12 @@ def main():
             res = {}
 
             def run():
-                with quiet():
+                with gs.quiet():
                     res["v"] = mesh_nerf.export_marching_cubes(model, a, model.cfg, dev)[0].shape[0]
 
-            out[tag] = {"wall_ms": wall_ms(run, opt.runs), "vertices": int(res["v"])}
+            out[tag] = {"wall_ms": gs.wall_ms(run, opt.runs), "vertices": int(res["v"])}
         print(json.dumps(out), flush=True)
-    text = json.dumps(out, indent=1)
-    if opt.out:
-        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-        with open(opt.out, "w") as fh:
-            fh.write(text + "\n")
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

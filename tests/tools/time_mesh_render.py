@@ -10,10 +10,8 @@ of its own, and adds the per-kernel times (mr_vertices, mr_faces, mr_large, mr_r
     python tests/tools/time_mesh_render.py [--res 480] [--views 64] [--size 800] [--kernels] [--out profiles/r13_mesh_render.json]
 """
 import argparse
-import contextlib
 import csv
 import glob
-import io
 import json
 import os
 import subprocess
@@ -25,7 +23,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from nerfmeshes_amd import hip_ops, mesh_nerf, models, synthetic as S  # noqa: E402
+from nerfmeshes_amd import hip_ops, mesh_nerf, synthetic as S  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 KERNELS = ("mr_vertices", "mr_faces", "mr_large", "mr_resolve", "mr_interpolate")
 
@@ -82,13 +81,7 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev)
     limit, size = 1.2, opt.size
     focal = S.LEGO_FOCAL_800 * size / 800.0
     near = model.cfg.dataset.near / 4
@@ -97,7 +90,7 @@ def main():
            "size": size, "focal": focal, "near": near, "device": torch.cuda.get_device_name(0), "meshes": {}}
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(["--res", str(opt.res), "--iso-level", "32", "--limit", str(limit)])
-        with contextlib.redirect_stdout(io.StringIO()):
+        with gs.quiet():
             v, f, n, _ = mesh_nerf.extract_geometry(model, dev, args)
             sv, sf, _ = mesh_nerf.simplify_mesh(v, f, n, 4.0, args)
         for name, (mv, mf) in (("full", (v, f)), ("simplify_cell_4", (sv, sf))):
@@ -128,10 +121,7 @@ def main():
     if opt.kernels:
         out["kernels_full_and_simplified_all_thresholds"] = kernel_trace(opt)
         print(json.dumps(out["kernels_full_and_simplified_all_thresholds"]), flush=True)
-    if opt.out:
-        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-        with open(opt.out, "w") as fh:
-            fh.write(json.dumps(out, indent=1) + "\n")
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

@@ -7,36 +7,18 @@ so that the accuracy cost stands next to the time saved.  K = 0 is the export as
     python tests/tools/time_mesh_simplify.py [--res 480] [--reps 21] [--runs 3] [--out profiles/r11_mesh_simplify.json]
 """
 import argparse
-import contextlib
-import io
 import json
 import os
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from nerfmeshes_amd import hip_ops, mesh_chamfer, mesh_nerf, models, synthetic as S  # noqa: E402
-
-
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (two warm-up calls first)"""
-    fn()
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
+from nerfmeshes_amd import hip_ops, mesh_chamfer, mesh_nerf  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def torch_simplify(v, f, cell, origin):
@@ -77,14 +59,7 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
+    model = gs.scene_model(dev)
     limit = 1.2
     common = ["--res", str(opt.res), "--iso-level", "32", "--limit", str(limit), "--view-disparity-max-bound", "1e0"]
     out = {"res": opt.res, "scene": "synthetic.make_scene_weights (8x256)", "iso_level": 32, "limit": limit, "reps": opt.reps,
@@ -92,7 +67,7 @@ def main():
            "stage": {}, "export": {}}
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(common)
-        with quiet():
+        with gs.quiet():
             v, f, n, _ = mesh_nerf.extract_geometry(model, dev, args)
         out.update(vertices=int(v.shape[0]), faces=int(f.shape[0]))
         origin = (-limit,) * 3
@@ -101,61 +76,27 @@ def main():
             cell = k * (2.0 * limit / opt.res)
             row = {"cell_world": cell}
             for name, aggregate in (("lane_atomics_ms", False), ("wave_aggregated_ms", True)):
-                row[name] = gpu_ms(lambda: hip_ops.mesh_simplify(v, f, n, cell=cell, origin=origin, aggregate=aggregate), opt.reps)
+                row[name] = gs.gpu_ms(lambda: hip_ops.mesh_simplify(v, f, n, cell=cell, origin=origin, aggregate=aggregate), opt.reps)
             sv, sf, _, info = hip_ops.mesh_simplify(v, f, n, cell=cell, origin=origin)
             row["info"] = info
             tv, tf = torch_simplify(v, f, cell, origin_t)
             assert torch.equal(tf, sf) and tv.shape == sv.shape, "torch ops and the kernels disagree on the faces"
             row["torch_max_abs_position_difference"] = float((tv - sv).abs().max())
-            row["torch_ops_ms"] = gpu_ms(lambda: torch_simplify(v, f, cell, origin_t), max(3, opt.reps // 4))
+            row["torch_ops_ms"] = gs.gpu_ms(lambda: torch_simplify(v, f, cell, origin_t), max(3, opt.reps // 4))
             report = mesh_chamfer.compare_meshes(sv, sf, v, f, device=dev)
             row["chamfer_to_unsimplified"] = {key: report[key] for key in report if not isinstance(report[key], dict)}
             out["stage"][f"K={k:g}"] = row
             print(json.dumps({f"K={k:g}": row}), flush=True)
         if not opt.skip_export:
-            stages = {}
-
-            def timed(name, fn):
-                def wrapper(*a, **kw):
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    r = fn(*a, **kw)
-                    torch.cuda.synchronize()
-                    stages[name] = stages.get(name, 0.0) + 1e3 * (time.perf_counter() - t0)
-                    return r
-                return wrapper
-
-            real = mesh_nerf.extract_geometry, mesh_nerf.simplify_mesh, mesh_nerf.export_obj
-            mesh_nerf.extract_geometry = timed("geometry_ms", real[0])
-            mesh_nerf.simplify_mesh = timed("simplify_ms", real[1])
-            mesh_nerf.export_obj = timed("obj_ms", real[2])
-            try:
-                for k in [0.0] + list(opt.cells):
-                    d = tempfile.mkdtemp(prefix="nm_simplify_time_")
-                    a = mesh_nerf.build_parser().parse_args(common + ["--save-dir", d, "--simplify-cell", str(k)])
-                    runs = []
-                    for i in range(opt.runs + 1):                  # the first run warms up
-                        stages.clear()
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        with quiet():
-                            res = mesh_nerf.export_marching_cubes(model, a, model.cfg, dev)
-                        torch.cuda.synchronize()
-                        whole = 1e3 * (time.perf_counter() - t0)
-                        if i:
-                            runs.append(dict(stages, whole_ms=whole, appearance_and_rest_ms=whole - sum(stages.values())))
-                    runs.sort(key=lambda r: r["whole_ms"])
-                    out["export"][f"K={k:g}"] = {"median": runs[len(runs) // 2], "whole_ms_all_runs": [r["whole_ms"] for r in runs],
-                                                 "vertices": int(res[0].shape[0]), "faces": int(res[1].shape[0]),
-                                                 "obj_bytes": os.path.getsize(os.path.join(d, "mesh.obj"))}
-                    print(json.dumps({f"export K={k:g}": out["export"][f"K={k:g}"]}), flush=True)
-            finally:
-                mesh_nerf.extract_geometry, mesh_nerf.simplify_mesh, mesh_nerf.export_obj = real
-    text = json.dumps(out, indent=1)
-    if opt.out:
-        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-        with open(opt.out, "w") as fh:
-            fh.write(text + "\n")
+            stages = {"geometry_ms": "extract_geometry", "simplify_ms": "simplify_mesh", "obj_ms": "export_obj"}
+            for k in [0.0] + list(opt.cells):
+                d = tempfile.mkdtemp(prefix="nm_simplify_time_")
+                row, res = gs.time_export(model, common + ["--save-dir", d, "--simplify-cell", str(k)], opt.runs, stages, dev,
+                                          rest_key="appearance_and_rest_ms")
+                out["export"][f"K={k:g}"] = dict(row, vertices=int(res[0].shape[0]), faces=int(res[1].shape[0]),
+                                                 obj_bytes=os.path.getsize(os.path.join(d, "mesh.obj")))
+                print(json.dumps({f"export K={k:g}": out["export"][f"K={k:g}"]}), flush=True)
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

@@ -9,37 +9,19 @@ neighbour's row -- so that bytes / time can be held against the HBM rate.  N = 0
     python tests/tools/time_mesh_smooth.py [--res 480] [--reps 21] [--runs 3] [--out profiles/r12_mesh_smooth.json]
 """
 import argparse
-import contextlib
 import ctypes as C
-import io
 import json
 import os
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from nerfmeshes_amd import _lib, hip_ops, mesh_chamfer, mesh_nerf, models, synthetic as S  # noqa: E402
-
-
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (two warm-up calls first)"""
-    fn()
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
+from nerfmeshes_amd import _lib, hip_ops, mesh_chamfer, mesh_nerf  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def torch_adjacency(v, f):
@@ -77,21 +59,14 @@ def main():
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
+    model = gs.scene_model(dev)
     limit, lam, mu = 1.2, 0.5, -0.53
     common = ["--res", str(opt.res), "--iso-level", "32", "--limit", str(limit), "--view-disparity-max-bound", "1e0"]
     out = {"res": opt.res, "scene": "synthetic.make_scene_weights (8x256)", "iso_level": 32, "limit": limit, "reps": opt.reps,
            "runs": opt.runs, "device": torch.cuda.get_device_name(0), "lambda": lam, "mu": mu, "stage": {}, "export": {}}
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(common)
-        with quiet():
+        with gs.quiet():
             v, f, n, _ = mesh_nerf.extract_geometry(model, dev, args)
         v, f, n = v.contiguous(), f.to(torch.int32).contiguous(), n.contiguous()
         nv, nf = int(v.shape[0]), int(f.shape[0])
@@ -114,67 +89,33 @@ def main():
         edges = int(counts[0])
         step_bytes = nv * (12 + 12 + 4 + 8) + 2 * edges * (4 + 12)
         out.update(vertices=nv, faces=nf, edges=edges, boundary_vertices=int(counts[3]), workspace_bytes=int(ws.numel()),
-                   half_step_bytes=step_bytes, build_ms=gpu_ms(build, opt.reps))
+                   half_step_bytes=step_bytes, build_ms=gs.gpu_ms(build, opt.reps))
         adjacency = torch_adjacency(v, f)
-        out["torch_ops_build_ms"] = gpu_ms(lambda: torch_adjacency(v, f), max(3, opt.reps // 4))
+        out["torch_ops_build_ms"] = gs.gpu_ms(lambda: torch_adjacency(v, f), max(3, opt.reps // 4))
         print(json.dumps({key: out[key] for key in ("vertices", "faces", "edges", "build_ms", "torch_ops_build_ms")}), flush=True)
         for k in opt.iterations:
-            row = {"run_ms": gpu_ms(lambda: run(k), opt.reps)}
+            row = {"run_ms": gs.gpu_ms(lambda: run(k), opt.reps)}
             row["half_step_us"] = 1e3 * row["run_ms"] / (2 * k)
             row["half_step_gb_per_s"] = step_bytes / (row["half_step_us"] * 1e-6) / 1e9
             run(k)
-            row["normals_ms"] = gpu_ms(normals, opt.reps)
+            row["normals_ms"] = gs.gpu_ms(normals, opt.reps)
             tv = torch_run(v, adjacency, k, lam, mu)
             row["torch_max_abs_position_difference"] = float((tv - sv).abs().max())
-            row["torch_ops_run_ms"] = gpu_ms(lambda: torch_run(v, adjacency, k, lam, mu), max(3, opt.reps // 4))
+            row["torch_ops_run_ms"] = gs.gpu_ms(lambda: torch_run(v, adjacency, k, lam, mu), max(3, opt.reps // 4))
             row["largest_displacement_voxels"] = float(torch.linalg.vector_norm(sv - v, dim=1).max()) / (2.0 * limit / opt.res)
             report = mesh_chamfer.compare_meshes(sv, f, v, f, device=dev)
             row["chamfer_to_unsmoothed"] = {key: report[key] for key in report if not isinstance(report[key], dict)}
             out["stage"][f"N={k}"] = row
             print(json.dumps({f"N={k}": row}), flush=True)
         if not opt.skip_export:
-            stages = {}
-
-            def timed(name, fn):
-                def wrapper(*a, **kw):
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    r = fn(*a, **kw)
-                    torch.cuda.synchronize()
-                    stages[name] = stages.get(name, 0.0) + 1e3 * (time.perf_counter() - t0)
-                    return r
-                return wrapper
-
-            real = mesh_nerf.extract_geometry, mesh_nerf.smooth_mesh, mesh_nerf.export_obj
-            mesh_nerf.extract_geometry = timed("geometry_ms", real[0])
-            mesh_nerf.smooth_mesh = timed("smooth_ms", real[1])
-            mesh_nerf.export_obj = timed("obj_ms", real[2])
-            try:
-                for k in [0] + list(opt.iterations):
-                    d = tempfile.mkdtemp(prefix="nm_smooth_time_")
-                    a = mesh_nerf.build_parser().parse_args(common + ["--save-dir", d, "--smooth-iters", str(k)])
-                    runs = []
-                    for i in range(opt.runs + 1):                  # the first run warms up
-                        stages.clear()
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        with quiet():
-                            mesh_nerf.export_marching_cubes(model, a, model.cfg, dev)
-                        torch.cuda.synchronize()
-                        whole = 1e3 * (time.perf_counter() - t0)
-                        if i:
-                            runs.append(dict(stages, whole_ms=whole, appearance_and_rest_ms=whole - sum(stages.values())))
-                    runs.sort(key=lambda r: r["whole_ms"])
-                    out["export"][f"N={k}"] = {"median": runs[len(runs) // 2], "whole_ms_all_runs": [r["whole_ms"] for r in runs],
-                                               "obj_bytes": os.path.getsize(os.path.join(d, "mesh.obj"))}
-                    print(json.dumps({f"export N={k}": out["export"][f"N={k}"]}), flush=True)
-            finally:
-                mesh_nerf.extract_geometry, mesh_nerf.smooth_mesh, mesh_nerf.export_obj = real
-    text = json.dumps(out, indent=1)
-    if opt.out:
-        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-        with open(opt.out, "w") as fh:
-            fh.write(text + "\n")
+            stages = {"geometry_ms": "extract_geometry", "smooth_ms": "smooth_mesh", "obj_ms": "export_obj"}
+            for k in [0] + list(opt.iterations):
+                d = tempfile.mkdtemp(prefix="nm_smooth_time_")
+                row, _ = gs.time_export(model, common + ["--save-dir", d, "--smooth-iters", str(k)], opt.runs, stages, dev,
+                                        rest_key="appearance_and_rest_ms")
+                out["export"][f"N={k}"] = dict(row, obj_bytes=os.path.getsize(os.path.join(d, "mesh.obj")))
+                print(json.dumps({f"export N={k}": out["export"][f"N={k}"]}), flush=True)
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

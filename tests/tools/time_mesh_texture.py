@@ -7,36 +7,18 @@ what the texture costs stands next to what it is added to.
     python tests/tools/time_mesh_texture.py [--res 480] [--texture-res 8] [--reps 21] [--runs 3] [--out profiles/r14_mesh_texture.json]
 """
 import argparse
-import contextlib
-import io
 import json
 import os
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from nerfmeshes_amd import hip_ops, mesh_nerf, models, synthetic as S  # noqa: E402
-
-
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (two warm-up calls first)"""
-    fn()
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
+from nerfmeshes_amd import hip_ops, mesh_nerf, synthetic as S  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def main():
@@ -51,14 +33,7 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
+    model = gs.scene_model(dev)
     limit, n = 1.2, opt.texture_res
     common = ["--res", str(opt.res), "--iso-level", "32", "--limit", str(limit), "--view-disparity-max-bound", "1e0",
               "--simplify-cell", str(opt.simplify_cell)]
@@ -67,7 +42,7 @@ def main():
            "stage": {}, "export": {}}
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(common)
-        with quiet():
+        with gs.quiet():
             v, f, normals, _ = mesh_nerf.extract_geometry(model, dev, args)
             v, f, normals = mesh_nerf.simplify_mesh(v, f.to(torch.int32), normals, opt.simplify_cell, args)
         nv, nf = int(v.shape[0]), int(f.shape[0])
@@ -78,72 +53,38 @@ def main():
         stage = out["stage"]
         # bytes that must move: the faces and their corners' positions and normals once, 24 bytes out per sample
         moved = 12 * nf + 24 * nv + 24 * samples
-        ms = gpu_ms(lambda: hip_ops.mesh_texture_samples(v, f, normals, n, flip=mesh_nerf.SMOOTH_FLIP), opt.reps)
+        ms = gs.gpu_ms(lambda: hip_ops.mesh_texture_samples(v, f, normals, n, flip=mesh_nerf.SMOOTH_FLIP), opt.reps)
         stage["samples"] = {"ms": ms, "bytes": moved, "gb_per_s": moved / ms / 1e6, "includes": "two allocations and the count read-back"}
         colours = torch.rand(samples, 3, device=dev)
         moved = 12 * samples + 3 * texels                           # every colour in once, every texel out once
-        ms = gpu_ms(lambda: hip_ops.mesh_texture_fill(colours, nf, n), opt.reps)
+        ms = gs.gpu_ms(lambda: hip_ops.mesh_texture_fill(colours, nf, n), opt.reps)
         stage["fill"] = {"ms": ms, "bytes": moved, "gb_per_s": moved / ms / 1e6}
         atlas, uv = hip_ops.mesh_texture_fill(colours, nf, n), hip_ops.mesh_texture_uv(nf, n)
-        stage["uv"] = {"ms": gpu_ms(lambda: hip_ops.mesh_texture_uv(nf, n), opt.reps), "bytes": 24 * nf}
+        stage["uv"] = {"ms": gs.gpu_ms(lambda: hip_ops.mesh_texture_uv(nf, n), opt.reps), "bytes": 24 * nf}
         size = opt.img_size
         view = hip_ops.make_view(list(S.orbit_poses(4))[1], size, size, S.LEGO_FOCAL_800 * size / 800.0)
         raster = hip_ops.mesh_rasterize(v, f, view, 0.5)
         covered = raster[3]["covered"]
         moved = 16 * size * size + covered * (24 + 12) + 12 * size * size   # id + barycentrics, uv rows + 4 texels, rgb out
-        ms = gpu_ms(lambda: hip_ops.mesh_texture_lookup(raster, uv, atlas, (1.0, 1.0, 1.0)), opt.reps)
+        ms = gs.gpu_ms(lambda: hip_ops.mesh_texture_lookup(raster, uv, atlas, (1.0, 1.0, 1.0)), opt.reps)
         stage["lookup"] = {"ms": ms, "bytes": moved, "gb_per_s": moved / ms / 1e6, "pixels": size * size, "covered": covered}
         vertex_colours = torch.rand(nv, 3, device=dev)
-        stage["interpolate_vertex_colours"] = {"ms": gpu_ms(lambda: hip_ops.mesh_interpolate(raster, f, vertex_colours, (1.0, 1.0, 1.0)),
+        stage["interpolate_vertex_colours"] = {"ms": gs.gpu_ms(lambda: hip_ops.mesh_interpolate(raster, f, vertex_colours, (1.0, 1.0, 1.0)),
                                                             opt.reps)}
-        stage["rasterize"] = {"ms": gpu_ms(lambda: hip_ops.mesh_rasterize(v, f, view, 0.5), opt.reps)}
+        stage["rasterize"] = {"ms": gs.gpu_ms(lambda: hip_ops.mesh_rasterize(v, f, view, 0.5), opt.reps)}
         print(json.dumps({"stage": stage}), flush=True)
         if not opt.skip_export:
-            stages = {}
-
-            def timed(name, fn):
-                def wrapper(*a, **kw):
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    r = fn(*a, **kw)
-                    torch.cuda.synchronize()
-                    stages[name] = stages.get(name, 0.0) + 1e3 * (time.perf_counter() - t0)
-                    return r
-                return wrapper
-
-            names = ("extract_geometry", "simplify_mesh", "bake_texture", "export_obj", "export_obj_textured")
-            real = [getattr(mesh_nerf, name) for name in names]
-            for name, fn in zip(names, real):
-                setattr(mesh_nerf, name, timed(name + "_ms", fn))
-            try:
-                for tag, extra in (("vertex_colours", []), ("texture", ["--texture-res", str(n)]),
-                                   ("texture_no_view_dependence", ["--texture-res", str(n), "--no-view-dependence"]),
-                                   ("vertex_colours_no_view_dependence", ["--no-view-dependence"])):
-                    d = tempfile.mkdtemp(prefix="nm_texture_time_")
-                    a = mesh_nerf.build_parser().parse_args(common + ["--save-dir", d] + extra)
-                    runs = []
-                    for i in range(opt.runs + 1):                  # the first run warms up
-                        stages.clear()
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        with quiet():
-                            mesh_nerf.export_marching_cubes(model, a, model.cfg, dev)
-                        torch.cuda.synchronize()
-                        whole = 1e3 * (time.perf_counter() - t0)
-                        if i:
-                            runs.append(dict(stages, whole_ms=whole, vertex_appearance_and_rest_ms=whole - sum(stages.values())))
-                    runs.sort(key=lambda r: r["whole_ms"])
-                    out["export"][tag] = {"median": runs[len(runs) // 2], "whole_ms_all_runs": [r["whole_ms"] for r in runs],
-                                          "bytes": {name: os.path.getsize(os.path.join(d, name)) for name in sorted(os.listdir(d))}}
-                    print(json.dumps({f"export {tag}": out["export"][tag]}), flush=True)
-            finally:
-                for name, fn in zip(names, real):
-                    setattr(mesh_nerf, name, fn)
-    text = json.dumps(out, indent=1)
-    if opt.out:
-        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-        with open(opt.out, "w") as fh:
-            fh.write(text + "\n")
+            stages = {name + "_ms": name for name in ("extract_geometry", "simplify_mesh", "bake_texture", "export_obj",
+                                                      "export_obj_textured")}
+            for tag, extra in (("vertex_colours", []), ("texture", ["--texture-res", str(n)]),
+                               ("texture_no_view_dependence", ["--texture-res", str(n), "--no-view-dependence"]),
+                               ("vertex_colours_no_view_dependence", ["--no-view-dependence"])):
+                d = tempfile.mkdtemp(prefix="nm_texture_time_")
+                row, _ = gs.time_export(model, common + ["--save-dir", d] + extra, opt.runs, stages, dev,
+                                        rest_key="vertex_appearance_and_rest_ms")
+                out["export"][tag] = dict(row, bytes={name: os.path.getsize(os.path.join(d, name)) for name in sorted(os.listdir(d))})
+                print(json.dumps({f"export {tag}": out["export"][tag]}), flush=True)
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

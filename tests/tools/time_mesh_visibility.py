@@ -8,38 +8,20 @@ poses, the PSNR between the two images of every pose (inf: no pixel differs) and
     python tests/tools/time_mesh_visibility.py [--res 480] [--reps 11] [--runs 2] [--out profiles/r15_mesh_visibility.json]
 """
 import argparse
-import contextlib
 import ctypes as C
-import io
 import json
 import os
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from nerfmeshes_amd import _lib, hip_ops, mesh_nerf, mesh_render, models, synthetic as S  # noqa: E402
+from nerfmeshes_amd import _lib, hip_ops, mesh_nerf, mesh_render, synthetic as S  # noqa: E402
 from nerfmeshes_amd.nerf.nerf_helpers import load_obj_attributes  # noqa: E402
-
-
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (two warm-up calls first)"""
-    fn()
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
+from tests import gpu_support as gs  # noqa: E402
 
 
 def main():
@@ -54,14 +36,7 @@ def main():
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
     lib = _lib.load()
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
+    model = gs.scene_model(dev)
     limit, radius, rings = 1.2, 3.0, 1
     size = mesh_nerf.cull_size(opt.res)
     common = ["--res", str(opt.res), "--iso-level", "32", "--limit", str(limit), "--view-disparity-max-bound", "1e0"]
@@ -70,7 +45,7 @@ def main():
            "stage": {}, "export": {}}
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(common)
-        with quiet():
+        with gs.quiet():
             v, f, n, _ = mesh_nerf.extract_geometry(model, dev, args)
         v, f, n = v.contiguous(), f.to(torch.int32).contiguous(), n.contiguous()
         nv, nf = int(v.shape[0]), int(f.shape[0])
@@ -95,13 +70,13 @@ def main():
                 hip_ops.check(lib.nm_mesh_visibility_views(array, count, ptr(v), nv, ptr(f), nf, near, hip_ops.RASTER_LARGE_THRESHOLD, 1,
                                                            ptr(ws), ptr(new), ptr(counts), stream()), "nm_mesh_visibility_views")
 
-            row = {"views_ms": gpu_ms(run, opt.reps)}
+            row = {"views_ms": gs.gpu_ms(run, opt.reps)}
             row["ms_per_view"] = row["views_ms"] / count
-            row["select_ms"] = gpu_ms(select, opt.reps)                # includes its one host synchronisation
+            row["select_ms"] = gs.gpu_ms(select, opt.reps)                # includes its one host synchronisation
             kv, kf = kept[0].value, kept[1].value
             ov, on = torch.empty(kv, 3, device=dev), torch.empty(kv, 3, device=dev)
             of, oi = torch.empty(kf, 3, dtype=torch.int32, device=dev), torch.empty(kf, dtype=torch.int32, device=dev)
-            row["compact_ms"] = gpu_ms(lambda: hip_ops.check(lib.nm_mesh_visibility_compact(
+            row["compact_ms"] = gs.gpu_ms(lambda: hip_ops.check(lib.nm_mesh_visibility_compact(
                 ptr(ws), ptr(f), nf, nv, ptr(v), ptr(n), kv, kf, ptr(ov), ptr(of), ptr(on), ptr(oi), stream()),
                 "nm_mesh_visibility_compact"), opt.reps)
             totals = counts.sum(0).tolist()
@@ -110,56 +85,24 @@ def main():
             out["stage"][f"views={count}"] = row
             print(json.dumps({f"views={count}": {k: row[k] for k in row if k not in ("new_faces", "raster_counts")}}), flush=True)
         if not opt.skip_export:
-            stages = {}
-
-            def timed(name, fn):
-                def wrapper(*a, **kw):
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    r = fn(*a, **kw)
-                    torch.cuda.synchronize()
-                    stages[name] = stages.get(name, 0.0) + 1e3 * (time.perf_counter() - t0)
-                    return r
-                return wrapper
-
             textured = ["--simplify-cell", "4", "--texture-res", "8"]     # the texture row of the README: 45 samples per face
-            names = ("extract_geometry", "cull_hidden", "bake_texture", "render_report")
-            real = [getattr(mesh_nerf, name) for name in names]
-            for name, fn in zip(names, real):
-                setattr(mesh_nerf, name, timed(name + "_ms", fn))
-            try:
-                for tag, extra in (("plain", []), ("culled", ["--cull-hidden-views", str(opt.export_views)]),
-                                   ("plain_textured", textured),
-                                   ("culled_textured", textured + ["--cull-hidden-views", str(opt.export_views)]),
-                                   ("plain_render8", ["--render-views", "8"]),
-                                   ("culled_render8", ["--render-views", "8", "--cull-hidden-views", str(opt.export_views)])):
-                    d = tempfile.mkdtemp(prefix="nm_visibility_time_")
-                    a = mesh_nerf.build_parser().parse_args(common + ["--save-dir", d] + extra)
-                    runs = []
-                    loops = 1 if "render8" in tag else opt.runs + 1    # the first run warms up; the render runs are there for
-                    for i in range(loops):                             # their report, once
-                        stages.clear()
-                        torch.cuda.synchronize()
-                        t0 = time.perf_counter()
-                        with quiet():
-                            mesh_nerf.export_marching_cubes(model, a, model.cfg, dev)
-                        torch.cuda.synchronize()
-                        whole = 1e3 * (time.perf_counter() - t0)
-                        if i or loops == 1:
-                            runs.append(dict(stages, whole_ms=whole))
-                    runs.sort(key=lambda r: r["whole_ms"])
-                    row = {"median": runs[len(runs) // 2], "whole_ms_all_runs": [r["whole_ms"] for r in runs],
-                           "obj_bytes": os.path.getsize(os.path.join(d, "mesh.obj")), "dir": d}
-                    for name in ("visibility", "render"):
-                        path = os.path.join(d, f"mesh.{name}.json")
-                        if os.path.exists(path):
-                            report = json.load(open(path))
-                            row[name] = report["mean"] if name == "render" else {k: report[k] for k in report if k != "new_faces"}
-                    out["export"][tag] = row
-                    print(json.dumps({f"export {tag}": {k: row[k] for k in row if k != "dir"}}), flush=True)
-            finally:
-                for name, fn in zip(names, real):
-                    setattr(mesh_nerf, name, fn)
+            stages = {name + "_ms": name for name in ("extract_geometry", "cull_hidden", "bake_texture", "render_report")}
+            for tag, extra in (("plain", []), ("culled", ["--cull-hidden-views", str(opt.export_views)]),
+                               ("plain_textured", textured),
+                               ("culled_textured", textured + ["--cull-hidden-views", str(opt.export_views)]),
+                               ("plain_render8", ["--render-views", "8"]),
+                               ("culled_render8", ["--render-views", "8", "--cull-hidden-views", str(opt.export_views)])):
+                d = tempfile.mkdtemp(prefix="nm_visibility_time_")
+                once = "render8" in tag                                # the render runs are there for their report, once, cold
+                row, _ = gs.time_export(model, common + ["--save-dir", d] + extra, 1 if once else opt.runs, stages, dev, warm=not once)
+                row.update(obj_bytes=os.path.getsize(os.path.join(d, "mesh.obj")), dir=d)
+                for name in ("visibility", "render"):
+                    path = os.path.join(d, f"mesh.{name}.json")
+                    if os.path.exists(path):
+                        report = json.load(open(path))
+                        row[name] = report["mean"] if name == "render" else {k: report[k] for k in report if k != "new_faces"}
+                out["export"][tag] = row
+                print(json.dumps({f"export {tag}": {k: row[k] for k in row if k != "dir"}}), flush=True)
             # the two OBJs in image space: the 8 --render-views poses, vertex colours, the same rasteriser
             cfg = model.cfg
             background = (1.0,) * 3 if cfg.dataset.white_background else (0.0,) * 3
@@ -177,11 +120,7 @@ def main():
             print(json.dumps({"image_space": rows}), flush=True)
             for row in out["export"].values():
                 del row["dir"]
-    text = json.dumps(out, indent=1)
-    if opt.out:
-        os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-        with open(opt.out, "w") as fh:
-            fh.write(text + "\n")
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

@@ -6,12 +6,10 @@ and fraction of the fp32 MFMA peak, and the geometry stage (extract_geometry*) o
     python tests/tools/time_network_normals.py --stage-only [--ss 2]      # only the normals stage, for a rocprofv3 --kernel-trace run
 """
 import argparse
-import contextlib
-import io
+import functools
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -19,34 +17,8 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from benchlib.common import FP32_MFMA_PEAK_TFLOPS  # noqa: E402
-from nerfmeshes_amd import _lib, mesh_nerf, models, synthetic as S  # noqa: E402
-
-
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (one warm-up call first)"""
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return sorted(times)[len(times) // 2]
+from nerfmeshes_amd import _lib, mesh_nerf  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def executed_flop_per_point(net):
@@ -65,6 +37,9 @@ def executed_flop_per_point(net):
     return net.flops_per_sample(density_only=False) + 2 * macs
 
 
+gpu_ms = functools.partial(gs.gpu_ms, warm=1)                     # one warm-up call, as these figures were taken
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=480)
@@ -74,15 +49,8 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev)
     net = model.get_model().hip("f32")
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
     flop = executed_flop_per_point(net)
     out = {"res": opt.res, "scene": "synthetic.make_scene_weights (8x256)", "iso_level": 32, "limit": 1.2, "reps": opt.reps,
            "peak_tflops": FP32_MFMA_PEAK_TFLOPS, "device": torch.cuda.get_device_name(0), "kernel_variant": net.kernel_variant()[0],
@@ -93,7 +61,7 @@ def main():
             args = mesh_nerf.build_parser().parse_args(["--res", str(opt.res), "--iso-level", "32", "--limit", "1.2",
                                                         "--super-sampling", str(ss)])
             geometry = mesh_nerf.extract_geometry_with_super_sampling if ss >= 1 else mesh_nerf.extract_geometry
-            with quiet():
+            with gs.quiet():
                 v, f, n, _ = geometry(model, dev, args)
             stage = lambda: mesh_nerf.network_normals(net, v, n)      # noqa: E731
             if opt.stage_only:
@@ -109,8 +77,8 @@ def main():
             row["mean_cos_to_grid_normal"] = float((nn * n).sum(1).mean())
             row["tflops"] = row["vertices"] * flop / (row["density_gradient_ms"] * 1e-3) / 1e12
             row["frac_of_peak"] = row["tflops"] / FP32_MFMA_PEAK_TFLOPS
-            with quiet():
-                row["geometry_ms"] = wall_ms(lambda: geometry(model, dev, args), max(1, opt.reps // 2))
+            with gs.quiet():
+                row["geometry_ms"] = gs.wall_ms(lambda: geometry(model, dev, args), max(1, opt.reps // 2))
             row["normals_over_geometry"] = row["normals_ms"] / row["geometry_ms"]
             out["per_ss"].append(row)
             print(json.dumps(row), flush=True)
@@ -118,9 +86,7 @@ def main():
         return
     text = json.dumps(out, indent=1)
     print(text)
-    if opt.out:
-        with open(opt.out, "w") as fh:
-            fh.write(text + "\n")
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

@@ -5,13 +5,11 @@ whole extract_geometry* time for ss = 0 and every ss.
     python tests/tools/time_super_sampling.py [--res 480] [--ss 1 2 4] [--reps 5] [--out FILE.json]
 """
 import argparse
-import contextlib
+import functools
 import ctypes as C
-import io
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -19,35 +17,12 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from benchlib.common import FP32_MFMA_PEAK_TFLOPS  # noqa: E402
-from nerfmeshes_amd import _lib, hip_ops, mesh_nerf, models, synthetic as S  # noqa: E402
+from nerfmeshes_amd import _lib, hip_ops, mesh_nerf  # noqa: E402
 from nerfmeshes_amd.hip_ops import _ptr, _stream, check  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (one warm-up call first)"""
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
-
-
-def wall_ms(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        times.append(1e3 * (time.perf_counter() - t0))
-    return sorted(times)[len(times) // 2]
+gpu_ms = functools.partial(gs.gpu_ms, warm=1)                     # one warm-up call, as these figures were taken
 
 
 def main():
@@ -58,18 +33,11 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev)
     net = model.get_model().hip("f32")
     lib = _lib.load()
     res = opt.res
     nums = (res, res, res)
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
     args = mesh_nerf.build_parser().parse_args(["--res", str(res), "--iso-level", "32"])
     ax = mesh_nerf._axes(args, nums, dev)
     out = {"res": res, "scene": "synthetic.make_scene_weights (8x256)", "reps": opt.reps, "peak_tflops": FP32_MFMA_PEAK_TFLOPS,
@@ -77,11 +45,11 @@ def main():
     with torch.no_grad():
         density = net.grid_query(*ax, density_only=True).view(*nums)
         out["stages_ms"]["grid"] = gpu_ms(lambda: net.grid_query(*ax, density_only=True), opt.reps)
-        with quiet():
+        with gs.quiet():
             iso = mesh_nerf.extract_iso_level(density, args)
-            out["stages_ms"]["iso"] = wall_ms(lambda: mesh_nerf.extract_iso_level(density, args), opt.reps)
+            out["stages_ms"]["iso"] = gs.wall_ms(lambda: mesh_nerf.extract_iso_level(density, args), opt.reps)
         out["iso"] = float(iso)
-        out["stages_ms"]["mc"] = wall_ms(lambda: hip_ops.marching_cubes(density, iso), opt.reps)
+        out["stages_ms"]["mc"] = gs.wall_ms(lambda: hip_ops.marching_cubes(density, iso), opt.reps)
         # the key export alone: count + emit as hip_ops.marching_cubes does, then nm_mc_vertex_edges under events
         ws = torch.empty(int(lib.nm_mc_workspace_bytes(res, res, res)), dtype=torch.uint8, device=dev)
         nv, nf = C.c_int64(), C.c_int64()
@@ -96,8 +64,8 @@ def main():
                                                         "nm_mc_vertex_edges"), opt.reps)
         verts = views()[0]
         out["centre_vertices"] = int(((keys & 3) == 3).sum())
-        with quiet():
-            out["extract_geometry_ms_ss0"] = wall_ms(lambda: mesh_nerf.extract_geometry(model, dev, args), opt.reps)
+        with gs.quiet():
+            out["extract_geometry_ms_ss0"] = gs.wall_ms(lambda: mesh_nerf.extract_geometry(model, dev, args), opt.reps)
         flops = net.flops_per_sample(density_only=True)
         for ss in opt.ss:
             fine = [hip_ops.fine_axis(args.limit, n, ss) for n in nums]
@@ -113,8 +81,8 @@ def main():
             row["density_tflops"] = n_pts * flops / (t_density * 1e-3) / 1e12
             row["density_frac_of_peak"] = row["density_tflops"] / FP32_MFMA_PEAK_TFLOPS
             ss_args = mesh_nerf.build_parser().parse_args(["--res", str(res), "--iso-level", "32", "--super-sampling", str(ss)])
-            with quiet():
-                row["extract_geometry_ms"] = wall_ms(lambda: mesh_nerf.extract_geometry_with_super_sampling(model, dev, ss_args), opt.reps)
+            with gs.quiet():
+                row["extract_geometry_ms"] = gs.wall_ms(lambda: mesh_nerf.extract_geometry_with_super_sampling(model, dev, ss_args), opt.reps)
             row["extra_over_ss0"] = row["extract_geometry_ms"] / out["extract_geometry_ms_ss0"] - 1.0
             # what the dense grids of the reference's sketch would cost at the measured grid rate
             dense_points = sum((n - 1) * (ss + 1) + 1 for n in nums) * res * res
@@ -124,9 +92,7 @@ def main():
             print(json.dumps(row), flush=True)
     text = json.dumps(out, indent=1)
     print(text)
-    if opt.out:
-        with open(opt.out, "w") as fh:
-            fh.write(text + "\n")
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

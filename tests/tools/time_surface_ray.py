@@ -8,8 +8,6 @@ oracle comparison (tests/test_gpu_surface_ray.py::test_against_the_cpu_oracle_un
     python tests/tools/time_surface_ray.py [--size 800] [--reps 5] [--skip-full] [--skip-parity] [--out FILE.json]
 """
 import argparse
-import contextlib
-import io
 import json
 import os
 import subprocess
@@ -23,25 +21,14 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from benchlib.common import HBM_PEAK_GBS  # noqa: E402
-from nerfmeshes_amd import hip_ops, mesh_surface_ray as msr, models, synthetic as S  # noqa: E402
+from nerfmeshes_amd import hip_ops, mesh_surface_ray as msr, synthetic as S  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
-def gpu_ms(fn, reps, calls=1):
-    """median over `reps` windows of the HIP-event time of `calls` back-to-back fn() on the current stream, per call (one
-    warm-up window first)"""
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b) / calls)
-    return sorted(times)[len(times) // 2], min(times), max(times)
+def spread(fn, reps, calls=1):
+    """{median, min, max} over `reps` windows of `calls` back-to-back fn(), per call (one warm-up window first)"""
+    times = gs.gpu_times(fn, reps, warm=1, calls=calls)
+    return {"median": times[len(times) // 2], "min": times[0], "max": times[-1]}
 
 
 def torch_stage(origin, dirs, depth, rgb, size, step, dist_threshold, prob_threshold):
@@ -68,15 +55,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_surface_ray.json"))
     a = ap.parse_args()
     dev = torch.device("cuda")
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev, chunksize=3000)
     size = a.size
     tmp = tempfile.mkdtemp(prefix="nm_sr_time_")
     args = msr.build_parser().parse_args(["--save-dir", tmp, "--img-size", str(size), "--focal", str(1111.1111 * size / 800)])
@@ -86,7 +65,7 @@ def main():
     with torch.no_grad():
         bounds = torch.tensor([2.0, 6.0])
         render = lambda: model.query_view(torch.from_numpy(pose), size, size, args.focal, bounds)   # noqa: E731
-        res["render_ms"] = dict(zip(("median", "min", "max"), gpu_ms(render, max(3, a.reps // 2))))
+        res["render_ms"] = spread(render, max(3, a.reps // 2))
         out = render()
         o, d = hip_ops.view_rays(hip_ops.make_view(pose, size, size, args.focal))
         o = o[:1].contiguous()
@@ -103,8 +82,8 @@ def main():
             return hip_ops.surface_filter(o, d, out.depth_map, size, size, args.step_size, args.dist_threshold, mv)
 
         res["kept_pixels"] = kept
-        res["hip_stage_ms"] = dict(zip(("median", "min", "max"), gpu_ms(hip_stage, a.reps, calls=50)))
-        res["hip_filter_only_ms"] = dict(zip(("median", "min", "max"), gpu_ms(hip_filter, a.reps, calls=50)))
+        res["hip_stage_ms"] = spread(hip_stage, a.reps, calls=50)
+        res["hip_filter_only_ms"] = spread(hip_filter, a.reps, calls=50)
         t0 = time.perf_counter()
         for _ in range(20):
             f = hip_ops.surface_filter(o, d, out.depth_map, size, size, args.step_size, args.dist_threshold, mv)
@@ -112,7 +91,7 @@ def main():
         torch.cuda.synchronize()
         res["hip_stage_with_count_readback_wall_ms"] = 1e3 * (time.perf_counter() - t0) / 20
         ref = lambda: torch_stage(o, d, out.depth_map, out.rgb_map, size, args.step_size, args.dist_threshold, args.prob_threshold)   # noqa: E731
-        res["torch_stage_ms"] = dict(zip(("median", "min", "max"), gpu_ms(ref, a.reps, calls=5)))
+        res["torch_stage_ms"] = spread(ref, a.reps, calls=5)
         tp, tn, tc = ref()
         res["torch_stage_equals_hip"] = bool(torch.equal(tp, rows[0]) and torch.equal(tn, rows[1]) and torch.equal(tc, rows[2]))
         res["speedup_over_torch_stage"] = res["torch_stage_ms"]["median"] / res["hip_stage_ms"]["median"]
@@ -128,10 +107,9 @@ def main():
         res["stage_share_of_view"] = res["hip_stage_ms"]["median"] / (res["render_ms"]["median"] + res["hip_stage_ms"]["median"])
 
         if not a.skip_full:
-            quiet = contextlib.redirect_stdout(io.StringIO())
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            with quiet:
+            with gs.quiet():
                 v, nrm, c, cu = msr.export_ray_trace(model, args, model.cfg, dev)
             res["full_run"] = {"views": 32, "points": int(len(v)), "wall_s": time.perf_counter() - t0}
             for fmt in ("ascii", "binary"):
@@ -150,9 +128,7 @@ def main():
                            env=dict(os.environ, NERFMESHES_SURFACE_RAY_FIGURES=fig), capture_output=True, text=True)
         res["oracle_comparison"] = json.load(open(fig)) if os.path.exists(fig) else {"error": r.stdout[-2000:]}
         res["oracle_comparison"]["test_passed"] = r.returncode == 0
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(res, fh, indent=1)
+    gs.write_json(res, a.out)
     print(json.dumps(res, indent=1))
 
 

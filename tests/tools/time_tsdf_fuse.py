@@ -7,8 +7,6 @@ network's own renders.  A projection is counted as one voxel in one view; the fi
     python tests/tools/time_tsdf_fuse.py [--res 480] [--views 32] [--size 800] [--reps 11] [--out profiles/r17_tsdf_fuse.json]
 """
 import argparse
-import contextlib
-import io
 import json
 import os
 import sys
@@ -21,23 +19,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from nerfmeshes_amd import hip_ops, mesh_nerf, models, synthetic as S  # noqa: E402
-
-
-def gpu_ms(fn, reps):
-    """median of `reps` HIP-event timings of fn() on the current stream (two warm-up calls first)"""
-    fn()
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b))
-    return sorted(times)[len(times) // 2]
+from nerfmeshes_amd import hip_ops, mesh_nerf  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def torch_integrate(views, depth, opacity, axes, trunc, near, min_opacity):
@@ -90,30 +73,17 @@ def main():
     ap.add_argument("--out", default=None)
     opt = ap.parse_args()
     dev = torch.device("cuda:0")
-    model = models.NeRFModel(S.hparams())
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev)
     cfg = model.cfg
-    quiet = lambda: contextlib.redirect_stdout(io.StringIO())      # noqa: E731
     limit = 1.2
     common = ["--res", str(opt.res), "--iso-level", "32", "--limit", str(limit), "--view-disparity-max-bound", "1e0"]
     tsdf = ["--geometry", "tsdf", "--tsdf-views", str(opt.views), "--tsdf-size", str(opt.size)]
     out = {"res": opt.res, "scene": "synthetic.make_scene_weights (8x256)", "limit": limit, "views": opt.views, "size": opt.size,
            "reps": opt.reps, "device": torch.cuda.get_device_name(0)}
 
-    def save():
-        if opt.out:
-            os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
-            with open(opt.out, "w") as fh:
-                fh.write(json.dumps(out, indent=1) + "\n")
-
     with torch.no_grad():
         args = mesh_nerf.build_parser().parse_args(common + tsdf)
-        with quiet():                                              # the first view warms the render kernels up
+        with gs.quiet():                                              # the first view warms the render kernels up
             mesh_nerf.tsdf_render_views(model, mesh_nerf.build_parser().parse_args(common + tsdf[:2] + ["--tsdf-views", "1", "--tsdf-size",
                                                                                                        str(opt.size)]), cfg, dev)
         torch.cuda.synchronize()
@@ -129,22 +99,22 @@ def main():
         run = lambda: hip_ops.tsdf_integrate(views, depth, opacity, axes, trunc, near, min_opacity=min_opacity)   # noqa: E731
         got = run()
         voxels = opt.res ** 3
-        ms = gpu_ms(run, opt.reps)
+        ms = gs.gpu_ms(run, opt.reps)
         out["integrate"] = {"ms": ms, "projections": voxels * opt.views, "projections_per_s": voxels * opt.views / (ms * 1e-3),
                             "field_gb_per_s": 4 * voxels / (ms * 1e-3) / 1e9,
                             "counts": dict(zip(hip_ops.TSDF_COUNTS, (int(x) for x in got["counts"].tolist()))),
                             "hit_pixels": int(((opacity >= min_opacity) & torch.isfinite(depth) & (depth > 0)).sum()),
                             "pixels": int(depth.numel())}
         print(json.dumps({"render_s": out["render_s"], "integrate": out["integrate"]}), flush=True)
-        save()
+        gs.write_json(out, opt.out)
         want = torch_integrate(views, depth, opacity, axes, trunc, near, min_opacity)
         out["torch_ops"] = {"field_bytes_equal": bool(torch.equal(want[0].view(torch.int32), got["field"].view(torch.int32))),
                             "counts_equal": want[2].tolist() == got["counts"].tolist(),
                             "fields_differing": int((want[0].view(torch.int32) != got["field"].view(torch.int32)).sum())}
         del want
-        out["torch_ops"]["ms"] = gpu_ms(lambda: torch_integrate(views, depth, opacity, axes, trunc, near, min_opacity), 3)
+        out["torch_ops"]["ms"] = gs.gpu_ms(lambda: torch_integrate(views, depth, opacity, axes, trunc, near, min_opacity), 3)
         print(json.dumps({"torch_ops": out["torch_ops"]}), flush=True)
-        save()
+        gs.write_json(out, opt.out)
         del got, depth, opacity
         if not opt.skip_export:
             out["export"] = {}
@@ -154,7 +124,7 @@ def main():
                 a = mesh_nerf.build_parser().parse_args(common + extra + scoring + ["--save-dir", d])
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                with quiet():
+                with gs.quiet():
                     v, f, _, _ = mesh_nerf.export_marching_cubes(model, a, cfg, dev)
                 torch.cuda.synchronize()
                 row = {"whole_s": time.perf_counter() - t0, "vertices": int(v.shape[0]), "faces": int(f.shape[0]),
@@ -164,8 +134,8 @@ def main():
                     row["report"] = json.load(open(os.path.join(d, "mesh.tsdf.json")))
                 out["export"][name] = row
                 print(json.dumps({f"export {name}": row}), flush=True)
-                save()
-    save()
+                gs.write_json(out, opt.out)
+    gs.write_json(out, opt.out)
 
 
 if __name__ == "__main__":

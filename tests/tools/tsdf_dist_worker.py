@@ -7,24 +7,14 @@ import contextlib
 import io
 import os
 import sys
-import tempfile
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from nerfmeshes_amd import dist as nd, synthetic as S  # noqa: E402
-
-
-def single_rank(fn):
-    """`fn` as a process outside any group runs it (nd.world() -> (0, 1)), on this rank."""
-    real = nd.world, nd.all_gather_rows
-    nd.world, nd.all_gather_rows = (lambda: (0, 1)), (lambda local, counts: local)
-    try:
-        return fn()
-    finally:
-        nd.world, nd.all_gather_rows = real
+from nerfmeshes_amd import dist as nd  # noqa: E402
+from tests import gpu_support as gs  # noqa: E402
 
 
 def stable(report):
@@ -36,26 +26,15 @@ def stable(report):
 
 def main():
     rank, world, dev = nd.init_from_env()
-    from nerfmeshes_amd import mesh_nerf, models
-    hp = S.hparams(chunksize=3000)
-    torch.manual_seed(0)
-    model = models.NeRFModel(hp)
-    sd = model.state_dict()
-    for prefix in ("model_coarse.", "model_fine."):
-        for k, v in S.make_scene_weights().items():
-            sd[prefix + k] = torch.from_numpy(v)
-    model.load_state_dict(sd)
-    model = model.eval().to(dev)
+    model = gs.scene_model(dev, chunksize=3000)
     files = {}
     for tag, gather in (("triangles", "triangles"), ("grid", "grid"), ("one", "triangles")):
-        d = tempfile.mkdtemp(prefix=f"nm_tsdf_{rank}_{tag}_")
-        args = mesh_nerf.build_parser().parse_args(["--save-dir", d, "--view-disparity-max-bound", "1.0", "--iso-level", "32",
-                                                    "--batch-size", "4096", "--geometry", "tsdf", "--res", "24", "--tsdf-views", "6",
-                                                    "--tsdf-size", "48", "--gather", gather])
+        d = gs.rank_dir("tsdf", rank, tag)
         text = io.StringIO()
-        with torch.no_grad(), contextlib.redirect_stdout(text):
-            run = lambda: mesh_nerf.export_marching_cubes(model, args, model.cfg, dev)   # noqa: E731
-            single_rank(run) if tag == "one" else run()
+        with contextlib.redirect_stdout(text):
+            run = lambda: gs.export_mesh(model, d, "--geometry", "tsdf", "--res", "24", "--tsdf-views", "6",   # noqa: E731
+                                         "--tsdf-size", "48", "--gather", gather, device=dev)
+            gs.single_rank(run) if tag == "one" else run()
         assert "TSDF: 6 views of 48² fused into 24 x 24 x 24 voxels" in text.getvalue(), f"{tag}: the report line"
         if rank == 0 or tag == "one":
             files[tag] = [open(os.path.join(d, name), "rb").read() for name in ("mesh.obj", "mesh.tsdf.json")]
