@@ -63,6 +63,8 @@ extern "C" {
  * --ssim, mesh_nerf --render-ssim).  Additions only. */
 /* 6, later: + nm_tsdf_integrate (+ nm_tsdf_workspace_bytes): rendered depth maps fused into a truncated signed distance field,
  * bit for bit a closed rule (mesh_nerf --geometry tsdf).  Additions only. */
+/* 6, later: + nm_mesh_simplify_quadric_faces (+ nm_mesh_simplify_quadric_workspace_bytes), nm_mesh_simplify_emit_quadric:
+ * quadric-optimal cluster vertices from exact integer quadrics (mesh_nerf --simplify-placement quadric).  Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -817,6 +819,39 @@ int nm_points_nearest(const float* d_x, int64_t num_x, const float* d_y, int64_t
  * aligned; 64 bytes per slot of a table of the smallest power of two >= 2 V slots, 4 per slot of one of >= 2 F) must stay
  * untouched between the two calls.  Argument errors -- a null array with a non-zero size, a cell that is not finite or
  * <= 0, a non-finite origin -- return 2 before any HIP call.
+ *
+ * QUADRIC PLACEMENT (mesh_nerf --simplify-placement quadric): the clustering, the faces, the numbering, the normals and a
+ * cluster of one member are the above; only the position of a cluster of n >= 2 members changes, to the point of its cell
+ * nearest (least squares, area^2 weights) to the planes of the faces around it -- Lindstrom's quadric-optimal representative
+ * with integer quadrics.  c, lo, t, S and n are the above; MSQ_LATTICE = 2^8, MSQ_MAX_CONTRIBUTIONS = 2^13, MSQ_LAMBDA = 2^-6.
+ *   lattice   u = (int64) rint((double) t * 2^8) per axis, clamped to [-2^9, 2^9]: a vertex on a lattice local to its cell.
+ *   corner    every face that is not BAD contributes once per corner k, to the cluster of that corner.  With C = (int64) c:
+ *             e1 = (C1 - C0) * 2^8 + (u1 - u0), e2 likewise for the third corner, in the face's cyclic order starting at k.
+ *             A component of e1 or e2 beyond 2^9 in magnitude (two cells) makes the corner FAR: counted, no contribution.
+ *             Else nrm = e1 x e2 (|component| <= 2^19), d = -(nrm . u0) (|d| <= 3 * 2^28), and the corner adds the six
+ *             nrm_i nrm_j (<= 2^38) to A, the three nrm_i d (< 2^49) to B and 1 to the cluster's contributions.  A face
+ *             with two corners in one cluster adds twice; one with a repeated index adds zeros and counts.
+ *   crowded   a cluster with more than 2^13 contributions is CROWDED: its sums are not read, it gets the mean.  Below that
+ *             |sum A| <= 2^51 and |sum B| < 2^62: exact int64 sums in any order.
+ *   position  of a kept cluster with n >= 2, 1 <= contributions <= 2^13 and tr > 0, in fp64, every operation rounded on its own:
+ *               m_j = ((double) S_j / ((double) n * 2^30)) * 2^8;  a = (double) A, b = (double) B;  tr = (a00 + a11) + a22
+ *               M = a with tr * 2^-6 added to the diagonal;  r_j = -(((a_j0 m0 + a_j1 m1) + a_j2 m2) + b_j)
+ *               c00 = M11 M22 - M12 M12   c01 = M02 M12 - M01 M22   c02 = M01 M12 - M02 M11
+ *               c11 = M00 M22 - M02 M02   c12 = M01 M02 - M00 M12   c22 = M00 M11 - M01 M01
+ *               det = (M00 c00 + M01 c01) + M02 c02
+ *               delta0 = ((c00 r0 + c01 r1) + c02 r2) / det   delta1 = ((c01 r0 + c11 r1) + c12 r2) / det
+ *               delta2 = ((c02 r0 + c12 r1) + c22 r2) / det
+ *             det > 0 fails or a delta is not finite: SINGULAR, the mean.  Else x = m + delta, each component clamped to
+ *             [0, 2^8] (CLAMPED when a clamp acted), p = (float)((double) lo + (double) cell * (x / 2^8)): SOLVED.  The
+ *             regulariser bounds the condition number by about 200 and leaves the vertex at the mean along directions the
+ *             planes do not constrain (flat regions, open boundaries, a crease along itself).  0 contributions or tr = 0:
+ *             the mean, counted nowhere.
+ * nm_mesh_simplify_quadric_faces: after nm_mesh_simplify_cluster, with its workspace and THE SAME mesh and grid: zeroes the
+ *   second workspace (nm_mesh_simplify_quadric_workspace_bytes: 128 bytes per slot of the vertex table; 0 for sizes out of
+ *   range) and sums the corners' contributions into it.  flags as above.  No host synchronisation.
+ * nm_mesh_simplify_emit_quadric: nm_mesh_simplify_emit with the positions above; returns on the HOST (it synchronises the
+ *   stream) h_counts[NM_MESH_SIMPLIFY_QUADRIC_COUNTS]: the kept clusters that are SOLVED (the CLAMPED among them included),
+ *   CROWDED, SINGULAR and CLAMPED, and the FAR corners of all faces.  Both workspaces must stay untouched between the calls.
  * ------------------------------------------------------------------------------------------ */
 #define NM_MESH_SIMPLIFY_AGGREGATE 1
 #define NM_MESH_SIMPLIFY_CLUSTERS 0
@@ -835,6 +870,21 @@ int nm_mesh_simplify_emit(const void* d_workspace, const float* d_verts, int64_t
                           int64_t num_faces, const float* d_normals, float origin_x, float origin_y, float origin_z, float cell,
                           int64_t vertices_kept, int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces,
                           float* d_out_normals, void* stream);
+#define NM_MESH_SIMPLIFY_QUADRIC_SOLVED 0
+#define NM_MESH_SIMPLIFY_QUADRIC_CROWDED 1
+#define NM_MESH_SIMPLIFY_QUADRIC_SINGULAR 2
+#define NM_MESH_SIMPLIFY_QUADRIC_CLAMPED 3
+#define NM_MESH_SIMPLIFY_QUADRIC_FAR 4
+#define NM_MESH_SIMPLIFY_QUADRIC_COUNTS 5
+int64_t nm_mesh_simplify_quadric_workspace_bytes(int64_t num_vertices, int64_t num_faces);
+int nm_mesh_simplify_quadric_faces(const void* d_workspace, const float* d_verts, int64_t num_vertices, const int32_t* d_faces,
+                                   int64_t num_faces, float origin_x, float origin_y, float origin_z, float cell, int32_t flags,
+                                   void* d_quadric_workspace, void* stream);
+int nm_mesh_simplify_emit_quadric(const void* d_workspace, void* d_quadric_workspace, const float* d_verts, int64_t num_vertices,
+                                  const int32_t* d_faces, int64_t num_faces, const float* d_normals, float origin_x,
+                                  float origin_y, float origin_z, float cell, int64_t vertices_kept, int64_t faces_kept,
+                                  float* d_out_verts, int32_t* d_out_faces, float* d_out_normals, int64_t* h_counts,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Taubin smoothing of a mesh (mesh_nerf --smooth-iters; DESIGN.md, "Mesh smoothing").  All arrays on the device: d_verts

@@ -209,6 +209,12 @@ SIGNATURES = {
                                            C.c_float, C.c_int32, c_void_p, C.POINTER(C.c_int64), c_void_p]),
     "nm_mesh_simplify_emit": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float, C.c_float,
                                         C.c_float, C.c_float, C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_simplify_quadric_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "nm_mesh_simplify_quadric_faces": (C.c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, C.c_float, C.c_float,
+                                                 C.c_float, C.c_float, C.c_int32, c_void_p, c_void_p]),
+    "nm_mesh_simplify_emit_quadric": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float,
+                                                C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int64, c_void_p, c_void_p,
+                                                c_void_p, C.POINTER(C.c_int64), c_void_p]),
     "nm_mesh_smooth_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "nm_mesh_smooth_build": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.POINTER(C.c_int64), c_void_p]),
     "nm_mesh_smooth_run": (C.c_int, [c_void_p, c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_int32, c_void_p, c_void_p]),

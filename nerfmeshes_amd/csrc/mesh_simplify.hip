@@ -42,7 +42,34 @@
 //                         p = (float)((double) lo + (double) cell * ((double) S / ((double) n * 2^30)))
 //                         normal = s / sqrt((sx sx + sy sy) + sz sz) with s = (float) S per component, or the representative's
 //                                  own normal when S is the zero vector
-// The only host round trip is the one that returns the counts (nm_mesh_simplify_cluster).
+// QUADRIC PLACEMENT (mesh_nerf --simplify-placement quadric; nm_mesh_simplify_quadric_faces + nm_mesh_simplify_emit_quadric)
+// changes one thing: the position of a cluster of two or more members is the point of its cell that is closest, in the least
+// squares sense, to the planes of the faces around it (Lindstrom's quadric-optimal representative), not the members' mean.
+//   3b. ms_quadric_faces   one thread per face, whole waves, after steps 1-4.  A face that is not BAD contributes once per
+//                       corner k to the cluster of that corner, in integers, on a lattice of 2^8 points per cell edge that is
+//                       local to the corner's cell: u = (int64) rint((double) t * 2^8) per axis, clamped to [-2^9, 2^9]; with
+//                       C = (int64) c, e1 = (C1 - C0) * 2^8 + (u1 - u0) and e2 likewise for the third corner (cyclic order from
+//                       k).  An edge component beyond 2^9 (two cells) makes the corner FAR: counted, no contribution.
+//                       Else nrm = e1 x e2 (area^2 weighting), d = -(nrm . u0), and the corner adds the six nrm_i nrm_j, the
+//                       three nrm_i d and 1 to its cluster's row of a SECOND per-slot array (MsQuadric, 128 bytes; MsSlot stays
+//                       as it is) by agent-scope relaxed 64-bit adds -- the rule of ms_insert: every access to the shared array
+//                       inside the launch is such an atomic; zero addends are skipped.
+//                       Overflow: |e| <= 2^9 gives |nrm_i| <= 2 * 2^9 * 2^9 = 2^19, so |nrm_i nrm_j| <= 2^38; |u0| <= 2^9 gives
+//                       |d| <= 3 * 2^19 * 2^9 = 3 * 2^28 and |nrm_i d| <= 3 * 2^47 < 2^49.  The row counts its contributions
+//                       (64 bits: fewer than 3 * 2^31 corners exist).  A cluster that ends with more than 2^13 is CROWDED: its
+//                       sums are never read, it gets the mean, and whatever the adds wrapped to is irrelevant.  One that ends
+//                       with at most 2^13 saw exactly that many adds, so every partial |sum of A| <= 2^13 * 2^38 = 2^51 and
+//                       every partial |sum of B| < 2^13 * 2^49 = 2^62 < 2^63: exact, whatever order the adds arrived in.
+//                       NM_MESH_SIMPLIFY_AGGREGATE: ms_insert's ballot loop once per corner -- the lanes of a wave whose
+//                       corner k shares a slot are summed in registers, their leader adds once: the same integers.
+//   5b. ms_emit_vertices<true>   a kept cluster of n >= 2 members with 1 <= contributions <= 2^13 and a positive trace solves
+//                       (A + tr * 2^-6 I) delta = -(A m + b) around the mean m (lattice units) by the adjugate, a fixed sequence
+//                       of individually rounded fp64 operations on the exact sums (msq_place); the regulariser bounds the
+//                       condition number by about 200 and leaves the vertex at the mean along directions no plane constrains.
+//                       det <= 0 or a non-finite delta: SINGULAR, the mean.  x = m + delta is clamped to the cell [0, 2^8]
+//                       (CLAMPED) and p = (float)((double) lo + (double) cell * (x / 2^8)).  The kept clusters' SOLVED /
+//                       CROWDED / SINGULAR / CLAMPED counts leave each wave as one atomic each.
+// The only host round trips are the ones that return counts (nm_mesh_simplify_cluster, nm_mesh_simplify_emit_quadric).
 #include "compact.h"
 #include "nm_internal.h"
 
@@ -61,6 +88,26 @@ struct MsSlot {                                  // 64 bytes: one vertex's atomi
     unsigned count;
 };
 static_assert(sizeof(MsSlot) == 64, "one slot per 64 bytes");
+
+constexpr double MSQ_LATTICE = 256.0;            // 2^8 lattice points per cell edge
+constexpr long long MSQ_REACH = 512;             // 2^9: the largest |u| and the largest edge component (two cells)
+constexpr unsigned long long MSQ_MAX_CONTRIBUTIONS = 8192ull;   // 2^13: a cluster with more is CROWDED
+constexpr double MSQ_LAMBDA = 0.015625;          // 2^-6 of the trace on the diagonal
+
+struct MsQuadric {                               // 128 bytes: one corner's atomics land in one line
+    long long a[6];                              // sum of nrm nrm^T: 00 01 02 11 12 22
+    long long b[3];                              // sum of nrm d
+    unsigned long long contributions;
+    unsigned long long pad[6];
+};
+static_assert(sizeof(MsQuadric) == 128, "one quadric per 128 bytes");
+
+struct MsQuadricHeader {                         // NM_MESH_SIMPLIFY_QUADRIC_* order
+    unsigned long long solved, crowded, singular, clamped, far;
+    unsigned long long pad[3];
+};
+
+enum : unsigned { MSQ_SOLVED = 1u, MSQ_CROWDED = 2u, MSQ_SINGULAR = 4u, MSQ_CLAMPED = 8u };
 
 struct MsHeader {
     unsigned long long clusters, degenerate, duplicate, bad_vertices, bad_faces;
@@ -87,6 +134,12 @@ __device__ __forceinline__ bool ms_cell(const MsGrid& g, const float (&x)[3], fl
 __device__ __forceinline__ long long ms_quantise(float t) {
     double s = (double)t * MS_QUANTUM;
     s = !(s >= -MS_QMAX) ? -MS_QMAX : (s > MS_QMAX ? MS_QMAX : s);
+    return (long long)rint(s);
+}
+
+__device__ __forceinline__ long long msq_lattice(float t) {
+    double s = (double)t * MSQ_LATTICE;
+    s = !(s >= -(double)MSQ_REACH) ? -(double)MSQ_REACH : (s > (double)MSQ_REACH ? (double)MSQ_REACH : s);
     return (long long)rint(s);
 }
 
@@ -285,16 +338,162 @@ __global__ __launch_bounds__(256) void ms_mark(const int32_t* __restrict__ faces
     }
 }
 
-__global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict__ verts, const float* __restrict__ normals, int nv,
-                                                        MsGrid g, const MsSlot* __restrict__ table,
-                                                        const uint32_t* __restrict__ slot_of,
-                                                        const unsigned long long* __restrict__ vwords,
-                                                        const uint32_t* __restrict__ vprefix, int64_t capacity,
-                                                        float* __restrict__ out_verts, float* __restrict__ out_normals) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv || !bit_test(vwords, v)) return;                       // set bits are representatives: good vertices
+// lattice coordinates and integer cell of the good vertex v
+__device__ __forceinline__ void msq_vertex(const float* __restrict__ verts, int v, const MsGrid& g, long long (&cell)[3],
+                                           long long (&u)[3]) {
+    float x[3], c[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) x[k] = verts[3 * (int64_t)v + k];
+    unsigned long long key;
+    ms_cell(g, x, c, key);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float step = c[k] * g.cell;
+        const float lo = g.o[k] + step;
+        cell[k] = (long long)c[k];
+        u[k] = msq_lattice((x[k] - lo) / g.cell);
+    }
+}
+
+// One thread per face, whole waves (the votes), after ms_representatives: rep[] tells the bad vertices, slot_of[] the rows.
+template <bool AGGREGATE>
+__global__ __launch_bounds__(256) void ms_quadric_faces(const float* __restrict__ verts, const int32_t* __restrict__ faces,
+                                                        int64_t nf, int nv, MsGrid g, const uint32_t* __restrict__ slot_of,
+                                                        const int* __restrict__ rep, uint64_t cap, MsQuadric* quad,
+                                                        MsQuadricHeader* qh) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int r[3];
+    const bool live = f < nf && ms_corners(faces, f, nv, rep, r);
+    long long cell[3][3], u[3][3];
+    uint32_t slot[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cell[k][j] = u[k][j] = 0;
+        if (live) {
+            const int v = faces[3 * f + k];
+            msq_vertex(verts, v, g, cell[k], u[k]);
+            slot[k] = slot_of[v];
+        }
+    }
+    unsigned far = 0u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+        long long e1[3], e2[3];
+        bool todo = live && slot[k] < cap;                             // a slot of this table: nothing else is ever addressed
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            e1[j] = (cell[k1][j] - cell[k][j]) * (long long)MSQ_LATTICE + (u[k1][j] - u[k][j]);
+            e2[j] = (cell[k2][j] - cell[k][j]) * (long long)MSQ_LATTICE + (u[k2][j] - u[k][j]);
+            todo = todo && e1[j] >= -MSQ_REACH && e1[j] <= MSQ_REACH && e2[j] >= -MSQ_REACH && e2[j] <= MSQ_REACH;
+        }
+        far += (unsigned)__popcll(__ballot(live && !todo));
+        long long q[9];
+        {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {                              // the bounds above hold for what is multiplied
+                e1[j] = todo ? e1[j] : 0ll;
+                e2[j] = todo ? e2[j] : 0ll;
+            }
+            const long long n0 = e1[1] * e2[2] - e1[2] * e2[1];
+            const long long n1 = e1[2] * e2[0] - e1[0] * e2[2];
+            const long long n2 = e1[0] * e2[1] - e1[1] * e2[0];
+            const long long d = -(n0 * u[k][0] + n1 * u[k][1] + n2 * u[k][2]);
+            q[0] = n0 * n0; q[1] = n0 * n1; q[2] = n0 * n2; q[3] = n1 * n1; q[4] = n1 * n2; q[5] = n2 * n2;
+            q[6] = n0 * d;  q[7] = n1 * d;  q[8] = n2 * d;
+        }
+        if (!AGGREGATE) {
+            if (todo) {
+                MsQuadric* row = quad + slot[k];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) ms_add(row->a + i, q[i]);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) ms_add(row->b + i, q[6 + i]);
+                __hip_atomic_fetch_add(&row->contributions, 1ull, NM_RELAXED_AGENT);
+            }
+            continue;
+        }
+        unsigned long long left = __ballot(todo);
+        while (left) {                                                   // uniform over the wave
+            const int leader = __ffsll((long long)left) - 1;
+            const uint32_t want = __shfl(slot[k], leader, 64);
+            const bool mine = todo && slot[k] == want;
+            const unsigned long long same = __ballot(mine);
+            long long s[9];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) s[i] = mine ? q[i] : 0ll;
+            if (__popcll(same) > 1) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) {
+#pragma unroll
+                    for (int off = 32; off; off >>= 1) s[i] += __shfl_xor(s[i], off, 64);
+                }
+            }
+            if (lane == leader) {
+                MsQuadric* row = quad + want;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) ms_add(row->a + i, s[i]);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) ms_add(row->b + i, s[6 + i]);
+                __hip_atomic_fetch_add(&row->contributions, (unsigned long long)__popcll(same), NM_RELAXED_AGENT);
+            }
+            if (mine) todo = false;
+            left &= ~same;
+        }
+    }
+    if (lane == 0 && far) atomicAdd(&qh->far, (unsigned long long)far);
+}
+
+// The quadric-optimal place of a cluster: frac[] comes in as the members' mean in units of the cell and leaves as x / 2^8 when
+// the cluster is SOLVED; every other status leaves the mean.  Every operation is an fp64 operation rounded on its own.
+__device__ __forceinline__ unsigned msq_place(const MsQuadric& q, double (&frac)[3]) {
+    if (q.contributions > MSQ_MAX_CONTRIBUTIONS) return MSQ_CROWDED;
+    if (q.contributions == 0ull) return 0u;
+    const double a00 = (double)q.a[0], a01 = (double)q.a[1], a02 = (double)q.a[2];
+    const double a11 = (double)q.a[3], a12 = (double)q.a[4], a22 = (double)q.a[5];
+    const double b0 = (double)q.b[0], b1 = (double)q.b[1], b2 = (double)q.b[2];
+    const double tr = (a00 + a11) + a22;
+    if (!(tr > 0.0)) return 0u;
+    const double m0 = frac[0] * MSQ_LATTICE, m1 = frac[1] * MSQ_LATTICE, m2 = frac[2] * MSQ_LATTICE;
+    const double ridge = tr * MSQ_LAMBDA;
+    const double M00 = a00 + ridge, M11 = a11 + ridge, M22 = a22 + ridge, M01 = a01, M02 = a02, M12 = a12;
+    const double r0 = -(((a00 * m0 + a01 * m1) + a02 * m2) + b0);
+    const double r1 = -(((a01 * m0 + a11 * m1) + a12 * m2) + b1);
+    const double r2 = -(((a02 * m0 + a12 * m1) + a22 * m2) + b2);
+    const double c00 = M11 * M22 - M12 * M12;
+    const double c01 = M02 * M12 - M01 * M22;
+    const double c02 = M01 * M12 - M02 * M11;
+    const double c11 = M00 * M22 - M02 * M02;
+    const double c12 = M01 * M02 - M00 * M12;
+    const double c22 = M00 * M11 - M01 * M01;
+    const double det = (M00 * c00 + M01 * c01) + M02 * c02;
+    const double d0 = ((c00 * r0 + c01 * r1) + c02 * r2) / det;
+    const double d1 = ((c01 * r0 + c11 * r1) + c12 * r2) / det;
+    const double d2 = ((c02 * r0 + c12 * r1) + c22 * r2) / det;
+    if (!(det > 0.0) || !(d0 - d0 == 0.0) || !(d1 - d1 == 0.0) || !(d2 - d2 == 0.0)) return MSQ_SINGULAR;
+    double x[3] = {m0 + d0, m1 + d1, m2 + d2};
+    unsigned status = MSQ_SOLVED;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (x[k] < 0.0) { x[k] = 0.0; status |= MSQ_CLAMPED; }
+        if (x[k] > MSQ_LATTICE) { x[k] = MSQ_LATTICE; status |= MSQ_CLAMPED; }
+        frac[k] = x[k] / MSQ_LATTICE;
+    }
+    return status;
+}
+
+// the rows of the kept cluster whose representative is v -> its MSQ_* status (0 under mean placement)
+template <bool QUADRIC>
+__device__ __forceinline__ unsigned ms_emit_cluster(int64_t v, const float* __restrict__ verts, const float* __restrict__ normals,
+                                                    const MsGrid& g, const MsSlot* __restrict__ table,
+                                                    const MsQuadric* __restrict__ quad, const uint32_t* __restrict__ slot_of,
+                                                    const unsigned long long* __restrict__ vwords,
+                                                    const uint32_t* __restrict__ vprefix, int64_t capacity,
+                                                    float* __restrict__ out_verts, float* __restrict__ out_normals) {
     const int64_t dst = bit_rank(vwords, vprefix, v);
-    if (dst >= capacity) return;                                     // never past the caller's arrays
+    if (dst >= capacity) return 0u;                                  // never past the caller's arrays
     const MsSlot slot = table[slot_of[v]];
     float x[3];
 #pragma unroll
@@ -305,25 +504,28 @@ __global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict_
             out_verts[3 * dst + k] = x[k];
             if (normals) out_normals[3 * dst + k] = normals[3 * v + k];
         }
-        return;
+        return 0u;
     }
     float c[3];
     unsigned long long key;
     ms_cell(g, x, c, key);
     const double members = (double)slot.count * MS_QUANTUM;
+    double frac[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) frac[k] = (double)slot.psum[k] / members;
+    const unsigned status = QUADRIC ? msq_place(quad[slot_of[v]], frac) : 0u;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float step = c[k] * g.cell;
         const float lo = g.o[k] + step;
-        const double mean = (double)slot.psum[k] / members;
-        const double offset = (double)g.cell * mean;
+        const double offset = (double)g.cell * frac[k];
         out_verts[3 * dst + k] = (float)((double)lo + offset);
     }
-    if (!normals) return;
+    if (!normals) return status;
     if (slot.nsum[0] == 0 && slot.nsum[1] == 0 && slot.nsum[2] == 0) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) out_normals[3 * dst + k] = normals[3 * v + k];
-        return;
+        return status;
     }
     const float sx = (float)slot.nsum[0], sy = (float)slot.nsum[1], sz = (float)slot.nsum[2];
     const float xx = sx * sx, yy = sy * sy, zz = sz * sz;
@@ -332,6 +534,33 @@ __global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict_
     out_normals[3 * dst + 0] = sx / len;
     out_normals[3 * dst + 1] = sy / len;
     out_normals[3 * dst + 2] = sz / len;
+    return status;
+}
+
+// QUADRIC: quad and qh are the second workspace's; the launch is in whole waves and the statuses are counted per wave
+template <bool QUADRIC>
+__global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict__ verts, const float* __restrict__ normals, int nv,
+                                                        MsGrid g, const MsSlot* __restrict__ table,
+                                                        const MsQuadric* __restrict__ quad,
+                                                        const uint32_t* __restrict__ slot_of,
+                                                        const unsigned long long* __restrict__ vwords,
+                                                        const uint32_t* __restrict__ vprefix, int64_t capacity,
+                                                        float* __restrict__ out_verts, float* __restrict__ out_normals,
+                                                        MsQuadricHeader* qh) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned status = 0u;
+    if (v < nv && bit_test(vwords, v))                                 // set bits are representatives: good vertices
+        status = ms_emit_cluster<QUADRIC>(v, verts, normals, g, table, quad, slot_of, vwords, vprefix, capacity, out_verts,
+                                          out_normals);
+    if (!QUADRIC) return;
+    const unsigned long long solved = __ballot(status & MSQ_SOLVED), crowded = __ballot(status & MSQ_CROWDED);
+    const unsigned long long singular = __ballot(status & MSQ_SINGULAR), clamped = __ballot(status & MSQ_CLAMPED);
+    if ((threadIdx.x & 63) == 0) {
+        if (solved) atomicAdd(&qh->solved, (unsigned long long)__popcll(solved));
+        if (crowded) atomicAdd(&qh->crowded, (unsigned long long)__popcll(crowded));
+        if (singular) atomicAdd(&qh->singular, (unsigned long long)__popcll(singular));
+        if (clamped) atomicAdd(&qh->clamped, (unsigned long long)__popcll(clamped));
+    }
 }
 
 // the smallest power of two >= 2 n (at least 64)
@@ -365,6 +594,23 @@ static MsWorkspace ms_carve(const void* ws, int64_t nv, int64_t nf) {
     w.ftab = c.take<int>((int64_t)w.fcap);
     w.fslot = c.take<uint32_t>(nf);
     w.bits = take_subset_bits(c, nv, nf);
+    w.bytes = c.offset;
+    return w;
+}
+
+struct MsQuadricWorkspace {
+    MsQuadricHeader* hdr;
+    MsQuadric* quad;                             // row s belongs to slot s of the vertex table
+    uint64_t cap;
+    int64_t bytes;
+};
+
+static MsQuadricWorkspace msq_carve(const void* ws, int64_t nv) {
+    Carver c(ws, 256);
+    MsQuadricWorkspace w;
+    w.cap = ms_capacity(nv);
+    w.hdr = c.take<MsQuadricHeader>(1);
+    w.quad = c.take<MsQuadric>((int64_t)w.cap);
     w.bytes = c.offset;
     return w;
 }
@@ -449,11 +695,76 @@ int nm_mesh_simplify_emit(const void* d_workspace, const float* d_verts, int64_t
     const int nv = (int)num_vertices;
     const MsGrid g{{origin_x, origin_y, origin_z}, cell};
     if (vertices_kept) {
-        hipLaunchKernelGGL(ms_emit_vertices, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table,
-                           w.slot_of, w.bits.vwords, w.bits.vprefix, vertices_kept, d_out_verts, d_out_normals);
+        hipLaunchKernelGGL(ms_emit_vertices<false>, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, g,
+                           w.table, (const MsQuadric*)nullptr, w.slot_of, w.bits.vwords, w.bits.vprefix, vertices_kept, d_out_verts,
+                           d_out_normals, (MsQuadricHeader*)nullptr);
         NM_HIP_CHECK(hipGetLastError());
     }
     return subset_compact_faces(d_faces, num_faces, nv, faces_kept, w.bits, w.rep, d_out_faces, nullptr, s);
+}
+
+int64_t nm_mesh_simplify_quadric_workspace_bytes(int64_t num_vertices, int64_t num_faces) {
+    if (!mesh_size_ok(num_vertices) || !mesh_size_ok(num_faces)) return 0;
+    return msq_carve(nullptr, num_vertices).bytes;
+}
+
+int nm_mesh_simplify_quadric_faces(const void* d_workspace, const float* d_verts, int64_t num_vertices, const int32_t* d_faces,
+                                   int64_t num_faces, float origin_x, float origin_y, float origin_z, float cell, int32_t flags,
+                                   void* d_quadric_workspace, void* stream) {
+    if (require_mesh("mesh simplify", num_vertices, num_faces)) return 2;
+    MS_REQUIRE_GRID(origin_x, origin_y, origin_z, cell);
+    NM_REQUIRE((flags & ~NM_MESH_SIMPLIFY_AGGREGATE) == 0, "mesh simplify: unknown flags");
+    NM_REQUIRE(d_workspace && d_quadric_workspace && (num_vertices == 0 || d_verts) && (num_faces == 0 || d_faces), "bad argument");
+    const MsWorkspace w = ms_carve(d_workspace, num_vertices, num_faces);
+    const MsQuadricWorkspace q = msq_carve(d_quadric_workspace, num_vertices);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const MsGrid g{{origin_x, origin_y, origin_z}, cell};
+    NM_HIP_CHECK(hipMemsetAsync(d_quadric_workspace, 0, (size_t)q.bytes, s));
+    if (num_faces) {
+        if (flags & NM_MESH_SIMPLIFY_AGGREGATE)
+            hipLaunchKernelGGL(ms_quadric_faces<true>, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_verts, d_faces, num_faces,
+                               (int)num_vertices, g, w.slot_of, w.rep, q.cap, q.quad, q.hdr);
+        else
+            hipLaunchKernelGGL(ms_quadric_faces<false>, dim3(launch_grid(num_faces)), dim3(256), 0, s, d_verts, d_faces, num_faces,
+                               (int)num_vertices, g, w.slot_of, w.rep, q.cap, q.quad, q.hdr);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+int nm_mesh_simplify_emit_quadric(const void* d_workspace, void* d_quadric_workspace, const float* d_verts, int64_t num_vertices,
+                                  const int32_t* d_faces, int64_t num_faces, const float* d_normals, float origin_x,
+                                  float origin_y, float origin_z, float cell, int64_t vertices_kept, int64_t faces_kept,
+                                  float* d_out_verts, int32_t* d_out_faces, float* d_out_normals, int64_t* h_counts,
+                                  void* stream) {
+    if (require_mesh("mesh simplify", num_vertices, num_faces)) return 2;
+    MS_REQUIRE_GRID(origin_x, origin_y, origin_z, cell);
+    NM_REQUIRE_COMPACT_OUTPUTS("mesh simplify",
+                               d_workspace && d_quadric_workspace && h_counts && (num_vertices == 0 || d_verts) &&
+                                   (num_faces == 0 || d_faces),
+                               d_out_verts && (!d_normals || d_out_normals));
+    const MsWorkspace w = ms_carve(d_workspace, num_vertices, num_faces);
+    const MsQuadricWorkspace q = msq_carve(d_quadric_workspace, num_vertices);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = (int)num_vertices;
+    const MsGrid g{{origin_x, origin_y, origin_z}, cell};
+    NM_HIP_CHECK(hipMemsetAsync(q.hdr, 0, offsetof(MsQuadricHeader, far), s));   // the four counts of this call; far is the face pass's
+    if (vertices_kept) {
+        hipLaunchKernelGGL(ms_emit_vertices<true>, dim3(launch_grid(num_vertices)), dim3(256), 0, s, d_verts, d_normals, nv, g,
+                           w.table, (const MsQuadric*)q.quad, w.slot_of, w.bits.vwords, w.bits.vprefix, vertices_kept, d_out_verts,
+                           d_out_normals, q.hdr);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    if (const int rc = subset_compact_faces(d_faces, num_faces, nv, faces_kept, w.bits, w.rep, d_out_faces, nullptr, s)) return rc;
+    MsQuadricHeader h;
+    NM_HIP_CHECK(hipMemcpyAsync(&h, q.hdr, sizeof(MsQuadricHeader), hipMemcpyDeviceToHost, s));
+    NM_HIP_CHECK(hipStreamSynchronize(s));
+    h_counts[NM_MESH_SIMPLIFY_QUADRIC_SOLVED] = (int64_t)h.solved;
+    h_counts[NM_MESH_SIMPLIFY_QUADRIC_CROWDED] = (int64_t)h.crowded;
+    h_counts[NM_MESH_SIMPLIFY_QUADRIC_SINGULAR] = (int64_t)h.singular;
+    h_counts[NM_MESH_SIMPLIFY_QUADRIC_CLAMPED] = (int64_t)h.clamped;
+    h_counts[NM_MESH_SIMPLIFY_QUADRIC_FAR] = (int64_t)h.far;
+    return 0;
 }
 
 }  // extern "C"

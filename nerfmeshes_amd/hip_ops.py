@@ -795,7 +795,14 @@ SIMPLIFY_AGGREGATE = False               # wave aggregation of equal clusters be
                                          # (tests/tools/time_mesh_simplify.py measures both)
 
 
-def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=None):
+SIMPLIFY_QUADRIC_AGGREGATE = True        # the same for the face pass of placement="quadric": nine 64-bit adds per corner land in
+                                         # rows that wave-mates share, and aggregation takes that pass from 2.4 -- 2.6 ms to
+                                         # 1.0 -- 1.4 (tests/tools/time_mesh_simplify_quadric.py)
+SIMPLIFY_PLACEMENTS = ("mean", "quadric")
+SIMPLIFY_QUADRIC_COUNTS = ("quadric_clusters", "crowded_clusters", "singular_clusters", "clamped_clusters", "far_corners")
+
+
+def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=None, placement="mean"):
     """Vertex clustering on the device (nm_mesh_simplify_cluster + _emit; semantics in include/nerfmeshes_hip.h): the vertices in
     one cell of the grid (origin, cell) become one vertex -- the exact mean of its members, a single member unchanged bit for bit
     --, degenerate and duplicate faces go (opposite windings are not duplicates), and so do the clusters no face is left on.
@@ -803,8 +810,15 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     floats, None = the per-axis minimum of the vertices.  -> (verts, faces, normals, info): kept faces in input order, vertices
     by ascending smallest member index, normals None where None came in; info = dict(vertices, faces, clusters, vertices_kept,
     faces_kept, degenerate_faces, duplicate_faces).  Nothing left gives empty (0,3) arrays.  Raises ValueError for a vertex with
-    a non-finite coordinate or beyond 2^21 cells from the origin and for a face index out of range (the one read-back)."""
+    a non-finite coordinate or beyond 2^21 cells from the origin and for a face index out of range (the one read-back).
+    placement="quadric" (nm_mesh_simplify_quadric_faces + _emit_quadric) puts a cluster of two or more members at the point of
+    its cell nearest to the planes of the faces around it, from exact integer quadrics, instead of at the mean -- the same
+    faces, numbering and normals -- and adds to info the kept clusters placed so (quadric_clusters, the clamped_clusters among
+    them moved back into their cell), those left at the mean (crowded_clusters: more than 2^13 face corners; singular_clusters)
+    and far_corners, the face corners with an edge longer than two cells, which contribute nothing."""
     lib = _lib.load()
+    if placement not in SIMPLIFY_PLACEMENTS:
+        raise ValueError(f"mesh_simplify: placement must be one of {SIMPLIFY_PLACEMENTS}, got {placement!r}")
     if cell is None:
         raise ValueError("mesh_simplify: the cell size is required")
     cell = float(np.float32(cell))
@@ -830,11 +844,22 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     if bad_f:
         raise ValueError(f"mesh simplify: {bad_f} faces have a vertex index outside [0, {nv})")
     out_verts, out_faces, out_normals, _, _ = _mesh_subset_outputs(kv, kf, dev, normals)
-    if kv:
-        check(lib.nm_mesh_simplify_emit(_ptr(ws), _ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin, cell, kv, kf,
-                                        _ptr(out_verts), _ptr(out_faces), _ptr(out_normals), _stream()), "nm_mesh_simplify_emit")
     info = dict(vertices=nv, faces=nf, clusters=clusters, vertices_kept=kv, faces_kept=kf, degenerate_faces=degenerate,
                 duplicate_faces=duplicate)
+    if placement == "quadric":
+        quadrics = _mesh_workspace(int(lib.nm_mesh_simplify_quadric_workspace_bytes(nv, nf)), "mesh simplify", nv, nf, dev)
+        face_flags = 1 if (SIMPLIFY_QUADRIC_AGGREGATE if aggregate is None else aggregate) else 0
+        rc = lib.nm_mesh_simplify_quadric_faces(_ptr(ws), _ptr(verts), nv, _ptr(faces), nf, *origin, cell, face_flags,
+                                                _ptr(quadrics), _stream())
+        _mesh_check(lib, rc, "nm_mesh_simplify_quadric_faces")
+        tally = (C.c_int64 * len(SIMPLIFY_QUADRIC_COUNTS))()
+        rc = lib.nm_mesh_simplify_emit_quadric(_ptr(ws), _ptr(quadrics), _ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin,
+                                               cell, kv, kf, _ptr(out_verts), _ptr(out_faces), _ptr(out_normals), tally, _stream())
+        _mesh_check(lib, rc, "nm_mesh_simplify_emit_quadric")
+        info.update(zip(SIMPLIFY_QUADRIC_COUNTS, (int(x) for x in tally)))
+    elif kv:
+        check(lib.nm_mesh_simplify_emit(_ptr(ws), _ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin, cell, kv, kf,
+                                        _ptr(out_verts), _ptr(out_faces), _ptr(out_normals), _stream()), "nm_mesh_simplify_emit")
     return out_verts, out_faces, out_normals, info
 
 

@@ -503,16 +503,23 @@ def smooth_mesh(vertices, triangles, normals, args):
 def simplify_mesh(vertices, triangles, normals, cell_voxels, args):
     """`--simplify-cell K` on the device (hip_ops.mesh_simplify): vertex clustering on a grid of K-voxel cells, K * (2 * limit /
     res) world units, anchored at (-limit,)*3 -- the vertices of one cell become their exact mean (one alone stays bit for bit),
-    degenerate and duplicate triangles go, kept ones stay in their order.  ValueError when no triangle is left."""
+    degenerate and duplicate triangles go, kept ones stay in their order.  `--simplify-placement quadric` puts the vertex of a
+    cell where the planes of the triangles around it meet instead (exact integer quadrics: the same bytes on every rank), which
+    keeps creases and curved surfaces where they are.  ValueError when no triangle is left."""
     cell = float(cell_voxels) * (2.0 * args.limit / args.res)
     v0, f0 = vertices.shape[0], triangles.shape[0]
+    placement = getattr(args, "simplify_placement", "mean")
     vertices, triangles, normals, info = hip_ops.mesh_simplify(vertices, triangles.to(torch.int32), normals, cell=cell,
-                                                               origin=(-args.limit,) * 3)
+                                                               origin=(-args.limit,) * 3, placement=placement)
     if info["faces_kept"] == 0:
         raise ValueError(f"--simplify-cell {cell_voxels:g} leaves no triangle of {f0}: every one has two corners in one cell "
                          f"({info['clusters']} clusters of {v0} vertices)")
     print(f"Simplify: cell {cell_voxels:g} voxels: {v0} -> {info['vertices_kept']} vertices, {f0} -> {info['faces_kept']} faces "
           f"({info['degenerate_faces']} degenerate, {info['duplicate_faces']} duplicate)")
+    if placement == "quadric":
+        print(f"Simplify placement: quadric: {info['quadric_clusters']} clusters at their quadric's minimum "
+              f"({info['clamped_clusters']} clamped to the cell), at the mean: {info['crowded_clusters']} crowded, "
+              f"{info['singular_clusters']} singular; {info['far_corners']} far corners")
     return vertices, triangles, normals
 
 
@@ -608,9 +615,14 @@ FEATURES = {
                            "--smooth-mu in [-1, 0]"),
         run=lambda v, t, n, o, args: smooth_mesh(v, t, n, args)),
     "simplify": Feature(
-        "--simplify-cell", {"simplify_cell": 0.0}, on=lambda o: float(o["simplify_cell"]),
-        valid=lambda o: 0.0 < float(o["simplify_cell"]) < float("inf"),
-        invalid=lambda o: f"--simplify-cell must be finite and >= 0, got {float(o['simplify_cell'])}",
+        "--simplify-cell", {"simplify_cell": 0.0, "simplify_placement": "mean"},
+        on=lambda o: float(o["simplify_cell"]), any_option=True,      # a placement without a cell is refused, not ignored
+        valid=lambda o: 0.0 < float(o["simplify_cell"]) < float("inf") and o["simplify_placement"] in hip_ops.SIMPLIFY_PLACEMENTS,
+        invalid=lambda o: (f"--simplify-placement must be mean or quadric, got {o['simplify_placement']}"
+                           if o["simplify_placement"] not in hip_ops.SIMPLIFY_PLACEMENTS else
+                           f"--simplify-placement {o['simplify_placement']} needs --simplify-cell K > 0"
+                           if float(o["simplify_cell"]) == 0.0 else
+                           f"--simplify-cell must be finite and >= 0, got {float(o['simplify_cell'])}"),
         run=lambda v, t, n, o, args: simplify_mesh(v, t, n, float(o["simplify_cell"]), args)),
     "target": Feature(
         "--target-mesh", {"target_mesh": None, "chamfer_samples": 100000}, on=lambda o: o["target_mesh"],
@@ -880,6 +892,11 @@ def build_parser():
                    help="(addition) simplify the mesh by vertex clustering: the vertices in one cell of a grid of this many voxels "
                         "per edge become their mean, degenerate and duplicate triangles go; after the component filter, before "
                         "the normals and the appearance query (0 = off)")
+    p.add_argument("--simplify-placement", choices=["mean", "quadric"], default="mean",
+                   help="(addition) where --simplify-cell puts the vertex of a cell with several: mean (default) is their exact "
+                        "mean; quadric is the point of the cell nearest to the planes of the triangles around it (exact integer "
+                        "quadrics, a regularised 3 x 3 solve per cell), which keeps creases and curved surfaces where they are; "
+                        "needs --simplify-cell")
     p.add_argument("--cull-hidden-views", type=_non_negative, default=0,
                    help="(addition) drop the faces no outside camera sees: rasterise the mesh on the GPU from this many cameras "
                         "spread evenly over a sphere around it and keep the faces that win a pixel in at least one view; after "
