@@ -135,6 +135,14 @@ def split_range(n, rank, world_size):
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def own_range(n):
+    """`split_range` for the current rank and world: (lo, hi, counts) -- this rank's part [lo, hi) of range(n) and every
+    rank's item count, which is what `all_gather_rows` takes for the parts."""
+    rank, ws = world()
+    counts = [b - a for a, b in (split_range(n, r, ws) for r in range(ws))]
+    return (*split_range(n, rank, ws), counts)
+
+
 def slab_range(n0, rank, world_size):
     """Axis-0 planes of the density grid owned by `rank` (axis 0 is the outermost marching-cubes scan axis)."""
     return split_range(n0, rank, world_size)
@@ -213,19 +221,15 @@ def all_gather_v(local, counts):
 def render_view_sharded(render_fn, num_rays):
     """Each rank renders rays [lo, hi) with `render_fn(lo, hi) -> (hi-lo, C)` and all ranks receive the
     full (num_rays, C) image."""
-    rank, ws = world()
-    counts = [b - a for a, b in (split_range(num_rays, r, ws) for r in range(ws))]
-    lo, hi = split_range(num_rays, rank, ws)
+    lo, hi, counts = own_range(num_rays)
     return all_gather_rows(render_fn(lo, hi), counts)
 
 
 def density_grid_sharded(query_fn, n0, n1, n2):
     """Each rank evaluates its slab of axis-0 planes with `query_fn(plane_lo, plane_hi) -> ((hi-lo)*n1*n2,)`
     and all ranks receive the full (n0, n1, n2) grid."""
-    rank, ws = world()
-    counts = [(b - a) * n1 * n2 for a, b in (slab_range(n0, r, ws) for r in range(ws))]
-    lo, hi = slab_range(n0, rank, ws)
-    return all_gather_rows(query_fn(lo, hi), counts).view(n0, n1, n2)
+    lo, hi, counts = own_range(n0)
+    return all_gather_rows(query_fn(lo, hi), [c * n1 * n2 for c in counts]).view(n0, n1, n2)
 
 
 def all_gather_ragged(local):
@@ -259,7 +263,10 @@ def marching_cubes_sharded(query_fn, n0, n1, n2, iso_fn, refine=None):
     `hip_ops.np_stats_sharded`).  The result equals the single-GPU mesh bit for bit, vertex numbering included.
     `refine(slab, p_lo, iso, verts, keys)` (optional) may move the slab's own vertices in place before they are packed (the
     super-sampled mesh: mesh_nerf.refine_vertices; keys = hip_ops.marching_cubes_slab's edge keys); None changes nothing.
-    Returns (vertices, faces, normals, values, local slab (planes p_lo .. p_hi))."""
+    Returns (vertices, faces, normals, values, local slab (planes p_lo .. p_hi)).
+    A mesh without a vertex is `hip_ops.marching_cubes`' two errors, with its texts and in its order: the gathered counts
+    tell every rank, ONE more collective carries the minimum and maximum of every slab (on this path only), and all ranks
+    raise together -- ValueError when the level lies outside the grid's range, else RuntimeError."""
     from . import hip_ops
     rank, ws = world()
     lo, hi, below, above, p_lo, p_hi = slab_layers(n0, rank, ws)
@@ -282,6 +289,14 @@ def marching_cubes_sharded(query_fn, n0, n1, n2, iso_fn, refine=None):
     counts = counts.cpu()
     # vertex ids of a slab are local id + (vertices of all lower slabs) - its ghost vertices (nm_mc_emit_slab)
     nv, nf = [int(c) for c in counts[:, 0]], [int(c) for c in counts[:, 1]]
+    if sum(nv) == 0:
+        # every rank sees the same counts, so all of them are here: the ends of every slab (its ghost planes are planes of the
+        # grid; a rank without a slab contributes +inf / -inf) are those of the whole grid
+        ends = torch.tensor([float("inf"), float("-inf")], device=dev) if empty else torch.stack(torch.aminmax(slab))
+        ends = all_gather_into(torch.empty(ws, 2, dtype=torch.float32, device=dev), ends.view(1, 2))
+        if iso < float(ends[:, 0].min()) or iso > float(ends[:, 1].max()):
+            raise ValueError("Surface level must be within volume data range.")
+        raise RuntimeError("No surface found at the given iso value.")
     if empty:
         payload = torch.empty(0, dtype=torch.uint8, device=dev)
     else:

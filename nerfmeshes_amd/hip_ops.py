@@ -1283,12 +1283,9 @@ def _nearest_dist2_sharded(x, y):
     """dist2 of `points_nearest(x, y)`, the queries split over the ranks of torch.distributed: every rank searches its
     dist.split_range slice against the whole of y and one dist.all_gather_rows assembles the (N,) array on every rank."""
     from . import dist as nd
-    rank, world = nd.world()
-    if world == 1:
+    if nd.world()[1] == 1:
         return points_nearest(x, y)[0]
-    n = int(x.shape[0])
-    counts = [b - a for a, b in (nd.split_range(n, r, world) for r in range(world))]
-    lo, hi = nd.split_range(n, rank, world)
+    lo, hi, counts = nd.own_range(int(x.shape[0]))
     return nd.all_gather_rows(points_nearest(x[lo:hi], y)[0].contiguous(), counts)
 
 

@@ -10,6 +10,11 @@ marching cubes runs on the GPU grid directly.  `extract_radiance` still returns 
 array for callers that want it; `extract_geometry` uses the density-only path (the colour branch of the MLP is
 skipped; sigma is bit-identical to the full evaluation).
 
+The geometry stage exists once (`_mesh_field`): a field given as a query of axis-0 planes, meshed on one rank, on the assembled
+grid (`--gather grid`) or per slab (`--gather triangles`) and scaled to world units.  `extract_geometry` hands it the density,
+`extract_geometry_with_super_sampling` the density and a vertex refinement, `extract_geometry_tsdf` the fused depth field and a
+fixed level.
+
 `--route script` (addition) runs the UNMODIFIED script's own call sequence over the same kernels instead -- host-built sample
 points, `batchify` at `--batch-size`, `model.sample_points` + `.cpu()` per batch, numpy's iso level,
 `skimage.measure.marching_cubes`, the per-vertex re-query in `--batch-size` calls -- i.e. INTEGRATION.md's route A without the
@@ -57,17 +62,20 @@ def _axes(args, nums, device):
     return [torch.linspace(-args.limit, args.limit, n).to(device) for n in nums]
 
 
-def _grid_query(model, args, device, nums, density_only, shard=None):
-    """shard = (rank, world): evaluate only this rank's slab of axis-0 planes (see nerfmeshes_amd.dist)."""
+def _grid_query(model, args, device, nums, density_only):
     nums = _nums(nums)
     net = model.get_model().hip("f32")
     ax = _axes(args, nums, device)
-    first, count = 0, nums[0] * nums[1] * nums[2]
-    if shard is not None:
-        from .dist import slab_range
-        lo, hi = slab_range(nums[0], *shard)
-        first, count = lo * nums[1] * nums[2], (hi - lo) * nums[1] * nums[2]
-    return net.grid_query(ax[0], ax[1], ax[2], first=first, count=count, density_only=density_only), nums
+    return net.grid_query(ax[0], ax[1], ax[2], first=0, count=nums[0] * nums[1] * nums[2], density_only=density_only), nums
+
+
+def _density_query(model, args, device, nums):
+    """query(p_lo, p_hi) -> the raw sigma of the axis-0 planes [p_lo, p_hi) of the grid, flat fp32 on the device: what
+    `_mesh_field` and the sharding helpers of nerfmeshes_amd.dist take"""
+    net = model.get_model().hip("f32")
+    ax = _axes(args, nums, device)
+    plane = nums[1] * nums[2]
+    return lambda p_lo, p_hi: net.grid_query(ax[0], ax[1], ax[2], first=p_lo * plane, count=(p_hi - p_lo) * plane, density_only=True)
 
 
 def extract_radiance(model, args, device, nums):
@@ -90,17 +98,11 @@ def extract_density(model, args, device, nums):
     all-gather (RCCL over xGMI) assembles the full grid on every rank; marching cubes then runs on the full
     grid, so the mesh is identical to the single-GPU one by construction."""
     from . import dist as nd
-    rank, world = nd.world()
-    if world == 1:
-        out, nums = _grid_query(model, args, device, nums, density_only=True)
-        return out.view(*nums)
     nums = _nums(nums)
-    net = model.get_model().hip("f32")
-    ax = _axes(args, nums, device)
-    plane = nums[1] * nums[2]
-    return nd.density_grid_sharded(
-        lambda lo, hi: net.grid_query(ax[0], ax[1], ax[2], first=lo * plane, count=(hi - lo) * plane, density_only=True),
-        *nums)
+    query = _density_query(model, args, device, nums)
+    if nd.world()[1] == 1:
+        return query(0, nums[0]).view(*nums)
+    return nd.density_grid_sharded(query, *nums)
 
 
 def extract_iso_level(density, args):
@@ -136,16 +138,43 @@ def extract_iso_level_sharded(slab, first_plane, own_lo, own_hi, nums, args):
     iso_value = min(max(args.iso_level, st["min"] + st["std"]), st["max"] - st["std"])
     print(f"Min density {st['min']}, Max density: {st['max']}, Mean density {st['mean']}")
     print(f"Querying based on iso level: {iso_value}")
-    return iso_value, st
+    return iso_value
+
+
+def _mesh_field(query, nums, args, level=None, refine=None):
+    """The geometry stage of every route: the mesh of the scalar field whose axis-0 planes [p_lo, p_hi) `query(p_lo, p_hi)`
+    returns (flat fp32 on the device) -> (vertices (V,3) f32 in world units, triangles (F,3) i32, normals (V,3) f32, the field).
+    `level`: the level to mesh at; None is the numpy-exact adaptive iso level of the whole field (extract_iso_level).
+    `refine(volume, z_global, iso, vertices, keys)` (optional) moves the vertices in place while they are in grid-index units,
+    as dist.marching_cubes_sharded calls it.  One rank evaluates and meshes the whole field and issues no collective.  Under
+    torch.distributed `--gather grid` assembles the field on every rank (dist.density_grid_sharded) and meshes it redundantly;
+    `--gather triangles`, the default, meshes every rank's own slab of cube layers and only the triangles travel
+    (dist.marching_cubes_sharded; the 4th value is then the rank's own slab, None on a rank without one).  All three give the
+    same mesh bit for bit; an empty one is skimage's two errors on every rank."""
+    from . import dist as nd
+    world = nd.world()[1]
+    if world > 1 and getattr(args, "gather", "triangles") == "triangles":
+        if level is None:
+            iso_fn = lambda slab, p_lo, own_lo, own_hi: extract_iso_level_sharded(slab, p_lo, own_lo, own_hi, nums, args)  # noqa: E731
+        else:
+            iso_fn = lambda *slab: level  # noqa: E731
+        vertices, triangles, normals, _, field = nd.marching_cubes_sharded(query, *nums, iso_fn, refine=refine)
+    else:
+        field = nd.density_grid_sharded(query, *nums) if world > 1 else query(0, nums[0]).view(*nums)
+        iso = extract_iso_level(field, args) if level is None else level
+        if refine is None:
+            vertices, triangles, normals, _ = hip_ops.marching_cubes(field, iso)
+        else:
+            vertices, triangles, normals, _, keys = hip_ops.marching_cubes(field, iso, return_keys=True)
+            refine(field, 0, iso, vertices, keys)
+    vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)   # res/2, not (res-1)/2: as the reference
+    return vertices, triangles, normals, field
 
 
 def extract_geometry(model, device, args):
-    """mesh_nerf.py:68-92 -> (vertices (V,3) f32, triangles (F,3) i32, normals (V,3) f32, density grid).
-    Under torch.distributed the default is `--gather triangles`: every rank meshes its own slab of cube layers and only
-    the triangles travel (dist.marching_cubes_sharded; the 4th value is then the rank's own slab of the grid);
-    `--gather grid` assembles the density grid on every rank first (extract_density) and meshes it redundantly."""
-    from . import dist as nd
-    rank, world = nd.world()
+    """mesh_nerf.py:68-92 -> (vertices (V,3) f32, triangles (F,3) i32, normals (V,3) f32, density grid): `_mesh_field` of the
+    density, whose three ways of running on one or several ranks are described there (under `--gather triangles` the 4th
+    value is the rank's own slab of the grid)."""
     if getattr(args, "route", "kernel") == "script":
         # mesh_nerf.py:68-92 as written: the full radiance grid on the host, numpy's statistics, scikit-image's entry point
         # (the real package, or compat's nm_mc_* stand-in where it is not installed)
@@ -160,33 +189,8 @@ def extract_geometry(model, device, args):
         vertices, triangles, normals, _ = [torch.from_numpy(np.ascontiguousarray(r)) for r in marching_cubes(density, iso_value)]
         vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)
         return vertices, triangles, normals, density
-    if world > 1 and getattr(args, "gather", "triangles") == "triangles":
-        nums = _nums(args.res)
-        net = model.get_model().hip("f32")
-        ax = _axes(args, nums, device)
-        plane = nums[1] * nums[2]
-        stats = {}
-
-        def iso_fn(slab, p_lo, own_lo, own_hi):
-            iso, st = extract_iso_level_sharded(slab, p_lo, own_lo, own_hi, nums, args)
-            stats.update(st)
-            return iso
-
-        vertices, triangles, normals, _, slab = nd.marching_cubes_sharded(
-            lambda p_lo, p_hi: net.grid_query(ax[0], ax[1], ax[2], first=p_lo * plane, count=(p_hi - p_lo) * plane, density_only=True),
-            *nums, iso_fn)
-        if vertices.shape[0] == 0:              # skimage's two errors, in its order (see hip_ops.marching_cubes)
-            iso = min(max(args.iso_level, stats["min"] + stats["std"]), stats["max"] - stats["std"])
-            if iso < stats["min"] or iso > stats["max"]:
-                raise ValueError("Surface level must be within volume data range.")
-            raise RuntimeError("No surface found at the given iso value.")
-        vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)
-        return vertices, triangles, normals, slab
-    density = extract_density(model, args, device, args.res)
-    iso_value = extract_iso_level(density, args)
-    vertices, triangles, normals, _ = hip_ops.marching_cubes(density, iso_value)
-    vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)   # res/2, not (res-1)/2: as the reference
-    return vertices, triangles, normals, density
+    nums = _nums(args.res)
+    return _mesh_field(_density_query(model, args, device, nums), nums, args)
 
 
 def _assemble_grid_from_slabs(slab, nums, device):
@@ -228,41 +232,14 @@ def extract_geometry_with_super_sampling(model, device, args):
     the reference's three dense grids ("Super-sampled meshing").  Under torch.distributed, `--gather grid` refines
     after the redundant marching cubes, `--gather triangles` refines every slab's own vertices before they travel; both give
     the single-rank mesh bit for bit."""
-    from . import dist as nd
     ss = int(args.super_sampling)
     if getattr(args, "route", "kernel") == "script":
         raise ValueError("--super-sampling has no --route script: the reference's script never runs it (mesh_nerf.py:95-96)")
     nums = _nums(args.res)
     hip_ops.check_super_sampling(nums, ss)
     net = model.get_model().hip("f32")
-    rank, world = nd.world()
-    if world > 1 and getattr(args, "gather", "triangles") == "triangles":
-        ax = _axes(args, nums, device)
-        plane = nums[1] * nums[2]
-        stats = {}
-
-        def iso_fn(slab, p_lo, own_lo, own_hi):
-            iso, st = extract_iso_level_sharded(slab, p_lo, own_lo, own_hi, nums, args)
-            stats.update(st)
-            return iso
-
-        vertices, triangles, normals, _, slab = nd.marching_cubes_sharded(
-            lambda p_lo, p_hi: net.grid_query(ax[0], ax[1], ax[2], first=p_lo * plane, count=(p_hi - p_lo) * plane, density_only=True),
-            *nums, iso_fn,
-            refine=lambda slab, p_lo, iso, v, keys: refine_vertices(net, args, nums, ss, slab, p_lo, iso, v, keys))
-        if vertices.shape[0] == 0:              # the plain path's errors (extract_geometry)
-            iso = min(max(args.iso_level, stats["min"] + stats["std"]), stats["max"] - stats["std"])
-            if iso < stats["min"] or iso > stats["max"]:
-                raise ValueError("Surface level must be within volume data range.")
-            raise RuntimeError("No surface found at the given iso value.")
-        vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)
-        return vertices, triangles, normals, slab
-    density = extract_density(model, args, device, args.res)
-    iso_value = extract_iso_level(density, args)
-    vertices, triangles, normals, _, keys = hip_ops.marching_cubes(density, iso_value, return_keys=True)
-    refine_vertices(net, args, nums, ss, density, 0, iso_value, vertices, keys)
-    vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)   # res/2, not (res-1)/2: as the reference
-    return vertices, triangles, normals, density
+    return _mesh_field(_density_query(model, args, device, nums), nums, args,
+                       refine=lambda volume, z_global, iso, v, keys: refine_vertices(net, args, nums, ss, volume, z_global, iso, v, keys))
 
 
 def tsdf_focal(args):
@@ -294,22 +271,21 @@ def tsdf_render_views(model, args, cfg, device):
     `query_view(..., keep_depth=True)` measures the depth along the UNIT ray of each pixel (get_ray_bundle normalises its
     directions); the fusion compares it with a voxel's depth along the camera's axis, so every depth is divided by its pixel's
     |(x, y, -1)| (tsdf_ray_lengths) in fp64 and rounded to fp32 once.  Under torch.distributed the VIEWS are split over the
-    ranks (dist.split_range) and ONE all-gather assembles both stacks on every rank."""
+    ranks (dist.own_range) and ONE all-gather assembles both stacks on every rank."""
     from . import dist as nd
     from . import mesh_render
-    rank, world = nd.world()
     count, size, focal = int(args.tsdf_views), int(args.tsdf_size), tsdf_focal(args)
     poses = mesh_render.sphere_poses(count, (0.0, 0.0, 0.0), float(args.tsdf_radius))
     bounds = torch.tensor([cfg.dataset.near, cfg.dataset.far], dtype=torch.float32)
-    lo, hi = nd.split_range(count, rank, world)
+    lo, hi, counts = nd.own_range(count)
     own = torch.empty(hi - lo, 2, size, size, dtype=torch.float32, device=device)
     lengths = torch.from_numpy(tsdf_ray_lengths(size, focal)).to(device)
     for k in range(lo, hi):
         out = model.query_view(torch.from_numpy(poses[k]), size, size, focal, bounds, keep_depth=True)
         own[k - lo, 0] = (out.depth_map.view(size, size).double() / lengths).float()
         own[k - lo, 1] = out.acc_map.view(size, size)
-    if world > 1:
-        own = nd.all_gather_rows(own, [b - a for a, b in (nd.split_range(count, r, world) for r in range(world))])
+    if len(counts) > 1:                     # more than one rank
+        own = nd.all_gather_rows(own, counts)
     views = [hip_ops.make_view(pose, size, size, focal) for pose in poses]
     return views, own[:, 0].contiguous(), own[:, 1].contiguous()
 
@@ -347,7 +323,7 @@ def extract_geometry_tsdf(model, device, args, cfg):
     clock("render", start)
     tally = torch.zeros(3, dtype=torch.int64, device=device)
 
-    def integrate(p_lo, p_hi, counted=True):
+    def integrate(p_lo, p_hi, counted):
         nonlocal tally
         out = hip_ops.tsdf_integrate(views, depth, opacity, ax, trunc, cfg.dataset.near, min_opacity=float(args.tsdf_min_opacity),
                                      first=p_lo * plane, count=(p_hi - p_lo) * plane)
@@ -355,40 +331,28 @@ def extract_geometry_tsdf(model, device, args, cfg):
             tally = tally + out["counts"]
         return out["field"]
 
-    start = time.perf_counter()
+    # the counters count every plane of the grid on exactly one rank: under `--gather triangles` a rank's ghost planes are fused
+    # in calls of their own (voxels are independent, so the field is the same bytes) and not counted; elsewhere no plane is
+    # fused twice
+    own = None
     if world > 1 and getattr(args, "gather", "triangles") == "triangles":
-        # a rank's ghost planes are fused in calls of their own: voxels are independent, so the field is the same bytes, and the
-        # counters then count every plane of the grid on exactly one rank
-        lo, hi, _, _, _, _ = nd.slab_layers(nums[0], rank, world)
-        top = hi + (1 if hi == nums[0] - 1 else 0)
+        lo, hi = nd.slab_layers(nums[0], rank, world)[:2]
+        own = lo, hi + (1 if hi == nums[0] - 1 else 0)
 
-        def query(p_lo, p_hi):
-            start = time.perf_counter()
-            parts = [integrate(a, b, counted) for a, b, counted in ((p_lo, lo, False), (lo, top, True), (top, p_hi, False)) if b > a]
-            clock("integrate", start)
-            return torch.cat(parts)
-
-        vertices, triangles, normals, _, field = nd.marching_cubes_sharded(query, *nums, lambda *slab: level)
-        seconds["marching_cubes"] = time.perf_counter() - start - seconds.get("integrate", 0.0)
-    else:
-        if world > 1:
-            field = nd.density_grid_sharded(integrate, *nums)
-        else:
-            field = integrate(0, nums[0]).view(*nums)
-        clock("integrate", start)
+    def query(p_lo, p_hi):
         start = time.perf_counter()
-        vertices, triangles, normals, _ = hip_ops.marching_cubes(field, level)
-        clock("marching_cubes", start)
+        lo, top = own or (p_lo, p_hi)
+        parts = [integrate(a, b, counted) for a, b, counted in ((p_lo, lo, False), (lo, top, True), (top, p_hi, False)) if b > a]
+        clock("integrate", start)
+        return torch.cat(parts) if len(parts) > 1 else parts[0]
+
+    start = time.perf_counter()
+    vertices, triangles, normals, field = _mesh_field(query, nums, args, level=level)
+    clock("marching_cubes", start)
+    seconds["marching_cubes"] -= seconds.get("integrate", 0.0)       # the stage without the fusion inside it (a rank may fuse nothing)
     if world > 1:
         nd.all_reduce(tally)
     counts = dict(zip(hip_ops.TSDF_COUNTS, (int(x) for x in tally.tolist())))
-    if vertices.shape[0] == 0:              # the sharded path: skimage's two errors, in its order (see hip_ops.marching_cubes)
-        import torch.distributed as td
-        ends = torch.tensor([1.0, -1.0] if field is None else [float(field.min()), float(field.max())], device=device)
-        lo, hi = float(nd.all_reduce(ends[:1], td.ReduceOp.MIN)), float(nd.all_reduce(ends[1:], td.ReduceOp.MAX))
-        if level < lo or level > hi:
-            raise ValueError("Surface level must be within volume data range.")
-        raise RuntimeError("No surface found at the given iso value.")
     print(f"TSDF: {len(views)} views of {int(args.tsdf_size)}² fused into {nums[0]} x {nums[1]} x {nums[2]} voxels: "
           f"{counts['observed']} observed, {counts['interior']} interior (occluded in every view), {counts['outside']} outside every "
           f"view; {vertices.shape[0]} vertices, {triangles.shape[0]} faces")
@@ -403,7 +367,6 @@ def extract_geometry_tsdf(model, device, args, cfg):
             json.dump(report, fh, indent=1)
             fh.write("\n")
         print(f"TSDF report saved to {path}")
-    vertices = args.limit * (vertices / (args.res / 2.0) - 1.0)   # res/2, not (res-1)/2: as the density path
     return vertices, triangles, normals, field
 
 
@@ -713,8 +676,7 @@ def export_marching_cubes(model, args, cfg, device):
     # Appearance: one query per vertex.  Vertices are independent, so under torch.distributed every rank queries a
     # contiguous range of them and one ragged all-gather assembles the (V,3) colours; rank 0 writes the file.
     rank, world = nd.world()
-    counts = [b - a for a, b in (nd.split_range(vertices.shape[0], r, world) for r in range(world))]
-    lo, hi = nd.split_range(vertices.shape[0], rank, world)
+    lo, hi, counts = nd.own_range(vertices.shape[0])
     if "normals" in on:
         # the fp32 handle whatever --precision is (as the geometry); every rank its own vertex range, one ragged all-gather
         # (the fallback flag travels as a 4th column)
@@ -782,15 +744,13 @@ def bake_texture(model, vertices, triangles, normals, args, device, chunk):
     the device.  Under torch.distributed every rank takes a contiguous face range and one all-gather assembles the colours;
     every rank then fills the atlas redundantly.  -> (face_uv (F,3,2) f32, atlas (H,W,3) uint8), both on the device."""
     from . import dist as nd
-    rank, world = nd.world()
     n = int(args.texture_res)
     faces = triangles.to(device=device, dtype=torch.int32).contiguous()
     num_faces = int(faces.shape[0])
     layout = hip_ops.mesh_texture_layout(num_faces, n)                # ValueError: no face, or an atlas wider than 16384
     per_face = layout["samples_per_face"]
     vertices, normals = vertices.to(device), normals.to(device=device, dtype=torch.float32)
-    ranges = [nd.split_range(num_faces, r, world) for r in range(world)]
-    lo, hi = ranges[rank]
+    lo, hi, counts = nd.own_range(num_faces)
     step = max(1, TEXTURE_WINDOW_SAMPLES // per_face)
     colours = torch.empty((hi - lo) * per_face, 3, dtype=torch.float32, device=device)
     fallback = bad = 0
@@ -800,8 +760,8 @@ def bake_texture(model, vertices, triangles, normals, args, device, chunk):
         fallback, bad = fallback + fb, bad + bd
         parts = query_appearance(model, args, positions, directions, device, chunk, announce=False)
         colours[(first - lo) * per_face:(first - lo + count) * per_face] = torch.cat(parts, dim=0)
-    colours = nd.all_gather_rows(colours, [(b - a) * per_face for a, b in ranges])
-    tally = nd.all_gather_rows(torch.tensor([[fallback, bad]], dtype=torch.int64, device=device), [1] * world).sum(0).tolist()
+    colours = nd.all_gather_rows(colours, [c * per_face for c in counts])
+    tally = nd.all_gather_rows(torch.tensor([[fallback, bad]], dtype=torch.int64, device=device), [1] * len(counts)).sum(0).tolist()
     atlas = hip_ops.mesh_texture_fill(colours, num_faces, n)
     face_uv = hip_ops.mesh_texture_uv(num_faces, n, device=device)
     print(f"Texture atlas: {layout['width']} x {layout['height']} texels ({layout['cols']} x {layout['rows']} cells of {n + 3} x "

@@ -1,13 +1,15 @@
 """GPU parity: nm_mc_count / nm_mc_emit vs the C oracle (itself pinned bit-for-bit to scikit-image) and the
 committed scikit-image golden set.  Everything is compared BITWISE: vertices, faces (vertex numbering and
 triangle order), normals, values, and the two error conditions."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import mc_oracle
 from tests.helpers import load_golden
-from tests.gpu_support import ops  # noqa: F401
+from tests.gpu_support import assert_ranks_ok, launch_ranks, ops  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -141,6 +143,18 @@ def test_mc_errors(ops):
         ops.marching_cubes(vol, 1.0)               # in range but no strictly-greater / not-greater mix
     with pytest.raises(ValueError):
         ops.marching_cubes(torch.ones(1, 4, 4, device="cuda"), 1.0)
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_mc_sharded_empty_mesh_raises_on_every_rank(world):
+    """dist.marching_cubes_sharded of a 3 x 4 x 4 grid (value = axis-0 index) on `world` ranks sharing one GPU: a level
+    outside the range is the whole-grid call's ValueError on every rank, the maximum its RuntimeError, and 0.5 afterwards its
+    mesh bit for bit (tests/tools/mc_errors_dist_worker.py).  At 3 ranks one rank has no slab.  A rank left waiting in a
+    collective shows as the launch's time limit."""
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a MI355X")
+    r = launch_ranks(os.path.join("tests", "tools", "mc_errors_dist_worker.py"), world, timeout=120)
+    assert_ranks_ok(r, f"MC_ERRORS_DIST_OK world={world}")
 
 
 def test_mc_properties_large(ops):
