@@ -783,6 +783,35 @@ int nm_points_nearest(const float* d_x, int64_t num_x, const float* d_y, int64_t
                       void* d_workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Point to mesh: the exact distance of points to the TRIANGLES of a mesh (mesh_chamfer --surface exact, mesh_nerf
+ * --target-surface exact; DESIGN.md, "Mesh quality: exact surface distance").  d_x (N,3) fp32, d_verts (V,3) fp32, d_faces
+ * (F,3) int32, all on the device.  fp32 with every operation rounded on its own (no fused multiply-add), division correctly
+ * rounded, dot(u, v) = (ux vx + uy vy) + uz vz, u x v = (uy vz - uz vy, uz vx - ux vz, ux vy - uy vx), so a numpy fp32
+ * restatement (tests/mesh_surface_distance.py) reproduces every output bit for bit.  Per query p and face (a, b, c):
+ *   ab = b - a, ac = c - a, bc = c - b, ca = a - c;  ap = p - a, bp = p - b, cp = p - c.
+ *   seg(q, e): r = 1 / dot(e, e); t = dot(q, e) * r; t = fmin(fmax(t, 0), 1) with fmax / fmin returning their non-NaN operand
+ *     (a zero-length edge has r = inf, t = NaN or inf -> 0 or 1 times a zero vector: the distance to the point);
+ *     d = q - t * e per component; the term is dot(d, d).
+ *   s1 = seg(ap, ab), s2 = seg(bp, bc), s3 = seg(cp, ca).
+ *   n = ab x ac, nn = dot(n, n); inside = dot(n, ab x ap) >= 0 && dot(n, bc x bp) >= 0 && dot(n, ca x cp) >= 0 && nn > 0;
+ *   h = dot(n, ap); pl = (h * h) * (1 / nn) where `inside` holds and the value is finite, else +inf.
+ *   d2 = min(min(s1, s2), min(s3, pl)), and NaN when any of s1, s2, s3 is NaN.
+ * The value of one face never depends on another face, and every degenerate face is defined: a zero-area face is its
+ * segments, a point face the point.  d_dist2[i] = the smallest d2 over the faces; d_face[i] (int32) = the smallest face index
+ * that attains it; d_face_normals (N,3), may be NULL = c / |c| of that face exactly as nm_mesh_sample_points writes it (NaN
+ * for |c| = 0).  A pair whose d2 is NaN never wins (a NaN vertex takes out its own faces only); a face with an index outside
+ * [0, V) is never dereferenced and never wins; a row that no face wins (a NaN query, F = 0) gets (+inf, -1, NaN normal).
+ * Brute force over all N * F pairs, no spatial culling: a bound computed in fp32 could exceed the computed distance of a
+ * near-coplanar face.  The workspace is nm_points_to_mesh_workspace_bytes(N, F) bytes (one 112-byte record per face and 8
+ * bytes per query; 0 for sizes out of range; 256-byte aligned).  The result does not depend on the order the workgroups ran
+ * in.  V, F and N are in [0, 2^31 - 64).  Argument errors return 2 before any HIP call.  No allocation, no host
+ * synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+int64_t nm_points_to_mesh_workspace_bytes(int64_t num_x, int64_t num_faces);
+int nm_points_to_mesh(const float* d_x, int64_t num_x, const float* d_verts, int64_t num_vertices, const int32_t* d_faces,
+                      int64_t num_faces, float* d_dist2, int32_t* d_face, float* d_face_normals, void* d_workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mesh simplification by vertex clustering (mesh_nerf --simplify-cell; DESIGN.md, "Mesh simplification").  All arrays on
  * the device: d_verts (V,3) fp32, d_faces (F,3) int32, d_normals (V,3) fp32 or NULL.  The grid is (origin, cell): cell is
  * finite and > 0, the origin finite.  Every fp32 / fp64 operation below is rounded on its own (no fused multiply-add), sqrt

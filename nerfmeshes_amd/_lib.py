@@ -204,6 +204,9 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p]),
     "nm_points_nearest_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "nm_points_nearest": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nm_points_to_mesh_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "nm_points_to_mesh": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
     "nm_mesh_simplify_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "nm_mesh_simplify_cluster": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float, C.c_float, C.c_float,
                                            C.c_float, C.c_int32, c_void_p, C.POINTER(C.c_int64), c_void_p]),

@@ -1306,6 +1306,99 @@ def chamfer_distance(x, y):
     return dict(chamfer=x_to_y + y_to_x, x_to_y=x_to_y, y_to_x=y_to_x, dist2_x=dist2_x, dist2_y=dist2_y)
 
 
+def points_to_mesh(x, verts, faces, return_normals=False):
+    """Exact distance of every row of x (N,3) to the TRIANGLES of a mesh (nm_points_to_mesh: brute force over all N * F pairs;
+    the arithmetic is in include/nerfmeshes_hip.h, "Point to mesh") -> (dist2 (N,) f32: the smallest squared distance to a
+    face, face (N,) i32: the smallest face index that attains it[, normals (N,3): that face's unit normal, NaN for a face
+    without area]).  NaN pairs never win; a row without a winner (a NaN query, F = 0) gets (+inf, -1, NaN).  Raises ValueError
+    for a face index out of range (the one read-back of this call)."""
+    lib = _lib.load()
+    x = _points(x, None, "x")
+    dev = x.device
+    verts, faces, nv, nf = _mesh_arrays(verts.to(dev) if isinstance(verts, torch.Tensor) else verts, faces, "points_to_mesh")
+    n = int(x.shape[0])
+    _mesh_face_weights(lib, verts, faces, nv, nf, "points_to_mesh")
+    nbytes = int(lib.nm_points_to_mesh_workspace_bytes(n, nf))
+    if nbytes == 0:
+        raise ValueError(f"points_to_mesh: {n} points x {nf} faces are beyond the supported sizes")
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    normals = torch.empty(n, 3, dtype=torch.float32, device=dev) if return_normals else None
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # 112 bytes per face: not kept beyond the call
+    _mesh_check(lib, lib.nm_points_to_mesh(_ptr(x), n, _ptr(verts), nv, _ptr(faces), nf, _ptr(dist2), _ptr(face), _ptr(normals),
+                                           _ptr(ws), _stream()), "nm_points_to_mesh")
+    return (dist2, face, normals) if return_normals else (dist2, face)
+
+
+def _points_to_mesh_sharded(x, verts, faces):
+    """`points_to_mesh(x, verts, faces, return_normals=True)`, the queries split over the ranks of torch.distributed as
+    `_nearest_dist2_sharded` splits them: one dist.all_gather_rows per array assembles it on every rank."""
+    from . import dist as nd
+    if nd.world()[1] == 1:
+        return points_to_mesh(x, verts, faces, return_normals=True)
+    lo, hi, counts = nd.own_range(int(x.shape[0]))
+    return tuple(nd.all_gather_rows(t.contiguous(), counts) for t in points_to_mesh(x[lo:hi], verts, faces, return_normals=True))
+
+
+def surface_metrics(dist2_x, dist2_y, normals_x, face_normals_x, normals_y, face_normals_y, thresholds=()):
+    """The numbers of `mesh_surface_distance` from its gathered arrays (x: mesh -> target, y: target -> mesh): fp64 sums,
+    integer counts, Python numbers.  The normal agreement of a row is |dot| of the sample's normal and the winning face's,
+    the dot in fp32 as (x x' + y y') + z z', over the rows where both are finite."""
+    out = {}
+    roots = {}
+    for side, d2 in (("x_to_y", dist2_x), ("y_to_x", dist2_y)):
+        d2 = d2.double()
+        roots[side] = d2.sqrt()
+        out[side] = float(d2.sum().item()) / d2.shape[0]
+    out["chamfer"] = out["x_to_y"] + out["y_to_x"]
+    out["accuracy"] = float(roots["x_to_y"].sum().item()) / roots["x_to_y"].shape[0]
+    out["completeness"] = float(roots["y_to_x"].sum().item()) / roots["y_to_x"].shape[0]
+    for side in ("x_to_y", "y_to_x"):
+        out["hausdorff_" + side] = float(roots[side].max().item())
+    out["hausdorff"] = max(out["hausdorff_x_to_y"], out["hausdorff_y_to_x"])
+    for side, a, b in (("x_to_y", normals_x, face_normals_x), ("y_to_x", normals_y, face_normals_y)):
+        dot = (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+        ok = torch.isfinite(a).all(1) & torch.isfinite(b).all(1)
+        pairs = int(ok.sum().item())
+        total = float(torch.where(ok, dot.double().abs(), torch.zeros((), dtype=torch.float64, device=dot.device)).sum().item())
+        out["normal_pairs_" + side] = pairs
+        out["normal_consistency_" + side] = total / pairs if pairs else float("nan")
+    out["normal_consistency"] = 0.5 * (out["normal_consistency_x_to_y"] + out["normal_consistency_y_to_x"])
+    out["fscore"] = []
+    for tau in thresholds:
+        tau = float(tau)
+        p, r = (int((d2.double() <= tau * tau).sum().item()) / d2.shape[0] for d2 in (dist2_x, dist2_y))
+        out["fscore"].append(dict(threshold=tau, precision=p, recall=r, fscore=2 * p * r / (p + r) if p + r > 0 else 0.0))
+    return out
+
+
+def mesh_surface_distance(verts_a, faces_a, verts_b, faces_b, n, generator=None, thresholds=()):
+    """Surface distance of two triangle meshes without a noise floor of its own: `n` points with their face normals are
+    sampled on each mesh (mesh_sample_points from `generator`, mesh A first: the draws `mesh_chamfer.compare_meshes` makes) and
+    every cloud is measured against the other mesh's TRIANGLES (points_to_mesh).  -> dict: x_to_y, y_to_x, chamfer (means of
+    squared distances), accuracy, completeness (means of distances, A -> B and B -> A), hausdorff_x_to_y, hausdorff_y_to_x,
+    hausdorff (maxima), normal_consistency_x_to_y, normal_consistency_y_to_x, normal_consistency and normal_pairs_* (mean
+    |cos| between the sample's and the winning face's normal over the rows where both are finite; NaN without any), fscore: a
+    list of dict(threshold, precision, recall, fscore) per threshold (dist2 <= tau^2 in fp64; 0 when P + R = 0), and the
+    device arrays dist2_x, dist2_y, face_x, face_y.  Under torch.distributed every rank measures a slice of the queries and
+    then reduces the same gathered arrays: any number of ranks gives the single-rank result bit for bit."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"mesh_surface_distance: the number of samples must be >= 1, got {n}")
+    thresholds = tuple(float(t) for t in thresholds)
+    if any(not (0.0 < t < float("inf")) for t in thresholds):
+        raise ValueError(f"mesh_surface_distance: thresholds must be finite and > 0, got {thresholds}")
+    verts_a, faces_a, _, _ = _mesh_arrays(verts_a, faces_a, "mesh_surface_distance")
+    verts_b, faces_b, _, _ = _mesh_arrays(verts_b, faces_b, "mesh_surface_distance")
+    points_a, _, normals_a = mesh_sample_points(verts_a, faces_a, n=n, generator=generator, return_normals=True)
+    points_b, _, normals_b = mesh_sample_points(verts_b, faces_b, n=n, generator=generator, return_normals=True)
+    dist2_x, face_x, fn_x = _points_to_mesh_sharded(points_a, verts_b, faces_b)
+    dist2_y, face_y, fn_y = _points_to_mesh_sharded(points_b, verts_a, faces_a)
+    out = surface_metrics(dist2_x, dist2_y, normals_a, fn_x, normals_b, fn_y, thresholds)
+    out.update(dist2_x=dist2_x, dist2_y=dist2_y, face_x=face_x, face_y=face_y)
+    return out
+
+
 SURFACE_STEP_MAX = 8
 
 

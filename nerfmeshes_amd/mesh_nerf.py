@@ -488,14 +488,15 @@ def simplify_mesh(vertices, triangles, normals, cell_voxels, args):
 
 def chamfer_to_target(vertices, triangles, args, device):
     """`--target-mesh PATH`: the chamfer distance between the extracted mesh and an OBJ file, both in world coordinates
-    (mesh_chamfer.compare_meshes with --chamfer-samples / --chamfer-seed), printed; rank 0 writes
+    (mesh_chamfer.compare_meshes with --chamfer-samples / --chamfer-seed / --target-surface / --target-fscore), printed; rank 0 writes
     <save-dir>/<mesh-name stem>.chamfer.json.  Under torch.distributed the searches are shared out over the ranks."""
     from . import dist as nd
     from . import mesh_chamfer
     from .nerf.nerf_helpers import load_obj
     target_vertices, target_faces = load_obj(args.target_mesh)
     report = mesh_chamfer.compare_meshes(vertices, triangles, target_vertices, target_faces, samples=args.chamfer_samples,
-                                         seed=args.chamfer_seed, device=device)
+                                         seed=args.chamfer_seed, device=device, surface=getattr(args, "target_surface", "sampled"),
+                                         fscore=getattr(args, "target_fscore", None))
     report["target"]["path"] = args.target_mesh
     for line in mesh_chamfer.format_report(report):
         print(line)
@@ -527,6 +528,15 @@ class Feature(typing.NamedTuple):
 
 def _finite(x, lo=float("-inf"), hi=float("inf")):
     return lo < float(x) < hi                       # a NaN fails both comparisons
+
+
+def _target_surface_valid(o):
+    from . import mesh_chamfer
+    try:
+        mesh_chamfer.check_surface(o["target_surface"], o["target_fscore"])
+    except ValueError:
+        return False
+    return bool(o["target_mesh"])
 
 
 TSDF_OPTIONS = {"geometry": "density", "tsdf_views": 32, "tsdf_size": 800, "tsdf_radius": 4.0, "tsdf_focal": 0.0, "tsdf_trunc": 3.0,
@@ -591,6 +601,15 @@ FEATURES = {
         "--target-mesh", {"target_mesh": None, "chamfer_samples": 100000}, on=lambda o: o["target_mesh"],
         valid=lambda o: int(o["chamfer_samples"]) >= 1,
         invalid=lambda o: f"--chamfer-samples must be >= 1, got {o['chamfer_samples']}"),
+    "target_surface": Feature(
+        "--target-surface / --target-fscore", {"target_surface": "sampled", "target_fscore": None, "target_mesh": None},
+        # options of "target", which runs the measure: checked, never switched on; --target-mesh is among the options because
+        # the two are valid only with it ("target", which comes first, speaks for --target-mesh itself)
+        on=lambda o: False, any_option=True,
+        valid=_target_surface_valid,
+        invalid=lambda o: ("--target-surface / --target-fscore need --target-mesh PATH" if not o["target_mesh"] else
+                           "--target-surface must be sampled or exact, and --target-fscore T1,T2,... (thresholds finite and > 0) "
+                           "needs --target-surface exact")),
     "render": Feature(
         "--render-views", {"render_views": 0, "render_size": 800}, on=lambda o: int(o["render_views"]),
         valid=lambda o: int(o["render_views"]) >= 0 and 1 <= int(o["render_size"]) <= 16384,
@@ -887,6 +906,13 @@ def build_parser():
                         "on the GPU, world coordinates) and write <save-dir>/<mesh-name stem>.chamfer.json")
     p.add_argument("--chamfer-samples", type=int, default=100000, help="(addition) points sampled on each mesh for --target-mesh")
     p.add_argument("--chamfer-seed", type=int, default=0, help="(addition) seed of the device generator the samples are drawn from")
+    p.add_argument("--target-surface", type=str, default="sampled",
+                   help="(addition) sampled (default): --target-mesh compares two samplings; exact: every sample against the other "
+                        "mesh's triangles (mesh_chamfer --surface exact), which adds accuracy / completeness, Hausdorff and normal "
+                        "consistency to the report")
+    p.add_argument("--target-fscore", type=str, default=None, metavar="T1,T2,...",
+                   help="(addition) distance thresholds in world units for precision / recall / F-score against --target-mesh; "
+                        "needs --target-surface exact")
     p.add_argument("--render-views", type=_non_negative, default=0,
                    help="(addition) after the OBJ is written, draw the mesh from this many orbit poses on the GPU and report it "
                         "against the network's own render of each pose: PSNR, depth difference, silhouette IoU; writes "
