@@ -65,6 +65,9 @@ extern "C" {
  * bit for bit a closed rule (mesh_nerf --geometry tsdf).  Additions only. */
 /* 6, later: + nm_mesh_simplify_quadric_faces (+ nm_mesh_simplify_quadric_workspace_bytes), nm_mesh_simplify_emit_quadric:
  * quadric-optimal cluster vertices from exact integer quadrics (mesh_nerf --simplify-placement quadric).  Additions only. */
+/* 6, later: + nm_mesh_simplify_adaptive_level (+ nm_mesh_simplify_adaptive_workspace_bytes), nm_mesh_simplify_adaptive_faces,
+ * nm_mesh_simplify_adaptive_emit: error-bounded adaptive vertex clustering on nested grids (mesh_nerf --simplify-levels).
+ * Additions only. */
 #define NM_ABI_VERSION 6
 
 const char* nm_last_error(void);
@@ -914,6 +917,77 @@ int nm_mesh_simplify_emit_quadric(const void* d_workspace, void* d_quadric_works
                                   float origin_y, float origin_z, float cell, int64_t vertices_kept, int64_t faces_kept,
                                   float* d_out_verts, int32_t* d_out_faces, float* d_out_normals, int64_t* h_counts,
                                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * ADAPTIVE LEVELS of the quadric placement (mesh_nerf --simplify-levels L / --simplify-error E; DESIGN.md, "Adaptive
+ * clustering"): Schaefer and Warren's adaptive vertex clustering on the nested grids (origin, cell * 2^l), l = 0 .. L
+ * (1 <= L <= NM_MESH_SIMPLIFY_MAX_LEVELS = 8).  cell * 2^l is exact in fp32 (it must stay finite), so a vertex's cell at
+ * level l is c_0 >> l per axis: the cells of level l + 1 are unions of eight cells of level l.  Every vertex joins the
+ * cluster of the COARSEST level whose cell is acceptable; everything else is the quadric placement above, bit for bit.
+ *   level     a cluster of level l is the set of vertices of one cell of that grid.  Its members, representative, position
+ *             and normal sums, its quadric (on the lattice of 2^8 points per edge of THAT level's cell, FAR meaning two of that
+ *             level's cells), its status and its place x are what the sections above define for a grid of that cell size,
+ *             computed from the faces directly -- never from its children's sums --, so every overflow bound above holds per level.
+ *   error     of a cluster of n >= 2 members that is SOLVED: over every corner that contributed to it with nrm != 0, with
+ *             x = (x / 2^8) * 2^8 in fp64 as the position step leaves it (clamped), u0 the corner's lattice point, all in fp64,
+ *             every operation rounded on its own:
+ *               d2 = ((n0 (x0 - u0_0) + n1 (x1 - u0_1)) + n2 (x2 - u0_2))^2 / ((n0 n0 + n1 n1) + n2 n2)
+ *             the squared distance, in lattice units, of x from the corner's plane.  The cluster's error is the MAXIMUM d2
+ *             (0 without such a corner): a maximum of non-negative doubles is the maximum of their bits and does not depend
+ *             on the order it is taken in.
+ *   accept    at level l >= 1 a cluster of one member is acceptable; one of more members iff it is SOLVED (clamped or not: so
+ *             neither CROWDED nor SINGULAR, with a contribution and a positive trace), none of its corners is FAR (such a
+ *             corner's plane was never tested) and its error <= tol_l^2, where, in fp64 in this order,
+ *               tol_l = (max_error / (double) (cell * 2^l)) * 2^8,  tol_l^2 = tol_l * tol_l     (max_error >= 0, +inf allowed).
+ *             Every cluster of level 0 is acceptable: the output is never finer than the uniform clustering with `cell`
+ *             and never coarser than the one with cell * 2^L.
+ *   choice    a vertex joins the cluster of the largest l whose cell is acceptable.  Acceptance is a property of the cell,
+ *             and all members of a cell share every coarser cell, so they choose alike: the chosen cells partition the
+ *             vertices.  A refused cluster none of whose coarser cells was chosen is counted once, by the first reason of:
+ *             crowded, no contribution (or zero trace), singular, far, error.
+ *   output    faces, duplicates and numbering as above through the final representatives.  A chosen cluster of one member
+ *             emits its rows bit for bit; another p = (float)((double) lo_l + (double) (cell * 2^l) * (x / 2^8)) (the mean
+ *             where level 0 is not SOLVED) and the normal of the level's integer normal sum by the rule above.
+ * nm_mesh_simplify_adaptive_level: ONE level: call it for level = levels, levels - 1, .., 0 in this order with THE SAME mesh,
+ *   grid, error and three workspaces -- nm_mesh_simplify_workspace_bytes, nm_mesh_simplify_quadric_workspace_bytes, both
+ *   reused by every level, and nm_mesh_simplify_adaptive_workspace_bytes (a header and 30 bytes per vertex of staged rows; 0
+ *   for sizes out of range): memory does not grow with the number of levels.  `cell` is level 0's.  flags:
+ *   NM_MESH_SIMPLIFY_AGGREGATE for the vertex pass, NM_MESH_SIMPLIFY_AGGREGATE_FACES for the two face passes (the same
+ *   results; another speed).  No host synchronisation.
+ * nm_mesh_simplify_adaptive_faces: after level 0: filters the faces and scans; returns on the HOST (it synchronises the stream)
+ *   h_counts[NM_MESH_SIMPLIFY_ADAPTIVE_COUNTS]: the NM_MESH_SIMPLIFY_* counts (clusters: the chosen ones of all levels), then
+ *   for l = 0 .. levels at NM_MESH_SIMPLIFY_COUNTS + l * NM_MESH_SIMPLIFY_LEVEL_FIELDS the NM_MESH_SIMPLIFY_LEVEL_* fields:
+ *   vertices that chose level l, clusters chosen there, clusters refused there per reason, and the bits of the largest error
+ *   d2 of a cluster of n >= 2 chosen there (l >= 1; lattice units of that level, squared).
+ * nm_mesh_simplify_adaptive_emit: writes the outputs as nm_mesh_simplify_emit does (with_normals: d_normals was given to the
+ *   levels); returns on the HOST h_counts[NM_MESH_SIMPLIFY_ADAPTIVE_EMIT_COUNTS]: the NM_MESH_SIMPLIFY_QUADRIC_* counts of the
+ *   kept clusters at their chosen level (FAR: level 0's corners), then the kept clusters of level 0 .. levels.
+ * Argument errors return 2 before any HIP call.  A mesh with BAD vertices or faces gives the counts and unspecified rows.
+ * ------------------------------------------------------------------------------------------ */
+#define NM_MESH_SIMPLIFY_AGGREGATE_FACES 2
+#define NM_MESH_SIMPLIFY_MAX_LEVELS 8
+#define NM_MESH_SIMPLIFY_LEVEL_VERTICES 0
+#define NM_MESH_SIMPLIFY_LEVEL_CLUSTERS 1
+#define NM_MESH_SIMPLIFY_LEVEL_REFUSED_ERROR 2
+#define NM_MESH_SIMPLIFY_LEVEL_REFUSED_CROWDED 3
+#define NM_MESH_SIMPLIFY_LEVEL_REFUSED_SINGULAR 4
+#define NM_MESH_SIMPLIFY_LEVEL_REFUSED_FAR 5
+#define NM_MESH_SIMPLIFY_LEVEL_REFUSED_EMPTY 6
+#define NM_MESH_SIMPLIFY_LEVEL_MAX_D2 7
+#define NM_MESH_SIMPLIFY_LEVEL_FIELDS 8
+#define NM_MESH_SIMPLIFY_ADAPTIVE_COUNTS (NM_MESH_SIMPLIFY_COUNTS + (NM_MESH_SIMPLIFY_MAX_LEVELS + 1) * NM_MESH_SIMPLIFY_LEVEL_FIELDS)
+#define NM_MESH_SIMPLIFY_ADAPTIVE_EMIT_COUNTS (NM_MESH_SIMPLIFY_QUADRIC_COUNTS + NM_MESH_SIMPLIFY_MAX_LEVELS + 1)
+int64_t nm_mesh_simplify_adaptive_workspace_bytes(int64_t num_vertices, int64_t num_faces);
+int nm_mesh_simplify_adaptive_level(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
+                                    const float* d_normals, float origin_x, float origin_y, float origin_z, float cell,
+                                    int32_t level, int32_t levels, double max_error, int32_t flags, void* d_workspace,
+                                    void* d_quadric_workspace, void* d_adaptive_workspace, void* stream);
+int nm_mesh_simplify_adaptive_faces(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t levels,
+                                    void* d_workspace, void* d_adaptive_workspace, int64_t* h_counts, void* stream);
+int nm_mesh_simplify_adaptive_emit(const void* d_workspace, void* d_adaptive_workspace, const int32_t* d_faces, int64_t num_faces,
+                                   int64_t num_vertices, int32_t levels, int32_t with_normals, int64_t vertices_kept,
+                                   int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces, float* d_out_normals,
+                                   int64_t* h_counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Taubin smoothing of a mesh (mesh_nerf --smooth-iters; DESIGN.md, "Mesh smoothing").  All arrays on the device: d_verts

@@ -218,6 +218,15 @@ SIGNATURES = {
     "nm_mesh_simplify_emit_quadric": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float,
                                                 C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int64, c_void_p, c_void_p,
                                                 c_void_p, C.POINTER(C.c_int64), c_void_p]),
+    "nm_mesh_simplify_adaptive_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "nm_mesh_simplify_adaptive_level": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_float, C.c_float,
+                                                  C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_double, C.c_int32, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
+    "nm_mesh_simplify_adaptive_faces": (C.c_int, [c_void_p, C.c_int64, C.c_int64, C.c_int32, c_void_p, c_void_p,
+                                                  C.POINTER(C.c_int64), c_void_p]),
+    "nm_mesh_simplify_adaptive_emit": (C.c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                 C.c_int64, C.c_int64, c_void_p, c_void_p, c_void_p, C.POINTER(C.c_int64),
+                                                 c_void_p]),
     "nm_mesh_smooth_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "nm_mesh_smooth_build": (C.c_int, [c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.POINTER(C.c_int64), c_void_p]),
     "nm_mesh_smooth_run": (C.c_int, [c_void_p, c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_int32, c_void_p, c_void_p]),

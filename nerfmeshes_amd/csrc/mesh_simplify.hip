@@ -98,9 +98,12 @@ struct MsQuadric {                               // 128 bytes: one corner's atom
     long long a[6];                              // sum of nrm nrm^T: 00 01 02 11 12 22
     long long b[3];                              // sum of nrm d
     unsigned long long contributions;
-    unsigned long long pad[6];
+    double frac[3];                              // the adaptive levels' (msa_place): the placed point in units of the cell,
+    unsigned long long err;                      //   the largest d2 of a corner as the bits of a non-negative double (msa_error),
+    unsigned status, far;                        //   msq_place's status, and whether a corner of the row was FAR
+    unsigned long long pad;
 };
-static_assert(sizeof(MsQuadric) == 128, "one quadric per 128 bytes");
+static_assert(sizeof(MsQuadric) == 128 && offsetof(MsQuadric, frac) == 80, "one quadric per 128 bytes");
 
 struct MsQuadricHeader {                         // NM_MESH_SIMPLIFY_QUADRIC_* order
     unsigned long long solved, crowded, singular, clamped, far;
@@ -484,6 +487,23 @@ __device__ __forceinline__ unsigned msq_place(const MsQuadric& q, double (&frac)
     return status;
 }
 
+// the normal row of a cluster of two or more members whose representative is v
+__device__ __forceinline__ void ms_cluster_normal(const MsSlot& slot, const float* __restrict__ normals, int64_t v,
+                                                  float* __restrict__ out) {
+    if (slot.nsum[0] == 0 && slot.nsum[1] == 0 && slot.nsum[2] == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = normals[3 * v + k];
+        return;
+    }
+    const float sx = (float)slot.nsum[0], sy = (float)slot.nsum[1], sz = (float)slot.nsum[2];
+    const float xx = sx * sx, yy = sy * sy, zz = sz * sz;
+    const float xy = xx + yy;
+    const float len = sqrtf(xy + zz);
+    out[0] = sx / len;
+    out[1] = sy / len;
+    out[2] = sz / len;
+}
+
 // the rows of the kept cluster whose representative is v -> its MSQ_* status (0 under mean placement)
 template <bool QUADRIC>
 __device__ __forceinline__ unsigned ms_emit_cluster(int64_t v, const float* __restrict__ verts, const float* __restrict__ normals,
@@ -521,19 +541,7 @@ __device__ __forceinline__ unsigned ms_emit_cluster(int64_t v, const float* __re
         const double offset = (double)g.cell * frac[k];
         out_verts[3 * dst + k] = (float)((double)lo + offset);
     }
-    if (!normals) return status;
-    if (slot.nsum[0] == 0 && slot.nsum[1] == 0 && slot.nsum[2] == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out_normals[3 * dst + k] = normals[3 * v + k];
-        return status;
-    }
-    const float sx = (float)slot.nsum[0], sy = (float)slot.nsum[1], sz = (float)slot.nsum[2];
-    const float xx = sx * sx, yy = sy * sy, zz = sz * sz;
-    const float xy = xx + yy;
-    const float len = sqrtf(xy + zz);
-    out_normals[3 * dst + 0] = sx / len;
-    out_normals[3 * dst + 1] = sy / len;
-    out_normals[3 * dst + 2] = sz / len;
+    if (normals) ms_cluster_normal(slot, normals, v, out_normals + 3 * dst);
     return status;
 }
 
@@ -560,6 +568,255 @@ __global__ __launch_bounds__(256) void ms_emit_vertices(const float* __restrict_
         if (crowded) atomicAdd(&qh->crowded, (unsigned long long)__popcll(crowded));
         if (singular) atomicAdd(&qh->singular, (unsigned long long)__popcll(singular));
         if (clamped) atomicAdd(&qh->clamped, (unsigned long long)__popcll(clamped));
+    }
+}
+
+// ADAPTIVE LEVELS (mesh_nerf --simplify-levels L; nm_mesh_simplify_adaptive_level / _faces / _emit; DESIGN.md, "Adaptive
+// clustering"): steps 1, 2 and 3b run once per level l = L .. 0 on the grid (origin, cell * 2^l) -- the multiplication is exact
+// in fp32, so c_l = c_0 >> l per axis and the grids nest --, each level from the faces directly, in the same two workspaces;
+// the overflow bounds above hold per level as they stand.  Then, per level:
+//   msa_place    one lane per slot of the vertex table: an occupied slot of two or more members runs msq_place on its row and
+//                parks frac[] (x / 2^8 when SOLVED, the mean else) and the status in the row's spare bytes.
+//   msa_error    (l >= 1) one thread per face, whole waves: every corner that contributed to a SOLVED row -- the same u, e1, e2,
+//                nrm and FAR rule as ms_quadric_faces -- with nrm != 0 gives, with x = frac * 2^8 (exact),
+//                  d2 = ((n0 (x0 - u0) + n1 (x1 - u1)) + n2 (x2 - u2))^2 / ((n0 n0 + n1 n1) + n2 n2)
+//                in fp64, every operation rounded on its own; the row keeps the largest by an agent-scope atomicMax on the
+//                bits (d2 >= 0: the order of the bits is the order of the values, and a maximum does not depend on the order
+//                it was taken in).  A FAR corner marks its row (atomicOr).  NM_MESH_SIMPLIFY_AGGREGATE_FACES: the lanes of a
+//                wave whose corner k shares a row take their maximum in registers, their leader issues one atomic.
+//   msa_assign   one lane per vertex that no coarser level took: its cell is ACCEPTED when it has one member, or when its row is
+//                SOLVED (so neither CROWDED nor SINGULAR, and with a contribution), has no FAR corner and d2 <= tol^2 (level
+//                0: always).  The vertex then takes the cell's representative and the level; the representative stages the
+//                cluster's position, normal and status rows at its own index, by step 5 / 5b's rules with this level's grid.
+//                Acceptance is a property of the cell and the members of a cell share every coarser cell, so they were all
+//                still free and all decide alike: the chosen cells partition the vertices.  Refusals are counted once per
+//                cluster, by the first reason of: crowded, no contribution (or zero trace), singular, far, error.
+//   msa_emit     the staged rows of the kept clusters through the ordered compaction; statuses and levels are counted per wave.
+// The faces go through the final rep[] by steps 3 -- 5 unchanged.  Host round trips: the two that return counts.
+constexpr int MSA_MAX_LEVELS = 8;
+constexpr int MSA_LEVEL_FIELDS = 8;              // NM_MESH_SIMPLIFY_LEVEL_* order
+
+struct MsaHeader {
+    unsigned long long level[MSA_MAX_LEVELS + 1][MSA_LEVEL_FIELDS];
+    unsigned long long kept[MSA_MAX_LEVELS + 1];
+    unsigned long long status[4];                // kept clusters: solved, crowded, singular, clamped
+    unsigned long long far;                      // level 0's FAR corners
+    unsigned long long pad[2];
+};
+enum : int { MSA_VERTICES = 0, MSA_CLUSTERS, MSA_REFUSED_ERROR, MSA_REFUSED_CROWDED, MSA_REFUSED_SINGULAR, MSA_REFUSED_FAR,
+             MSA_REFUSED_EMPTY, MSA_MAX_D2 };
+
+__global__ __launch_bounds__(256) void msa_place(const MsSlot* __restrict__ table, uint64_t cap, MsQuadric* __restrict__ quad) {
+    const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= cap) return;
+    const MsSlot slot = table[s];
+    if (slot.key == EMPTY_KEY || slot.count <= 1u) return;
+    const double members = (double)slot.count * MS_QUANTUM;
+    double frac[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) frac[k] = (double)slot.psum[k] / members;
+    const MsQuadric q = quad[s];
+    const unsigned status = msq_place(q, frac);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) quad[s].frac[k] = frac[k];
+    quad[s].status = status;
+}
+
+// One thread per face, whole waves (the votes), after msa_place.  frac and status of a row are the previous launch's: plain
+// loads; err and far are this launch's: agent-scope atomics only.
+template <bool AGGREGATE>
+__global__ __launch_bounds__(256) void msa_error(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t nf,
+                                                 int nv, MsGrid g, const uint32_t* __restrict__ slot_of,
+                                                 const int* __restrict__ rep, uint64_t cap, MsQuadric* quad) {
+    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int r[3];
+    const bool live = f < nf && ms_corners(faces, f, nv, rep, r);
+    long long cell[3][3], u[3][3];
+    uint32_t slot[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cell[k][j] = u[k][j] = 0;
+        if (live) {
+            const int v = faces[3 * f + k];
+            msq_vertex(verts, v, g, cell[k], u[k]);
+            slot[k] = slot_of[v];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+        long long e1[3], e2[3];
+        const bool mine_row = live && slot[k] < cap;                   // a slot of this table: nothing else is ever addressed
+        bool todo = mine_row;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            e1[j] = (cell[k1][j] - cell[k][j]) * (long long)MSQ_LATTICE + (u[k1][j] - u[k][j]);
+            e2[j] = (cell[k2][j] - cell[k][j]) * (long long)MSQ_LATTICE + (u[k2][j] - u[k][j]);
+            todo = todo && e1[j] >= -MSQ_REACH && e1[j] <= MSQ_REACH && e2[j] >= -MSQ_REACH && e2[j] <= MSQ_REACH;
+        }
+        if (mine_row && !todo) __hip_atomic_fetch_or(&quad[slot[k]].far, 1u, NM_RELAXED_AGENT);
+        unsigned long long bits = 0ull;
+        if (todo && (quad[slot[k]].status & MSQ_SOLVED)) {
+            const long long n0 = e1[1] * e2[2] - e1[2] * e2[1];
+            const long long n1 = e1[2] * e2[0] - e1[0] * e2[2];
+            const long long n2 = e1[0] * e2[1] - e1[1] * e2[0];
+            if (n0 | n1 | n2) {
+                const MsQuadric* row = quad + slot[k];
+                const double x0 = row->frac[0] * MSQ_LATTICE, x1 = row->frac[1] * MSQ_LATTICE, x2 = row->frac[2] * MSQ_LATTICE;
+                const double d0 = (double)n0, d1 = (double)n1, d2 = (double)n2;
+                const double p0 = d0 * (x0 - (double)u[k][0]), p1 = d1 * (x1 - (double)u[k][1]), p2 = d2 * (x2 - (double)u[k][2]);
+                const double s = (p0 + p1) + p2;
+                const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2;
+                const double den = (q0 + q1) + q2;
+                const double ss = s * s;
+                bits = (unsigned long long)__double_as_longlong(ss / den);
+            }
+        }
+        if (!AGGREGATE) {
+            if (bits) __hip_atomic_fetch_max(&quad[slot[k]].err, bits, NM_RELAXED_AGENT);
+            continue;
+        }
+        bool open = bits != 0ull;
+        unsigned long long left = __ballot(open);
+        while (left) {                                                   // uniform over the wave
+            const int leader = __ffsll((long long)left) - 1;
+            const uint32_t want = __shfl(slot[k], leader, 64);
+            const bool mine = open && slot[k] == want;
+            const unsigned long long same = __ballot(mine);
+            unsigned long long m = mine ? bits : 0ull;
+            if (__popcll(same) > 1) {
+#pragma unroll
+                for (int off = 32; off; off >>= 1) {
+                    const unsigned long long other = __shfl_xor(m, off, 64);
+                    m = other > m ? other : m;
+                }
+            }
+            if (lane == leader) __hip_atomic_fetch_max(&quad[want].err, m, NM_RELAXED_AGENT);
+            if (mine) open = false;
+            left &= ~same;
+        }
+    }
+}
+
+struct MsaStage {                                // per vertex; rows are written at representatives only
+    int* rep;                                    // the final representative (-1: a bad vertex)
+    signed char* level;                          // the level that took the vertex (-1: none yet)
+    unsigned char* status;                       // the staged cluster's MSQ_* status
+    float* pos;
+    float* nrm;
+};
+
+// One thread per vertex, whole waves (the counts).  table, slot_of, rep and quad are this level's, all of earlier launches.
+__global__ __launch_bounds__(256) void msa_assign(const float* __restrict__ verts, const float* __restrict__ normals, int nv,
+                                                  MsGrid g, int level, double tol2, const MsSlot* __restrict__ table,
+                                                  const MsQuadric* __restrict__ quad, const uint32_t* __restrict__ slot_of,
+                                                  const int* __restrict__ rep, MsaStage st, MsaHeader* hdr) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool accepted = false, head = false, refused = false;
+    unsigned status = 0u, far = 0u;
+    unsigned long long err = 0ull;
+    unsigned count = 0u;
+    if (v < nv) {
+        const int r = rep[v];
+        if (r < 0) {
+            if (level == 0) st.rep[v] = -1;                          // a bad vertex of the finest grid is in no cluster
+        } else if (st.level[v] < 0) {
+            const uint32_t s = slot_of[v];
+            const MsSlot slot = table[s];
+            count = slot.count;
+            if (count >= 2u) {
+                status = quad[s].status;
+                far = quad[s].far;
+                err = quad[s].err;
+            }
+            accepted = level == 0 || count <= 1u ||
+                       ((status & MSQ_SOLVED) && !far && __longlong_as_double((long long)err) <= tol2);
+            head = r == (int)v;
+            refused = head && !accepted;
+            if (accepted) {
+                st.rep[v] = r;
+                st.level[v] = (signed char)level;
+            }
+            if (head && accepted) {
+                float x[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) x[k] = verts[3 * v + k];
+                st.status[v] = (unsigned char)(count >= 2u ? status : 0u);
+                if (count <= 1u) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        st.pos[3 * v + k] = x[k];
+                        if (normals) st.nrm[3 * v + k] = normals[3 * v + k];
+                    }
+                } else {
+                    float c[3];
+                    unsigned long long key;
+                    ms_cell(g, x, c, key);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const float step = c[k] * g.cell;
+                        const float lo = g.o[k] + step;
+                        const double offset = (double)g.cell * quad[s].frac[k];
+                        st.pos[3 * v + k] = (float)((double)lo + offset);
+                    }
+                    if (normals) ms_cluster_normal(slot, normals, v, st.nrm + 3 * v);
+                    if (level > 0 && err) atomicMax(&hdr->level[level][MSA_MAX_D2], err);
+                }
+            }
+        }
+    }
+    const bool crowded = refused && (status & MSQ_CROWDED), empty = refused && status == 0u;
+    const bool singular = refused && (status & MSQ_SINGULAR);
+    const bool solved = refused && (status & MSQ_SOLVED);
+    const unsigned long long took = __ballot(accepted), heads = __ballot(head && accepted);
+    const unsigned long long b_crowded = __ballot(crowded), b_empty = __ballot(empty), b_singular = __ballot(singular);
+    const unsigned long long b_far = __ballot(solved && far), b_error = __ballot(solved && !far);
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* row = hdr->level[level];
+        if (took) atomicAdd(row + MSA_VERTICES, (unsigned long long)__popcll(took));
+        if (heads) atomicAdd(row + MSA_CLUSTERS, (unsigned long long)__popcll(heads));
+        if (b_error) atomicAdd(row + MSA_REFUSED_ERROR, (unsigned long long)__popcll(b_error));
+        if (b_crowded) atomicAdd(row + MSA_REFUSED_CROWDED, (unsigned long long)__popcll(b_crowded));
+        if (b_singular) atomicAdd(row + MSA_REFUSED_SINGULAR, (unsigned long long)__popcll(b_singular));
+        if (b_far) atomicAdd(row + MSA_REFUSED_FAR, (unsigned long long)__popcll(b_far));
+        if (b_empty) atomicAdd(row + MSA_REFUSED_EMPTY, (unsigned long long)__popcll(b_empty));
+    }
+}
+
+// One thread per vertex, whole waves: the staged rows of the kept clusters, in the order of their representatives.
+__global__ __launch_bounds__(256) void msa_emit(int nv, int levels, MsaStage st, bool normals,
+                                                const unsigned long long* __restrict__ vwords,
+                                                const uint32_t* __restrict__ vprefix, int64_t capacity,
+                                                float* __restrict__ out_verts, float* __restrict__ out_normals, MsaHeader* hdr) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned status = 0u;
+    int level = -1;
+    if (v < nv && bit_test(vwords, v)) {                               // set bits are representatives: good vertices
+        const int64_t dst = bit_rank(vwords, vprefix, v);
+        if (dst < capacity) {                                          // never past the caller's arrays
+            status = st.status[v];
+            level = st.level[v];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                out_verts[3 * dst + k] = st.pos[3 * v + k];
+                if (normals) out_normals[3 * dst + k] = st.nrm[3 * v + k];
+            }
+        }
+    }
+    const unsigned long long solved = __ballot(status & MSQ_SOLVED), crowded = __ballot(status & MSQ_CROWDED);
+    const unsigned long long singular = __ballot(status & MSQ_SINGULAR), clamped = __ballot(status & MSQ_CLAMPED);
+    const bool first = (threadIdx.x & 63) == 0;
+    if (first) {
+        if (solved) atomicAdd(&hdr->status[0], (unsigned long long)__popcll(solved));
+        if (crowded) atomicAdd(&hdr->status[1], (unsigned long long)__popcll(crowded));
+        if (singular) atomicAdd(&hdr->status[2], (unsigned long long)__popcll(singular));
+        if (clamped) atomicAdd(&hdr->status[3], (unsigned long long)__popcll(clamped));
+    }
+    for (int l = 0; l <= levels; ++l) {                                // uniform over the wave
+        const unsigned long long at = __ballot(level == l);
+        if (first && at) atomicAdd(&hdr->kept[l], (unsigned long long)__popcll(at));
     }
 }
 
@@ -611,6 +868,25 @@ static MsQuadricWorkspace msq_carve(const void* ws, int64_t nv) {
     w.cap = ms_capacity(nv);
     w.hdr = c.take<MsQuadricHeader>(1);
     w.quad = c.take<MsQuadric>((int64_t)w.cap);
+    w.bytes = c.offset;
+    return w;
+}
+
+struct MsaWorkspace {
+    MsaHeader* hdr;
+    MsaStage stage;
+    int64_t bytes;
+};
+
+static MsaWorkspace msa_carve(const void* ws, int64_t nv) {
+    Carver c(ws, 256);
+    MsaWorkspace w;
+    w.hdr = c.take<MsaHeader>(1);
+    w.stage.rep = c.take<int>(nv);
+    w.stage.level = c.take<signed char>(nv);
+    w.stage.status = c.take<unsigned char>(nv);
+    w.stage.pos = c.take<float>(3 * nv);
+    w.stage.nrm = c.take<float>(3 * nv);
     w.bytes = c.offset;
     return w;
 }
@@ -764,6 +1040,162 @@ int nm_mesh_simplify_emit_quadric(const void* d_workspace, void* d_quadric_works
     h_counts[NM_MESH_SIMPLIFY_QUADRIC_SINGULAR] = (int64_t)h.singular;
     h_counts[NM_MESH_SIMPLIFY_QUADRIC_CLAMPED] = (int64_t)h.clamped;
     h_counts[NM_MESH_SIMPLIFY_QUADRIC_FAR] = (int64_t)h.far;
+    return 0;
+}
+
+int64_t nm_mesh_simplify_adaptive_workspace_bytes(int64_t num_vertices, int64_t num_faces) {
+    if (!mesh_size_ok(num_vertices) || !mesh_size_ok(num_faces)) return 0;
+    return msa_carve(nullptr, num_vertices).bytes;
+}
+
+#define MSA_REQUIRE_LEVELS(levels)                                                                                        \
+    NM_REQUIRE(levels >= 1 && levels <= NM_MESH_SIMPLIFY_MAX_LEVELS, "mesh simplify: levels must be in [1, 8]")
+
+int nm_mesh_simplify_adaptive_level(const float* d_verts, int64_t num_vertices, const int32_t* d_faces, int64_t num_faces,
+                                    const float* d_normals, float origin_x, float origin_y, float origin_z, float cell,
+                                    int32_t level, int32_t levels, double max_error, int32_t flags, void* d_workspace,
+                                    void* d_quadric_workspace, void* d_adaptive_workspace, void* stream) {
+    if (require_mesh("mesh simplify", num_vertices, num_faces)) return 2;
+    MS_REQUIRE_GRID(origin_x, origin_y, origin_z, cell);
+    MSA_REQUIRE_LEVELS(levels);
+    NM_REQUIRE(level >= 0 && level <= levels, "mesh simplify: the level must be in [0, levels]");
+    const float cell_l = ldexpf(cell, level);                        // exact: a power of two
+    NM_REQUIRE(ms_finite(cell_l), "mesh simplify: the coarsest cell size must be finite");
+    NM_REQUIRE(max_error >= 0.0, "mesh simplify: the error bound must be >= 0");                  // a NaN fails
+    NM_REQUIRE((flags & ~(NM_MESH_SIMPLIFY_AGGREGATE | NM_MESH_SIMPLIFY_AGGREGATE_FACES)) == 0, "mesh simplify: unknown flags");
+    NM_REQUIRE(d_workspace && d_quadric_workspace && d_adaptive_workspace && (num_vertices == 0 || d_verts) &&
+                   (num_faces == 0 || d_faces), "bad argument");
+    const MsWorkspace w = ms_carve(d_workspace, num_vertices, num_faces);
+    const MsQuadricWorkspace q = msq_carve(d_quadric_workspace, num_vertices);
+    const MsaWorkspace a = msa_carve(d_adaptive_workspace, num_vertices);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = (int)num_vertices;
+    const MsGrid g{{origin_x, origin_y, origin_z}, cell_l};
+    const unsigned vgrid = launch_grid(num_vertices), fgrid = launch_grid(num_faces);
+    // tol_l in lattice units of this level's cell, squared: four fp64 operations in this order
+    const double cell64 = (double)cell_l;
+    const double in_cells = max_error / cell64;
+    const double tol = in_cells * MSQ_LATTICE;
+    const double tol2 = tol * tol;
+    if (level == levels) {                                           // the first level of a run: nothing is assigned yet
+        NM_HIP_CHECK(hipMemsetAsync(a.hdr, 0, sizeof(MsaHeader), s));
+        if (nv) NM_HIP_CHECK(hipMemsetAsync(a.stage.level, 0xff, (size_t)nv, s));
+    }
+    // the face table and the keep words are the final faces' (nm_mesh_simplify_adaptive_faces): only level 0 clears them
+    const uint64_t fcap = level == 0 ? w.fcap : 0;
+    const int64_t nvw = level == 0 ? w.bits.nvw : 0;
+    const uint64_t most = w.cap > fcap ? w.cap : fcap;
+    hipLaunchKernelGGL(ms_init, dim3((unsigned)(most / 256 > 4096 ? 4096 : most / 256 ? most / 256 : 1)), dim3(256), 0, s, w.table,
+                       w.cap, w.ftab, fcap, w.bits.vwords, nvw, w.hdr);
+    NM_HIP_CHECK(hipGetLastError());
+    NM_HIP_CHECK(hipMemsetAsync(d_quadric_workspace, 0, (size_t)q.bytes, s));
+    if (!nv) return 0;
+    if (flags & NM_MESH_SIMPLIFY_AGGREGATE)
+        hipLaunchKernelGGL(ms_insert<true>, dim3(vgrid), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.cap, w.slot_of,
+                           w.rep, w.hdr);
+    else
+        hipLaunchKernelGGL(ms_insert<false>, dim3(vgrid), dim3(256), 0, s, d_verts, d_normals, nv, g, w.table, w.cap, w.slot_of,
+                           w.rep, w.hdr);
+    NM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(ms_representatives, dim3(vgrid), dim3(256), 0, s, w.table, w.slot_of, w.rep, nv, w.hdr);
+    NM_HIP_CHECK(hipGetLastError());
+    const bool aggregate = flags & NM_MESH_SIMPLIFY_AGGREGATE_FACES;
+    if (num_faces) {
+        if (aggregate)
+            hipLaunchKernelGGL(ms_quadric_faces<true>, dim3(fgrid), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, g, w.slot_of,
+                               w.rep, q.cap, q.quad, q.hdr);
+        else
+            hipLaunchKernelGGL(ms_quadric_faces<false>, dim3(fgrid), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, g, w.slot_of,
+                               w.rep, q.cap, q.quad, q.hdr);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(msa_place, dim3((unsigned)(w.cap / 256 ? w.cap / 256 : 1)), dim3(256), 0, s, (const MsSlot*)w.table, w.cap,
+                       q.quad);
+    NM_HIP_CHECK(hipGetLastError());
+    if (num_faces && level > 0) {
+        if (aggregate)
+            hipLaunchKernelGGL(msa_error<true>, dim3(fgrid), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, g, w.slot_of, w.rep,
+                               q.cap, q.quad);
+        else
+            hipLaunchKernelGGL(msa_error<false>, dim3(fgrid), dim3(256), 0, s, d_verts, d_faces, num_faces, nv, g, w.slot_of, w.rep,
+                               q.cap, q.quad);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(msa_assign, dim3(vgrid), dim3(256), 0, s, d_verts, d_normals, nv, g, (int)level, tol2,
+                       (const MsSlot*)w.table, (const MsQuadric*)q.quad, w.slot_of, (const int*)w.rep, a.stage, a.hdr);
+    NM_HIP_CHECK(hipGetLastError());
+    if (level == 0)
+        NM_HIP_CHECK(hipMemcpyAsync(&a.hdr->far, &q.hdr->far, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+int nm_mesh_simplify_adaptive_faces(const int32_t* d_faces, int64_t num_faces, int64_t num_vertices, int32_t levels,
+                                    void* d_workspace, void* d_adaptive_workspace, int64_t* h_counts, void* stream) {
+    if (require_mesh("mesh simplify", num_vertices, num_faces)) return 2;
+    MSA_REQUIRE_LEVELS(levels);
+    NM_REQUIRE(d_workspace && d_adaptive_workspace && h_counts && (num_faces == 0 || d_faces), "bad argument");
+    const MsWorkspace w = ms_carve(d_workspace, num_vertices, num_faces);
+    const MsaWorkspace a = msa_carve(d_adaptive_workspace, num_vertices);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = (int)num_vertices;
+    const unsigned fgrid = launch_grid(num_faces);
+    if (num_faces) {
+        hipLaunchKernelGGL(ms_insert_faces, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, (const int*)a.stage.rep, w.ftab,
+                           w.fcap, w.fslot);
+        NM_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(ms_mark, dim3(fgrid), dim3(256), 0, s, d_faces, num_faces, nv, (const int*)a.stage.rep,
+                           (const int*)w.ftab, (const uint32_t*)w.fslot, w.bits.fwords, w.bits.vwords, w.hdr);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    if (const int rc = subset_scan(w.bits, w.hdr->totals, s)) return rc;
+    MsHeader h;
+    MsaHeader ah;
+    NM_HIP_CHECK(hipMemcpyAsync(&h, w.hdr, sizeof(MsHeader), hipMemcpyDeviceToHost, s));
+    NM_HIP_CHECK(hipMemcpyAsync(&ah, a.hdr, sizeof(MsaHeader), hipMemcpyDeviceToHost, s));
+    NM_HIP_CHECK(hipStreamSynchronize(s));
+    unsigned long long clusters = 0;
+    for (int l = 0; l <= levels; ++l) {
+        clusters += ah.level[l][MSA_CLUSTERS];
+        for (int k = 0; k < MSA_LEVEL_FIELDS; ++k)
+            h_counts[NM_MESH_SIMPLIFY_COUNTS + l * NM_MESH_SIMPLIFY_LEVEL_FIELDS + k] = (int64_t)ah.level[l][k];
+    }
+    h_counts[NM_MESH_SIMPLIFY_CLUSTERS] = (int64_t)clusters;
+    h_counts[NM_MESH_SIMPLIFY_VERTICES_KEPT] = (int64_t)h.totals[0];
+    h_counts[NM_MESH_SIMPLIFY_FACES_KEPT] = (int64_t)h.totals[1];
+    h_counts[NM_MESH_SIMPLIFY_DEGENERATE] = (int64_t)h.degenerate;
+    h_counts[NM_MESH_SIMPLIFY_DUPLICATE] = (int64_t)h.duplicate;
+    h_counts[NM_MESH_SIMPLIFY_BAD_VERTICES] = (int64_t)h.bad_vertices;
+    h_counts[NM_MESH_SIMPLIFY_BAD_FACES] = (int64_t)h.bad_faces;
+    return 0;
+}
+
+int nm_mesh_simplify_adaptive_emit(const void* d_workspace, void* d_adaptive_workspace, const int32_t* d_faces, int64_t num_faces,
+                                   int64_t num_vertices, int32_t levels, int32_t with_normals, int64_t vertices_kept,
+                                   int64_t faces_kept, float* d_out_verts, int32_t* d_out_faces, float* d_out_normals,
+                                   int64_t* h_counts, void* stream) {
+    if (require_mesh("mesh simplify", num_vertices, num_faces)) return 2;
+    MSA_REQUIRE_LEVELS(levels);
+    NM_REQUIRE_COMPACT_OUTPUTS("mesh simplify", d_workspace && d_adaptive_workspace && h_counts && (num_faces == 0 || d_faces),
+                               d_out_verts && (!with_normals || d_out_normals));
+    const MsWorkspace w = ms_carve(d_workspace, num_vertices, num_faces);
+    const MsaWorkspace a = msa_carve(d_adaptive_workspace, num_vertices);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nv = (int)num_vertices;
+    NM_HIP_CHECK(hipMemsetAsync(a.hdr->kept, 0, sizeof(a.hdr->kept) + sizeof(a.hdr->status), s));   // the counts of this call
+    if (vertices_kept) {
+        hipLaunchKernelGGL(msa_emit, dim3(launch_grid(num_vertices)), dim3(256), 0, s, nv, (int)levels, a.stage, with_normals != 0,
+                           (const unsigned long long*)w.bits.vwords, (const uint32_t*)w.bits.vprefix, vertices_kept, d_out_verts,
+                           d_out_normals, a.hdr);
+        NM_HIP_CHECK(hipGetLastError());
+    }
+    if (const int rc = subset_compact_faces(d_faces, num_faces, nv, faces_kept, w.bits, a.stage.rep, d_out_faces, nullptr, s))
+        return rc;
+    MsaHeader ah;
+    NM_HIP_CHECK(hipMemcpyAsync(&ah, a.hdr, sizeof(MsaHeader), hipMemcpyDeviceToHost, s));
+    NM_HIP_CHECK(hipStreamSynchronize(s));
+    for (int k = 0; k < 4; ++k) h_counts[k] = (int64_t)ah.status[k];
+    h_counts[NM_MESH_SIMPLIFY_QUADRIC_FAR] = (int64_t)ah.far;
+    for (int l = 0; l <= levels; ++l) h_counts[NM_MESH_SIMPLIFY_QUADRIC_COUNTS + l] = (int64_t)ah.kept[l];
     return 0;
 }
 

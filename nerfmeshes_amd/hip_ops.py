@@ -4,6 +4,8 @@ Every function takes/returns torch CUDA(HIP) fp32 tensors, launches on torch's c
 raises if the HIP library is unavailable or an input is on the CPU -- no silent fallback.
 """
 import ctypes as C
+import math
+import struct
 
 import numpy as np
 import torch
@@ -802,7 +804,56 @@ SIMPLIFY_PLACEMENTS = ("mean", "quadric")
 SIMPLIFY_QUADRIC_COUNTS = ("quadric_clusters", "crowded_clusters", "singular_clusters", "clamped_clusters", "far_corners")
 
 
-def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=None, placement="mean"):
+SIMPLIFY_MAX_LEVELS = 8                  # NM_MESH_SIMPLIFY_MAX_LEVELS
+SIMPLIFY_LEVEL_FIELDS = ("level_vertices", "level_clusters", "refused_error", "refused_crowded", "refused_singular",
+                         "refused_far", "refused_empty")         # NM_MESH_SIMPLIFY_LEVEL_* order; then the largest d2's bits
+SIMPLIFY_ADAPTIVE_KEYS = ("levels",) + SIMPLIFY_LEVEL_FIELDS + ("level_kept", "largest_error")
+
+
+def _simplify_adaptive(lib, verts, faces, normals, nv, nf, dev, cell, origin, aggregate, levels, max_error):
+    """mesh_simplify with levels > 0: nm_mesh_simplify_adaptive_level for level = levels .. 0, then _faces (the counts; the
+    first read-back) and _emit (the second)."""
+    ws = _mesh_workspace(int(lib.nm_mesh_simplify_workspace_bytes(nv, nf)), "mesh simplify", nv, nf, dev)
+    quadrics = _mesh_workspace(int(lib.nm_mesh_simplify_quadric_workspace_bytes(nv, nf)), "mesh simplify", nv, nf, dev)
+    staged = _mesh_workspace(int(lib.nm_mesh_simplify_adaptive_workspace_bytes(nv, nf)), "mesh simplify", nv, nf, dev)
+    flags = (1 if (SIMPLIFY_AGGREGATE if aggregate is None else aggregate) else 0) | \
+            (2 if (SIMPLIFY_QUADRIC_AGGREGATE if aggregate is None else aggregate) else 0)
+    for level in range(levels, -1, -1):
+        rc = lib.nm_mesh_simplify_adaptive_level(_ptr(verts), nv, _ptr(faces), nf, _ptr(normals), *origin, cell, level, levels,
+                                                 max_error, flags, _ptr(ws), _ptr(quadrics), _ptr(staged), _stream())
+        _mesh_check(lib, rc, "nm_mesh_simplify_adaptive_level")
+    fields = len(SIMPLIFY_LEVEL_FIELDS) + 1
+    counts = (C.c_int64 * (7 + (SIMPLIFY_MAX_LEVELS + 1) * fields))()
+    rc = lib.nm_mesh_simplify_adaptive_faces(_ptr(faces), nf, nv, levels, _ptr(ws), _ptr(staged), counts, _stream())
+    _mesh_check(lib, rc, "nm_mesh_simplify_adaptive_faces")
+    clusters, kv, kf, degenerate, duplicate, bad_v, bad_f = (int(x) for x in counts[:7])
+    if bad_v:
+        raise ValueError(f"mesh simplify: {bad_v} vertices have a non-finite coordinate or a cell index outside [0, {SIMPLIFY_CELLS})")
+    if bad_f:
+        raise ValueError(f"mesh simplify: {bad_f} faces have a vertex index outside [0, {nv})")
+    out_verts, out_faces, out_normals, _, _ = _mesh_subset_outputs(kv, kf, dev, normals)
+    tally = (C.c_int64 * (len(SIMPLIFY_QUADRIC_COUNTS) + SIMPLIFY_MAX_LEVELS + 1))()
+    rc = lib.nm_mesh_simplify_adaptive_emit(_ptr(ws), _ptr(staged), _ptr(faces), nf, nv, levels, int(normals is not None), kv, kf,
+                                            _ptr(out_verts), _ptr(out_faces), _ptr(out_normals), tally, _stream())
+    _mesh_check(lib, rc, "nm_mesh_simplify_adaptive_emit")
+    info = dict(vertices=nv, faces=nf, clusters=clusters, vertices_kept=kv, faces_kept=kf, degenerate_faces=degenerate,
+                duplicate_faces=duplicate)
+    info.update(zip(SIMPLIFY_QUADRIC_COUNTS, (int(x) for x in tally)))
+    rows = [[int(x) for x in counts[7 + l * fields:7 + (l + 1) * fields]] for l in range(levels + 1)]
+    info["levels"] = levels
+    for k, name in enumerate(SIMPLIFY_LEVEL_FIELDS):
+        info[name] = tuple(row[k] for row in rows)
+    info["level_kept"] = tuple(int(x) for x in tally[len(SIMPLIFY_QUADRIC_COUNTS):len(SIMPLIFY_QUADRIC_COUNTS) + levels + 1])
+    # the largest error of a chosen cluster in the units of `cell`: sqrt(d2) lattice units of 1 / 2^8 of that level's cell
+    largest = 0.0
+    for l in range(1, levels + 1):
+        d2 = struct.unpack("<d", struct.pack("<q", rows[l][-1]))[0]
+        largest = max(largest, math.sqrt(d2) / 256.0 * (cell * 2.0 ** l))
+    info["largest_error"] = largest
+    return out_verts, out_faces, out_normals, info
+
+
+def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=None, placement="mean", levels=0, max_error=None):
     """Vertex clustering on the device (nm_mesh_simplify_cluster + _emit; semantics in include/nerfmeshes_hip.h): the vertices in
     one cell of the grid (origin, cell) become one vertex -- the exact mean of its members, a single member unchanged bit for bit
     --, degenerate and duplicate faces go (opposite windings are not duplicates), and so do the clusters no face is left on.
@@ -815,8 +866,14 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     its cell nearest to the planes of the faces around it, from exact integer quadrics, instead of at the mean -- the same
     faces, numbering and normals -- and adds to info the kept clusters placed so (quadric_clusters, the clamped_clusters among
     them moved back into their cell), those left at the mean (crowded_clusters: more than 2^13 face corners; singular_clusters)
-    and far_corners, the face corners with an edge longer than two cells, which contribute nothing."""
-    lib = _lib.load()
+    and far_corners, the face corners with an edge longer than two cells, which contribute nothing.
+    levels = L > 0 (at most 8; placement="quadric" only) with max_error = E >= 0 in the units of `cell` (inf allowed) is adaptive
+    clustering (nm_mesh_simplify_adaptive_*): the same clustering on the nested grids of cell * 2^l, l = 0 .. L, every vertex in
+    the coarsest cell whose quadric vertex lies within E of every triangle plane around it, level 0 always allowed.  info gains
+    levels, per level (tuples of L + 1) level_vertices, level_clusters, the clusters refused there by reason (refused_error,
+    refused_crowded, refused_singular, refused_far, refused_empty) and level_kept, and largest_error, the largest plane distance
+    of a chosen cluster of a level >= 1 in the units of `cell`; the quadric counts are of the kept clusters at their level.
+    levels = 0 is the call without the two arguments, whatever max_error is."""
     if placement not in SIMPLIFY_PLACEMENTS:
         raise ValueError(f"mesh_simplify: placement must be one of {SIMPLIFY_PLACEMENTS}, got {placement!r}")
     if cell is None:
@@ -824,6 +881,20 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     cell = float(np.float32(cell))
     if not (np.isfinite(cell) and cell > 0):
         raise ValueError(f"mesh_simplify: the cell size must be finite and > 0, got {cell}")
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 0 <= levels <= SIMPLIFY_MAX_LEVELS:
+        raise ValueError(f"mesh_simplify: levels must be an integer in [0, {SIMPLIFY_MAX_LEVELS}], got {levels!r}")
+    levels = int(levels)
+    if levels:
+        if placement != "quadric":
+            raise ValueError(f"mesh_simplify: levels = {levels} needs placement='quadric', got {placement!r}")
+        if max_error is None:
+            raise ValueError("mesh_simplify: max_error is required with levels > 0")
+        max_error = float(max_error)
+        if not max_error >= 0.0:
+            raise ValueError(f"mesh_simplify: max_error must be >= 0, got {max_error}")
+        if cell * 2.0 ** levels > float(np.finfo(np.float32).max):
+            raise ValueError(f"mesh_simplify: the coarsest cell size {cell} * 2^{levels} must be finite")
+    lib = _lib.load()
     verts, faces, normals, _, _, nv, nf, dev = _mesh_inputs("mesh_simplify", verts, faces, normals)
     if origin is None:
         # the minimum of the finite coordinates: a NaN or infinite vertex is reported below with its count, not as a bad origin
@@ -832,6 +903,8 @@ def mesh_simplify(verts, faces, normals=None, cell=None, origin=None, aggregate=
     origin = [float(np.float32(x)) for x in (origin.tolist() if isinstance(origin, (torch.Tensor, np.ndarray)) else origin)]
     if len(origin) != 3 or not all(np.isfinite(x) for x in origin):
         raise ValueError(f"mesh_simplify: the origin must be three finite numbers, got {origin}")
+    if levels:
+        return _simplify_adaptive(lib, verts, faces, normals, nv, nf, dev, cell, origin, aggregate, levels, max_error)
     ws = _mesh_workspace(int(lib.nm_mesh_simplify_workspace_bytes(nv, nf)), "mesh simplify", nv, nf, dev)
     counts = (C.c_int64 * 7)()
     flags = 1 if (SIMPLIFY_AGGREGATE if aggregate is None else aggregate) else 0

@@ -468,12 +468,17 @@ def simplify_mesh(vertices, triangles, normals, cell_voxels, args):
     res) world units, anchored at (-limit,)*3 -- the vertices of one cell become their exact mean (one alone stays bit for bit),
     degenerate and duplicate triangles go, kept ones stay in their order.  `--simplify-placement quadric` puts the vertex of a
     cell where the planes of the triangles around it meet instead (exact integer quadrics: the same bytes on every rank), which
-    keeps creases and curved surfaces where they are.  ValueError when no triangle is left."""
-    cell = float(cell_voxels) * (2.0 * args.limit / args.res)
+    keeps creases and curved surfaces where they are.  `--simplify-levels L` with `--simplify-error E` (voxels) makes the
+    clustering adaptive: the same on the nested grids of K * 2^l voxels, l = 0 .. L, every vertex in the coarsest cell whose
+    quadric vertex lies within E of every triangle plane around it.  ValueError when no triangle is left."""
+    voxel = 2.0 * args.limit / args.res
+    cell = float(cell_voxels) * voxel
     v0, f0 = vertices.shape[0], triangles.shape[0]
     placement = getattr(args, "simplify_placement", "mean")
+    levels = int(getattr(args, "simplify_levels", 0))
+    adaptive = dict(levels=levels, max_error=float(getattr(args, "simplify_error", SIMPLIFY_ERROR_DEFAULT)) * voxel) if levels else {}
     vertices, triangles, normals, info = hip_ops.mesh_simplify(vertices, triangles.to(torch.int32), normals, cell=cell,
-                                                               origin=(-args.limit,) * 3, placement=placement)
+                                                               origin=(-args.limit,) * 3, placement=placement, **adaptive)
     if info["faces_kept"] == 0:
         raise ValueError(f"--simplify-cell {cell_voxels:g} leaves no triangle of {f0}: every one has two corners in one cell "
                          f"({info['clusters']} clusters of {v0} vertices)")
@@ -483,6 +488,16 @@ def simplify_mesh(vertices, triangles, normals, cell_voxels, args):
         print(f"Simplify placement: quadric: {info['quadric_clusters']} clusters at their quadric's minimum "
               f"({info['clamped_clusters']} clamped to the cell), at the mean: {info['crowded_clusters']} crowded, "
               f"{info['singular_clusters']} singular; {info['far_corners']} far corners")
+    if levels:
+        print(f"Simplify levels: {levels} (cells of {cell_voxels:g} to {cell_voxels * 2 ** levels:g} voxels), error bound "
+              f"{args.simplify_error:g} voxels, largest accepted error {info['largest_error'] / voxel:.4f} voxels")
+        for l in range(levels, -1, -1):
+            refused = ("" if l == 0 else
+                       f"; refused: {info['refused_error'][l]} error, {info['refused_crowded'][l]} crowded, "
+                       f"{info['refused_singular'][l]} singular, {info['refused_far'][l]} far, "
+                       f"{info['refused_empty'][l]} no contributions")
+            print(f"Simplify level {l}: {info['level_vertices'][l]} vertices in {info['level_clusters'][l]} clusters, "
+                  f"{info['level_kept'][l]} kept{refused}")
     return vertices, triangles, normals
 
 
@@ -537,6 +552,26 @@ def _target_surface_valid(o):
     except ValueError:
         return False
     return bool(o["target_mesh"])
+
+
+# --simplify-error's default, in voxels: half of the tighter of the two distances the surface reports score at (F-score at half
+# a voxel and at one), so a vertex that uses the whole bound still leaves every triangle plane around it well inside that
+# band; it is also the accuracy uniform clustering with 4-voxel cells reaches on the synthetic scene (0.26 voxels, README)
+SIMPLIFY_ERROR_DEFAULT = 0.25
+
+
+def _simplify_levels_invalid(o):
+    """the refusal of --simplify-levels L != 0 with the other simplify options as they are, or None"""
+    levels, error = int(o["simplify_levels"]), float(o["simplify_error"])
+    if not 0 <= levels <= hip_ops.SIMPLIFY_MAX_LEVELS:
+        return f"--simplify-levels must be in [0, {hip_ops.SIMPLIFY_MAX_LEVELS}], got {levels}"
+    if not 0.0 < float(o["simplify_cell"]) < float("inf"):
+        return f"--simplify-levels {levels} needs --simplify-cell K > 0"
+    if o["simplify_placement"] != "quadric":
+        return f"--simplify-levels {levels} needs --simplify-placement quadric"
+    if not 0.0 <= error < float("inf"):
+        return f"--simplify-error must be finite and >= 0, got {error}"
+    return None
 
 
 TSDF_OPTIONS = {"geometry": "density", "tsdf_views": 32, "tsdf_size": 800, "tsdf_radius": 4.0, "tsdf_focal": 0.0, "tsdf_trunc": 3.0,
@@ -597,6 +632,15 @@ FEATURES = {
                            if float(o["simplify_cell"]) == 0.0 else
                            f"--simplify-cell must be finite and >= 0, got {float(o['simplify_cell'])}"),
         run=lambda v, t, n, o, args: simplify_mesh(v, t, n, float(o["simplify_cell"]), args)),
+    "simplify_levels": Feature(
+        "--simplify-levels / --simplify-error",
+        {"simplify_levels": 0, "simplify_error": SIMPLIFY_ERROR_DEFAULT, "simplify_cell": 0.0, "simplify_placement": "mean"},
+        # options of "simplify", which runs the stage: checked, never switched on; the cell and the placement are among the
+        # options because the levels are valid only with them ("simplify", which comes first, speaks for the two themselves).
+        # --simplify-error is read only with levels > 0: without them it is not even range-checked
+        on=lambda o: False, any_option=True,
+        valid=lambda o: int(o["simplify_levels"]) == 0 or _simplify_levels_invalid(o) is None,
+        invalid=lambda o: _simplify_levels_invalid(o)),
     "target": Feature(
         "--target-mesh", {"target_mesh": None, "chamfer_samples": 100000}, on=lambda o: o["target_mesh"],
         valid=lambda o: int(o["chamfer_samples"]) >= 1,
@@ -876,6 +920,14 @@ def build_parser():
                         "mean; quadric is the point of the cell nearest to the planes of the triangles around it (exact integer "
                         "quadrics, a regularised 3 x 3 solve per cell), which keeps creases and curved surfaces where they are; "
                         "needs --simplify-cell")
+    p.add_argument("--simplify-levels", type=_non_negative, default=0,
+                   help="(addition) adaptive clustering: also cluster on this many coarser grids, each of twice the cell before, "
+                        "and let every vertex join the coarsest cell whose vertex lies within --simplify-error of every triangle "
+                        "plane around it; at most 8; needs --simplify-cell and --simplify-placement quadric (0 = off)")
+    p.add_argument("--simplify-error", type=_cell_size, default=SIMPLIFY_ERROR_DEFAULT,
+                   help="(addition) the error bound of --simplify-levels in voxels, finite and >= 0 (default "
+                        f"{SIMPLIFY_ERROR_DEFAULT}: half of the half-voxel distance the surface reports score at); read only with "
+                        "--simplify-levels > 0")
     p.add_argument("--cull-hidden-views", type=_non_negative, default=0,
                    help="(addition) drop the faces no outside camera sees: rasterise the mesh on the GPU from this many cameras "
                         "spread evenly over a sphere around it and keep the faces that win a pixel in at least one view; after "
